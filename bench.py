@@ -2,7 +2,7 @@
 """
 bench.py -- GFLOP/s of the DG-wave p=4 grad einsum on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload grad|div|facemass|graddiv|pipeline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload grad|div|facemass|graddiv|pipeline] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -26,6 +26,11 @@ element + 29 400 B for D) / mean kernel time from the HIP events.
 ``protocol_ms_per_step`` is the same launch timed with the reference's own
 protocol (5 warm-ups, batches of 5, >= 10 launches and >= 2 s;
 src/feinsum/measure.py:248-275) right after the timed region.
+
+``--dump-outputs DIR`` writes the output arrays of the last timed step as
+DIR/<stage>[_<k>].npy (float64), under 64 MB in all: beyond that, the same
+seeded sample of elements in every run.  The inputs depend on the arguments
+only (seeded), so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -49,6 +54,10 @@ SETUP_SECONDS = 0.5            # ... and continued until this much time has pass
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 FP64_PEAK_GFLOPS = 78_600.0    # fp64 vector = matrix
 WORKLOADS = ("grad", "div", "facemass", "graddiv", "pipeline")
+STAGES = {"grad": ("grad",), "div": ("div",), "facemass": ("facemass",), "graddiv": ("div", "grad"),
+          "pipeline": ("div", "grad", "facemass")}      # the einsums of each workload, in launch order
+DUMP_MAX_BYTES = 60_000_000    # --dump-outputs: the arrays together at most this large (the files: under 64 MB) ...
+DUMP_SAMPLE_SEED = 2024        # ... beyond it, this seed picks the elements kept (dump_sample)
 
 
 def _einsums():
@@ -62,8 +71,8 @@ def _einsums():
         "ef,fij,fej->ei",
         [[f.array("Jf", ("E", NF)), f.array("L", (NF, NP, NFP)), f.array(f"w{k}", (NF, "E", NFP))]
          for k in range(NFIELDS)])
-    return {"grad": [grad], "div": [div], "facemass": [fm], "graddiv": [div, grad],
-            "pipeline": [div, grad, fm]}
+    by_name = {"grad": grad, "div": div, "facemass": fm}
+    return {w: [by_name[s] for s in STAGES[w]] for w in WORKLOADS}
 
 
 def _device_inputs(expr, E, device, seed):
@@ -206,6 +215,56 @@ def compose_line(*, workload, n_gpus, steps, warmup, setup_launches=SETUP_LAUNCH
     }
     line.update(extra)
     return line
+
+
+# --------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step
+# --------------------------------------------------------------------------
+
+def dump_sample(E: int, bytes_per_element: int, max_bytes: int = DUMP_MAX_BYTES):
+    """Element indices the dump keeps: None (all E) if the outputs of E elements fit *max_bytes*, else as many as fit,
+    drawn without repetition by DUMP_SAMPLE_SEED and sorted -- the same for every run with the same E."""
+    import numpy as np
+
+    keep = max_bytes // max(bytes_per_element, 1)
+    if E <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(E, size=keep, replace=False))
+
+
+def output_samples(workload: str, exprs, out_dicts, E: int, max_bytes: int = DUMP_MAX_BYTES):
+    """Host copies of the output arrays, by file name (``<stage>``, or ``<stage>_<k>`` for the k-th output of a batched
+    stage), each cut to the elements of dump_sample() along its element axis.  Returns (arrays, indices or None)."""
+    import torch
+
+    import feinsum_amd as f
+
+    items = []
+    for stage, expr, od in zip(STAGES[workload], exprs, out_dicts):
+        axis = [i for i, d in enumerate(expr.shape) if isinstance(d, f.SizeParam)][0]
+        for k, name in enumerate(expr.output_names):
+            items.append((stage if len(expr.output_names) == 1 else f"{stage}_{k}", od[name], axis))
+    per_element = sum(math.prod(n for i, n in enumerate(t.shape) if i != axis) * t.element_size() for _, t, axis in items)
+    idx = dump_sample(E, per_element, max_bytes)
+    arrays = {}
+    for fname, t, axis in items:
+        if idx is not None:
+            t = t.index_select(axis, torch.from_numpy(idx).to(t.device))
+        arrays[fname] = t.cpu().numpy()
+    return arrays, idx
+
+
+def write_dump(directory, arrays, idx, E: int) -> dict:
+    """``<directory>/<name>.npy`` for every array; returns what the JSON line says about them."""
+    import numpy as np
+
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    return {"dir": str(d), "files": sorted(f"{n}.npy" for n in arrays), "bytes": sum(a.nbytes for a in arrays.values()),
+            "elements": E if idx is None else len(idx), "of_elements": E,
+            "sample_seed": None if idx is None else DUMP_SAMPLE_SEED}
 
 
 # --------------------------------------------------------------------------
@@ -580,7 +639,12 @@ def main() -> None:
                          "the rate on stderr (SURVEY 8e's optional full-field exchange; never part of `value`)")
     ap.add_argument("--spawn-timeout", type=float, default=3000.0,
                     help="--gpus N started without a launcher: seconds the N rank processes may take")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's outputs) as DIR/<name>.npy, float64; above "
+                         f"{DUMP_MAX_BYTES // 10**6} MB in all, a fixed seeded sample of the elements (bench.dump_sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` without RANK / WORLD_SIZE: this process becomes the parent of N ranks (no torch.cuda, no
     # HIP call here) and exits with their verdict; under torch.distributed.run the ranks arrive with their environment set
@@ -733,6 +797,8 @@ def main() -> None:
     timed = timed_region(step_batch, args.steps, sync, device, keep_busy)
     wall_s, kernel_s = timed["wall"], timed["kernel"]
     launch_info = _hip.last_launch_info()      # what the launcher decided for the timed launches (fe_last_launch_info)
+    # the outputs of the last timed step, copied before the A/B launches below run on the same arrays
+    dump = output_samples(args.workload, exprs, out_dicts, E) if args.dump_outputs and info.rank == 0 else None
     pool_r = placement_report.get("pool") or {}
     per_rank = gather_rank_reports({"elements": E, "kernel_ms": timed["local_kernel"] / args.steps * 1e3, "wall_ms": timed["local_wall"] / args.steps * 1e3,
                                     "placement_mode": ("split" if placement_report.get("mode") == "split" else
@@ -865,6 +931,8 @@ def main() -> None:
                                  "launches": protocol_ms["launches"],
                                  "host_ms_per_step": round(protocol_ms["host"], 5)}
             extra["device_under_load"] = device_under_load
+        if dump is not None:
+            extra["dump_outputs"] = write_dump(args.dump_outputs, *dump, E)
         line = compose_line(workload=args.workload, n_gpus=info.world_size, steps=args.steps, warmup=args.warmup,
                             setup_launches=setup_launches,
                             wall_s=wall_s, kernel_s=kernel_s, flops_step_all=flops_all, flops_step_rank0=flops_step,

@@ -106,3 +106,81 @@ def test_bench_spawns_its_own_ranks():
     assert "self-spawned" in line["launcher"] and line["result_finite"] and line["value"] > 0
     assert line["config"]["elements_total"] == 2 * line["config"]["elements_per_gpu"]
     assert [r["rank"] for r in line["per_rank"]] == [0, 1] and all(r["kernel_ms"] > 0 and r["placement_mode"] == "separate" for r in line["per_rank"])
+
+
+def _oracle_of_dump(workload, E, idx):
+    """What the dump of rank 0 must hold: the oracle on bench.py's own seeded inputs (bench.main: stage k drawn with seed k,
+    div and grad sharing J and D), cut to the dumped elements *idx* (None: all)."""
+    import numpy as np
+    import torch
+
+    import bench
+    import feinsum_amd as f
+    from oracle import np_oracle
+
+    shared, want = {}, {}
+    for k, (stage, expr) in enumerate(zip(bench.STAGES[workload], bench._einsums()[workload])):
+        dev = bench._device_inputs(expr, E, torch.device("cuda", 0), seed=k)
+        for name in ("J", "R"):
+            if name in dev:
+                dev[name] = shared.setdefault(name, dev[name])
+        host = {}
+        for name, t in dev.items():
+            axes = [i for i, d in enumerate(expr.arg_to_shape[name]) if isinstance(d, f.SizeParam)]
+            host[name] = t.cpu().numpy() if idx is None or not axes else np.take(t.cpu().numpy(), idx, axis=axes[0])
+        refs = np_oracle.reference_outputs(expr.get_subscripts(), [[host[a.name] for a in row] for row in expr.args])
+        for j, ref in enumerate(refs):
+            want[stage if len(refs) == 1 else f"{stage}_{j}"] = ref
+    return want
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_sampled_and_repeatable(tmp_path):
+    """--dump-outputs at a size whose outputs exceed the budget: the seeded sample, the same bits from a second run whose
+    outputs come from the other allocator, and the oracle's values on those elements."""
+    import numpy as np
+
+    import bench
+
+    E = 200_000                                   # grad: 168 MB of output, above the 64 MiB budget
+    lines = []
+    for run, placement in (("a", "separate"), ("b", "split")):
+        small = [a for a in SMALL if a not in ("--placement", "separate")]
+        small[small.index("20000")] = str(E)
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "grad", "--placement", placement,
+               "--dump-outputs", str(tmp_path / run)] + small
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(_json_line(out.stdout))
+    rep = lines[0]["dump_outputs"]
+    idx = bench.dump_sample(E, 3 * 35 * 8)
+    assert rep["files"] == ["grad.npy"] and rep["elements"] == len(idx) and rep["of_elements"] == E
+    assert rep["bytes"] <= bench.DUMP_MAX_BYTES and rep["sample_seed"] == bench.DUMP_SAMPLE_SEED
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) < 64 * 10**6
+    got = np.load(tmp_path / "a" / "grad.npy")
+    assert got.dtype == np.float64 and got.shape == (3, len(idx), 35)
+    assert np.array_equal(got, np.load(tmp_path / "b" / "grad.npy"))
+    from oracle import np_oracle
+
+    assert np_oracle.max_rel_err(got, _oracle_of_dump("grad", E, idx)["grad"]) <= 1e-12
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_whole_pipeline(tmp_path):
+    """A pipeline whose outputs fit the budget is dumped whole: all six output arrays, each the oracle's."""
+    import numpy as np
+
+    from oracle import np_oracle
+
+    E = 20_000
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "pipeline", "--dump-outputs", str(tmp_path)] + SMALL
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rep = _json_line(out.stdout)["dump_outputs"]
+    assert rep["elements"] == E and rep["sample_seed"] is None
+    want = _oracle_of_dump("pipeline", E, None)
+    assert sorted(rep["files"]) == sorted(f"{n}.npy" for n in want) and len(want) == 6
+    for name, ref in want.items():
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == ref.shape, name
+        assert np_oracle.max_rel_err(got, ref) <= 1e-12, name
