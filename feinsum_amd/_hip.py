@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = (
     "fe_grad_f64", "fe_div_f64",
     "fe_graddiv3d_f64", "fe_waveop3d_f64",
     "fe_facemass_f64",
-    "fe_flops_per_element", "fe_time_launches", "fe_einsum_generic", "fe_kernel_resources",
+    "fe_flops_per_element", "fe_time_launches", "fe_einsum_generic", "fe_einsum_contract", "fe_einsum_contract_groups", "fe_kernel_resources",
     "fe_prepare_operator", "fe_grad3d_prepared_f64", "fe_div3d_prepared_f64", "fe_facemass_prepared_f64",
     "fe_graddiv3d_prepared_f64", "fe_waveop3d_prepared_f64", "fe_divcomp_f64", "fe_release_prepared",
     "fe_split_alloc", "fe_split_free", "fe_split_info", "fe_split_stats", "fe_split_reserve", "fe_split_trim", "fe_launch_f32", "fe_set_tail_rounds", "fe_set_tail_min_rounds",
@@ -233,6 +233,11 @@ def load_library() -> C.CDLL:
     lib.fe_einsum_generic.restype = C.c_int
     lib.fe_einsum_generic.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_void_p), C.c_void_p,
                                       C.c_void_p]
+    lib.fe_einsum_contract.restype = C.c_int
+    lib.fe_einsum_contract.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_void_p), C.c_void_p,
+                                       C.c_void_p]
+    lib.fe_einsum_contract_groups.restype = C.c_int
+    lib.fe_einsum_contract_groups.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _lib = lib
     return lib
 
@@ -431,6 +436,63 @@ def time_launches(family: int, pack: ArgPack, n_launches: int, stream: int = 0) 
 
 def einsum_generic(desc: EinsumDesc, operands: Sequence[int], out: int, stream: int = 0) -> None:
     check(load_library().fe_einsum_generic(C.byref(desc), _ptr_array(operands), out, stream))
+
+
+def einsum_desc(in_idxs: Sequence[str], out_idxs: Sequence[str], sum_idxs: Sequence[str], extent, tensors: Sequence,
+                float64: bool) -> EinsumDesc:
+    """The descriptor of ``fe_einsum_generic`` / ``fe_einsum_contract`` for operands *tensors* (torch tensors, any strides)
+    whose axes carry the indices *in_idxs* (one string per operand); the output is C-contiguous in *out_idxs* order.
+    A repeated index adds its strides."""
+    if len(in_idxs) > FE_MAX_EINSUM_OPERANDS or len(out_idxs) > FE_MAX_EINSUM_INDICES \
+            or len(sum_idxs) > FE_MAX_EINSUM_INDICES:
+        raise NotImplementedError("einsum has more operands / indices than the generic kernel supports")
+    out_idxs, sum_idxs = list(out_idxs), list(sum_idxs)
+    d = EinsumDesc()
+    d.n_operands, d.n_out, d.n_sum = len(in_idxs), len(out_idxs), len(sum_idxs)
+    d.dtype = 0 if float64 else 1
+    for k, idx in enumerate(out_idxs):
+        d.out_extent[k] = extent[idx]
+    for k, idx in enumerate(sum_idxs):
+        d.sum_extent[k] = extent[idx]
+    for p, (t, idxs) in enumerate(zip(tensors, in_idxs)):
+        strides = t.stride()
+        for axis, idx in enumerate(idxs):
+            if idx in out_idxs:
+                d.op_out_stride[p][out_idxs.index(idx)] += strides[axis]
+            else:
+                d.op_sum_stride[p][sum_idxs.index(idx)] += strides[axis]
+    return d
+
+
+def time_with_events(launch, n: int, stream_ptr: int) -> float:
+    """Seconds for *n* calls of ``launch(stream_ptr)``, by HIP events recorded on that stream."""
+    import torch
+
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    stream = torch.cuda.ExternalStream(stream_ptr) if stream_ptr else torch.cuda.current_stream()
+    t0.record(stream)
+    for _ in range(n):
+        launch(stream_ptr)
+    t1.record(stream)
+    t1.synchronize()
+    return t0.elapsed_time(t1) * 1e-3
+
+
+CONTRACT_GROUP_NAMES = {-1: "dropped", 0: "batch", 1: "m", 2: "n", 3: "k"}   # FE_CONTRACT_*
+
+
+def einsum_contract_groups(desc: EinsumDesc):
+    """``(output groups, summed groups)``: the index groups ``fe_einsum_contract`` forms for *desc* (host only), by name
+    (``CONTRACT_GROUP_NAMES``)."""
+    og, sg = (C.c_int32 * FE_MAX_EINSUM_INDICES)(), (C.c_int32 * FE_MAX_EINSUM_INDICES)()
+    check(load_library().fe_einsum_contract_groups(C.byref(desc), og, sg))
+    return (tuple(CONTRACT_GROUP_NAMES[og[k]] for k in range(desc.n_out)),
+            tuple(CONTRACT_GROUP_NAMES[sg[k]] for k in range(desc.n_sum)))
+
+
+def einsum_contract(desc: EinsumDesc, operands: Sequence[int], out: int, stream: int = 0) -> None:
+    """Two-operand einsum on the matrix cores (``fe_einsum_contract``); same descriptor as :func:`einsum_generic`."""
+    check(load_library().fe_einsum_contract(C.byref(desc), _ptr_array(operands), out, stream))
 
 
 def set_tail_rounds(rounds: int) -> int:

@@ -1,0 +1,265 @@
+// fe_contract.h -- strided batched tensor contraction (GETT) on the matrix cores.
+// Any two-operand einsum is, after its indices are grouped (host: fe_einsum_contract),
+//   C[b, m, n] = sum_k A[b, m, k] * B[b, n, k]
+// with b, m, n, k multi-indices of up to FE_MAX_EINSUM_INDICES einsum indices, each with its own
+// element strides per operand (0 = the operand does not carry the index).  The class of einsum the
+// reference's TTGT / COGENT transforms take (tuning/impls/ttgt.py, cogent.py), on
+// v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32.
+//
+// Block: 256 threads, a 64 x 64 tile of C (2 x 2 waves of 32 x 32, four 16 x 16 accumulators per
+// wave); k in steps of 16 through LDS, two buffers: the global loads of step s + 1 are in flight
+// in registers while the MFMAs of step s read LDS.  The grid is persistent and 1-D over
+// (batch, m tile, n tile), so a batch count of 10^6 needs no gridDim.y / z.
+//
+// Loads: each thread owns ONE k column per operand and 4 / V groups of V elements along the
+// operand's fast direction -- V consecutive k of one row (k-fast) or V consecutive rows at one k
+// (m-fast).  The row offsets are decoded once per tile, the k offset by an odometer that is
+// advanced by 16 per step (a division only when an index wraps).  V > 1 only when the fast
+// direction's innermost extent is a multiple of V (so a group never straddles an index or the
+// ragged edge); the group is then one vector load when its stride is 1 and the host found the
+// operand 16-byte aligned, V strided scalar loads otherwise.  All offsets are int64.
+#pragma once
+#include "fe_common.h"
+
+namespace fe {
+
+constexpr int kCtMaxIdx = 8;     // FE_MAX_EINSUM_INDICES
+constexpr int kCtBM = 64;        // rows of a C tile (m) = columns (n)
+constexpr int kCtBK = 16;        // k per LDS step
+constexpr int kCtThreads = 256;
+constexpr int kCtBlocksPerCu = 2;
+
+// The grouped einsum (filled by the host; by value in the kernel arguments).
+struct ContractPlan {
+    int32_t nb, nm, nn, nk;              // indices per group (innermost last)
+    int32_t a_mfast, b_mfast;            // operand walks its rows (1) or its k (0) fastest
+    int32_t a_vec, b_vec;                // V-groups are single vector loads
+    int64_t a_vstep, b_vstep;            // element stride inside a V-group
+    int64_t M, N, K, tiles_m, tiles_n, n_tiles;
+    int64_t b_ext[kCtMaxIdx], b_sa[kCtMaxIdx], b_sb[kCtMaxIdx], b_sc[kCtMaxIdx];
+    int64_t m_ext[kCtMaxIdx], m_sa[kCtMaxIdx], m_sc[kCtMaxIdx];
+    int64_t n_ext[kCtMaxIdx], n_sb[kCtMaxIdx], n_sc[kCtMaxIdx];
+    int64_t k_ext[kCtMaxIdx], k_sa[kCtMaxIdx], k_sb[kCtMaxIdx];
+};
+
+template <typename T>
+struct CtMfma;
+// C/D layouts differ: f64 row = (lane >> 4) + 4 reg, f32 row = 4 (lane >> 4) + reg; col = lane & 15 for both.
+template <>
+struct CtMfma<double> {
+    typedef double acc_t __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ acc_t step(double a, double b, acc_t c) {
+        return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
+};
+template <>
+struct CtMfma<float> {
+    typedef float acc_t __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ acc_t step(float a, float b, acc_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
+};
+
+// Offsets of linear position x of a group (last index fastest) under up to three stride sets.
+__device__ __forceinline__ void ct_decode(int64_t x, int n, const int64_t* ext, const int64_t* s0, const int64_t* s1,
+                                          const int64_t* s2, int64_t& o0, int64_t& o1, int64_t& o2) {
+    o0 = o1 = o2 = 0;
+#pragma unroll
+    for (int t = 0; t < kCtMaxIdx; ++t) {
+        const int j = n - 1 - t;
+        if (j >= 0) {
+            const int64_t q = x / ext[j];
+            const int64_t r = x - q * ext[j];
+            o0 += r * s0[j];
+            o1 += r * s1[j];
+            o2 += r * s2[j];
+            x = q;
+        }
+    }
+}
+
+// k odometer: idx[t] is the position in index n - 1 - t (registers: t is a compile-time constant).
+__device__ __forceinline__ void ct_advance(int64_t (&idx)[kCtMaxIdx], int n, const int64_t* ext, int64_t carry) {
+#pragma unroll
+    for (int t = 0; t < kCtMaxIdx; ++t) {
+        const int j = n - 1 - t;
+        if (j >= 0 && carry != 0) {
+            const int64_t v = idx[t] + carry;
+            if (v < ext[j]) {
+                idx[t] = v;
+                carry = 0;
+            } else {
+                carry = v / ext[j];
+                idx[t] = v - carry * ext[j];
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ int64_t ct_koff(const int64_t (&idx)[kCtMaxIdx], int n, const int64_t* s) {
+    int64_t o = 0;
+#pragma unroll
+    for (int t = 0; t < kCtMaxIdx; ++t)
+        if (n - 1 - t >= 0) o += idx[t] * s[n - 1 - t];
+    return o;
+}
+
+template <typename T, int V>
+__global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan P, const T* __restrict__ A,
+                                                                   const T* __restrict__ B, T* __restrict__ C) {
+    typedef CtMfma<T> Mfma;
+    typedef typename Mfma::acc_t acc_t;
+    typedef T vec_t __attribute__((ext_vector_type(V)));
+    constexpr int R = 4 / V;                       // V-groups per thread and operand
+    constexpr int RSTEP = 16 * V;                  // rows between a thread's groups
+    constexpr int LD = kCtBM + 64 / (int)sizeof(T);   // padded LDS row: k rows 0..3 of an MFMA read hit distinct banks
+    __shared__ T lds[2][2][kCtBK][LD];             // [buffer][A, B][k][row]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    // loading slot of operand X: its k column kk and first row rr
+    const int kkA = P.a_mfast ? tid >> 4 : V * (tid % (16 / V));
+    const int rrA = P.a_mfast ? V * (tid & 15) : tid / (16 / V);
+    const int kkB = P.b_mfast ? tid >> 4 : V * (tid % (16 / V));
+    const int rrB = P.b_mfast ? V * (tid & 15) : tid / (16 / V);
+    const int64_t nsteps = (P.K + kCtBK - 1) / kCtBK;
+
+    for (int64_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
+        const int64_t tn = tile % P.tiles_n, rest = tile / P.tiles_n;
+        const int64_t tm = rest % P.tiles_m, bi = rest / P.tiles_m;
+        const int64_t m0 = tm * kCtBM, n0 = tn * kCtBM;
+        int64_t boffA, boffB, boffC;
+        ct_decode(bi, P.nb, P.b_ext, P.b_sa, P.b_sb, P.b_sc, boffA, boffB, boffC);
+
+        int64_t rowA[R], rowB[R], unused0, unused1;
+        bool rvA[R], rvB[R];
+#pragma unroll
+        for (int g = 0; g < R; ++g) {
+            const int64_t ra = m0 + rrA + g * RSTEP, rb = n0 + rrB + g * RSTEP;
+            rvA[g] = ra < P.M;
+            rvB[g] = rb < P.N;
+            rowA[g] = rowB[g] = 0;
+            if (rvA[g]) ct_decode(ra, P.nm, P.m_ext, P.m_sa, P.m_sa, P.m_sa, rowA[g], unused0, unused1);
+            if (rvB[g]) ct_decode(rb, P.nn, P.n_ext, P.n_sb, P.n_sb, P.n_sb, rowB[g], unused0, unused1);
+        }
+
+        int64_t kiA[kCtMaxIdx], kiB[kCtMaxIdx];
+#pragma unroll
+        for (int t = 0; t < kCtMaxIdx; ++t) kiA[t] = kiB[t] = 0;
+        if (nsteps > 0) {   // (an extent of 0 would divide by zero)
+            ct_advance(kiA, P.nk, P.k_ext, kkA);
+            ct_advance(kiB, P.nk, P.k_ext, kkB);
+        }
+
+        T ra[R][V], rb[R][V];
+        auto load = [&](int64_t k0) {
+            const int64_t koA = ct_koff(kiA, P.nk, P.k_sa), koB = ct_koff(kiB, P.nk, P.k_sb);
+            const bool kvA = k0 + kkA < P.K, kvB = k0 + kkB < P.K;
+#pragma unroll
+            for (int g = 0; g < R; ++g) {
+                if (rvA[g] && kvA) {
+                    const T* p = A + (boffA + rowA[g] + koA);
+                    if (V > 1 && P.a_vec) {
+                        const vec_t x = *reinterpret_cast<const vec_t*>(p);
+#pragma unroll
+                        for (int v = 0; v < V; ++v) ra[g][v] = x[v];
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < V; ++v) ra[g][v] = p[v * P.a_vstep];
+                    }
+                } else {
+#pragma unroll
+                    for (int v = 0; v < V; ++v) ra[g][v] = T(0);
+                }
+                if (rvB[g] && kvB) {
+                    const T* p = B + (boffB + rowB[g] + koB);
+                    if (V > 1 && P.b_vec) {
+                        const vec_t x = *reinterpret_cast<const vec_t*>(p);
+#pragma unroll
+                        for (int v = 0; v < V; ++v) rb[g][v] = x[v];
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < V; ++v) rb[g][v] = p[v * P.b_vstep];
+                    }
+                } else {
+#pragma unroll
+                    for (int v = 0; v < V; ++v) rb[g][v] = T(0);
+                }
+            }
+        };
+        auto stage = [&](int buf) {
+#pragma unroll
+            for (int g = 0; g < R; ++g)
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    if (P.a_mfast) lds[buf][0][kkA][rrA + g * RSTEP + v] = ra[g][v];
+                    else lds[buf][0][kkA + v][rrA + g * RSTEP] = ra[g][v];
+                    if (P.b_mfast) lds[buf][1][kkB][rrB + g * RSTEP + v] = rb[g][v];
+                    else lds[buf][1][kkB + v][rrB + g * RSTEP] = rb[g][v];
+                }
+        };
+
+        acc_t acc[2][2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int g = 0; g < 2; ++g) acc[f][g] = acc_t{0, 0, 0, 0};
+
+        if (nsteps > 0) {
+            load(0);
+            stage(0);
+            __syncthreads();
+        }
+        for (int64_t s = 0; s < nsteps; ++s) {
+            const int cur = (int)(s & 1);
+            const bool more = s + 1 < nsteps;
+            if (more) {
+                ct_advance(kiA, P.nk, P.k_ext, kCtBK);
+                ct_advance(kiB, P.nk, P.k_ext, kCtBK);
+                load((s + 1) * kCtBK);
+            }
+#pragma unroll
+            for (int ks = 0; ks < kCtBK / 4; ++ks) {
+                const int kr = 4 * ks + (lane >> 4);
+                T a[2], b[2];
+#pragma unroll
+                for (int f = 0; f < 2; ++f) a[f] = lds[cur][0][kr][32 * wm + 16 * f + (lane & 15)];
+#pragma unroll
+                for (int g = 0; g < 2; ++g) b[g] = lds[cur][1][kr][32 * wn + 16 * g + (lane & 15)];
+#pragma unroll
+                for (int f = 0; f < 2; ++f)
+#pragma unroll
+                    for (int g = 0; g < 2; ++g) acc[f][g] = Mfma::step(a[f], b[g], acc[f][g]);
+            }
+            if (more) stage(cur ^ 1);
+            __syncthreads();   // (every tile ends on a barrier: the next tile's first stage may overwrite buffer 0)
+        }
+
+        // C: column (n) on the lane, rows in the registers
+        int64_t colC[2];
+        bool cv[2];
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int64_t col = n0 + 32 * wn + 16 * g + (lane & 15);
+            cv[g] = col < P.N;
+            colC[g] = 0;
+            if (cv[g]) ct_decode(col, P.nn, P.n_ext, P.n_sc, P.n_sc, P.n_sc, colC[g], unused0, unused1);
+        }
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t row = m0 + 32 * wm + 16 * f + Mfma::row(lane, r);
+                if (row >= P.M) continue;
+                int64_t rowC;
+                ct_decode(row, P.nm, P.m_ext, P.m_sc, P.m_sc, P.m_sc, rowC, unused0, unused1);
+#pragma unroll
+                for (int g = 0; g < 2; ++g)
+                    if (cv[g]) C[boffC + rowC + colC[g]] = acc[f][g][r];
+            }
+    }
+}
+
+}  // namespace fe

@@ -13,10 +13,12 @@
 #include <string>
 #include <type_traits>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/feinsum_hip.h"
 #include "fe_common.h"
+#include "fe_contract.h"
 #include "fe_div.h"
 #include "fe_einsum.h"
 #include "fe_facemass.h"
@@ -1350,6 +1352,20 @@ inline bool fm_mfma_geometry(int Np, int nf, int Nfp, FmChoice* c) {
     return false;
 }
 
+// Index groups of a two-operand einsum for fe_einsum_contract, from the descriptor's strides alone: an output index
+// carried by A and B (nonzero stride), or by neither (a broadcast), is batch; by A only m; by B only n; a summed index
+// is k; an index of extent 1 adds nothing to any offset and is dropped (FE_CONTRACT_DROPPED).
+void contract_groups(const fe_einsum_desc* d, int32_t* out_group, int32_t* sum_group) {
+    for (int k = 0; k < d->n_out; ++k) {
+        const bool a = d->op_out_stride[0][k] != 0, b = d->op_out_stride[1][k] != 0;
+        out_group[k] = d->out_extent[k] == 1 ? FE_CONTRACT_DROPPED
+                       : a == b              ? FE_CONTRACT_BATCH
+                       : a                   ? FE_CONTRACT_M
+                                             : FE_CONTRACT_N;
+    }
+    for (int k = 0; k < d->n_sum; ++k) sum_group[k] = d->sum_extent[k] == 1 ? FE_CONTRACT_DROPPED : FE_CONTRACT_K;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2171,6 +2187,157 @@ int fe_einsum_generic(const fe_einsum_desc* d, const void* const* operands, void
     }
 #undef FE_EINSUM_CASE
     FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, void* out, void* stream) {
+    if (!d || !operands) return fail(FE_EINVAL, "contract: null descriptor");
+    if (d->n_operands != 2)
+        return fail(FE_EUNSUPPORTED, "contract: %d operands (the contraction kernel takes exactly 2)", d->n_operands);
+    if (d->n_out < 0 || d->n_out > FE_MAX_EINSUM_INDICES || d->n_sum < 0 || d->n_sum > FE_MAX_EINSUM_INDICES)
+        return fail(FE_EINVAL, "contract: %d output / %d summation indices out of range", d->n_out, d->n_sum);
+    if (d->dtype != FE_DTYPE_F64 && d->dtype != FE_DTYPE_F32)
+        return fail(FE_EUNSUPPORTED, "contract: dtype code %d not compiled (float64 / float32 only)", d->dtype);
+    int64_t n_out = 1;
+    for (int k = 0; k < d->n_out; ++k) {
+        if (d->out_extent[k] < 0) return fail(FE_EINVAL, "contract: negative extent");
+        n_out *= d->out_extent[k];
+    }
+    for (int k = 0; k < d->n_sum; ++k)
+        if (d->sum_extent[k] < 0) return fail(FE_EINVAL, "contract: negative extent");
+    if (n_out == 0) return FE_OK;
+    if (!out) return fail(FE_EINVAL, "contract: null output pointer");
+    if (n_out >= ((int64_t)1 << 39)) return fail(FE_EINVAL, "contract: output too large");
+    const bool f64 = d->dtype == FE_DTYPE_F64;
+    const size_t esize = f64 ? 8 : 4;
+    if (reinterpret_cast<uintptr_t>(out) % esize)
+        return fail(FE_EINVAL, "contract: output pointer not aligned to its element size");
+
+    // Group the indices (contract_groups); the output's innermost index of extent > 1 decides the orientation
+    int32_t og[FE_MAX_EINSUM_INDICES], sg[FE_MAX_EINSUM_INDICES];
+    contract_groups(d, og, sg);
+    fe::ContractPlan P;
+    memset(&P, 0, sizeof(P));
+    int64_t sc = 1;
+    char tail = 0;   // group of the output's innermost index of extent > 1: 'b', 'm' or 'n'
+    int64_t oc[FE_MAX_EINSUM_INDICES];
+    for (int k = d->n_out - 1; k >= 0; --k) {
+        oc[k] = sc;
+        sc *= d->out_extent[k];
+    }
+    for (int k = 0; k < d->n_out; ++k) {
+        const int64_t e = d->out_extent[k], sa = d->op_out_stride[0][k], sb = d->op_out_stride[1][k];
+        if (og[k] == FE_CONTRACT_BATCH) {
+            P.b_ext[P.nb] = e, P.b_sa[P.nb] = sa, P.b_sb[P.nb] = sb, P.b_sc[P.nb] = oc[k], ++P.nb;
+            tail = 'b';
+        } else if (og[k] == FE_CONTRACT_M) {
+            P.m_ext[P.nm] = e, P.m_sa[P.nm] = sa, P.m_sc[P.nm] = oc[k], ++P.nm;
+            tail = 'm';
+        } else if (og[k] == FE_CONTRACT_N) {
+            P.n_ext[P.nn] = e, P.n_sb[P.nn] = sb, P.n_sc[P.nn] = oc[k], ++P.nn;
+            tail = 'n';
+        }
+    }
+    bool empty_k = false;
+    int korder[FE_MAX_EINSUM_INDICES], nk = 0;
+    for (int k = 0; k < d->n_sum; ++k) {
+        if (d->sum_extent[k] == 0) empty_k = true;
+        if (sg[k] == FE_CONTRACT_K) korder[nk++] = k;
+    }
+    // the output's contiguous index goes on the MFMA column (n): lanes store consecutive addresses
+    const void* opA = operands[0];
+    const void* opB = operands[1];
+    int ia = 0, ib = 1;
+    if (tail == 'm') {
+        std::swap(opA, opB);
+        std::swap(ia, ib);
+        std::swap(P.nm, P.nn);
+        for (int j = 0; j < FE_MAX_EINSUM_INDICES; ++j) {
+            std::swap(P.m_ext[j], P.n_ext[j]);
+            std::swap(P.m_sa[j], P.n_sb[j]);
+            std::swap(P.m_sc[j], P.n_sc[j]);
+            std::swap(P.b_sa[j], P.b_sb[j]);
+        }
+    }
+    // summed indices: largest stride outermost, so that a unit-stride k index is the innermost one
+    auto kkey = [&](int k) {
+        const int64_t a = std::abs(d->op_sum_stride[ia][k]), b = std::abs(d->op_sum_stride[ib][k]);
+        return a > b ? a : b;
+    };
+    for (int i = 1; i < nk; ++i)
+        for (int j = i; j > 0 && kkey(korder[j - 1]) < kkey(korder[j]); --j) std::swap(korder[j - 1], korder[j]);
+    P.nk = nk;
+    P.K = empty_k ? 0 : 1;
+    for (int j = 0; j < nk; ++j) {
+        P.k_ext[j] = d->sum_extent[korder[j]];
+        P.k_sa[j] = d->op_sum_stride[ia][korder[j]];
+        P.k_sb[j] = d->op_sum_stride[ib][korder[j]];
+        P.K *= P.k_ext[j];
+    }
+    if (P.K > 0 && (!opA || !opB)) return fail(FE_EINVAL, "contract: null operand");
+    if ((reinterpret_cast<uintptr_t>(opA) | reinterpret_cast<uintptr_t>(opB)) % esize)
+        return fail(FE_EINVAL, "contract: operand pointer not aligned to its element size");
+    P.M = P.N = 1;
+    int64_t nbatch = 1;
+    for (int j = 0; j < P.nm; ++j) P.M *= P.m_ext[j];
+    for (int j = 0; j < P.nn; ++j) P.N *= P.n_ext[j];
+    for (int j = 0; j < P.nb; ++j) nbatch *= P.b_ext[j];
+
+    // fast direction of each operand: its rows when its innermost row index is contiguous and its innermost k is not
+    const int mlast = P.nm - 1, nlast = P.nn - 1, klast = nk - 1;
+    P.a_mfast = mlast >= 0 && P.m_sa[mlast] == 1 && !(klast >= 0 && P.k_sa[klast] == 1);
+    P.b_mfast = nlast >= 0 && P.n_sb[nlast] == 1 && !(klast >= 0 && P.k_sb[klast] == 1);
+    const int64_t fastA = P.a_mfast ? P.m_ext[mlast] : (klast >= 0 ? P.k_ext[klast] : 1);
+    const int64_t fastB = P.b_mfast ? P.n_ext[nlast] : (klast >= 0 ? P.k_ext[klast] : 1);
+    P.a_vstep = P.a_mfast ? P.m_sa[mlast] : (klast >= 0 ? P.k_sa[klast] : 0);
+    P.b_vstep = P.b_mfast ? P.n_sb[nlast] : (klast >= 0 ? P.k_sb[klast] : 0);
+    const int vmax = f64 ? 2 : 4;   // 16-byte groups
+    const int V = (fastA % vmax == 0 && fastB % vmax == 0) ? vmax : 1;
+    // one vector load per group: unit stride inside it, a 16-byte aligned base, every other stride a multiple of V
+    auto vec_ok = [&](const void* p, bool mfast, int64_t vstep, const int64_t* sb_, const int64_t* srow, int nrow,
+                      const int64_t* sk) {
+        if (V == 1 || vstep != 1 || reinterpret_cast<uintptr_t>(p) % (V * esize)) return false;
+        for (int j = 0; j < P.nb; ++j) if (sb_[j] % V) return false;
+        for (int j = 0; j < nrow; ++j) if (srow[j] % V && !(mfast && j == nrow - 1)) return false;
+        for (int j = 0; j < nk; ++j) if (sk[j] % V && !(!mfast && j == nk - 1)) return false;
+        return true;
+    };
+    P.a_vec = vec_ok(opA, P.a_mfast, P.a_vstep, P.b_sa, P.m_sa, P.nm, P.k_sa);
+    P.b_vec = vec_ok(opB, P.b_mfast, P.b_vstep, P.b_sb, P.n_sb, P.nn, P.k_sb);
+
+    P.tiles_m = (P.M + fe::kCtBM - 1) / fe::kCtBM;
+    P.tiles_n = (P.N + fe::kCtBM - 1) / fe::kCtBM;
+    P.n_tiles = nbatch * P.tiles_m * P.tiles_n;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t cap = (int64_t)fe::kCtBlocksPerCu * device_cu_count();
+    const dim3 grid((unsigned)(P.n_tiles < cap ? P.n_tiles : cap)), block(fe::kCtThreads);
+#define FE_CONTRACT_CASE(T, VV, NAME)                                                                                   \
+    do {                                                                                                                \
+        static PerDeviceOnce once;                                                                                      \
+        if (int rc = configured(once, fe::contract_mfma_kernel<T, VV>, NAME, 0, fe::kCtThreads, fe::kCtBlocksPerCu))   \
+            return rc;                                                                                                  \
+        hipLaunchKernelGGL((fe::contract_mfma_kernel<T, VV>), grid, block, 0, s, P, static_cast<const T*>(opA),        \
+                           static_cast<const T*>(opB), static_cast<T*>(out));                                          \
+    } while (0)
+    if (f64) {
+        if (V > 1) FE_CONTRACT_CASE(double, 2, "contract f64 (16-byte groups)");
+        else FE_CONTRACT_CASE(double, 1, "contract f64");
+    } else {
+        if (V > 1) FE_CONTRACT_CASE(float, 4, "contract f32 (16-byte groups)");
+        else FE_CONTRACT_CASE(float, 1, "contract f32");
+    }
+#undef FE_CONTRACT_CASE
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+int fe_einsum_contract_groups(const fe_einsum_desc* d, int32_t* out_group, int32_t* sum_group) {
+    if (!d || !out_group || !sum_group) return fail(FE_EINVAL, "contract groups: null pointer");
+    if (d->n_operands != 2)
+        return fail(FE_EUNSUPPORTED, "contract groups: %d operands (the contraction kernel takes exactly 2)", d->n_operands);
+    if (d->n_out < 0 || d->n_out > FE_MAX_EINSUM_INDICES || d->n_sum < 0 || d->n_sum > FE_MAX_EINSUM_INDICES)
+        return fail(FE_EINVAL, "contract groups: %d output / %d summation indices out of range", d->n_out, d->n_sum);
+    contract_groups(d, out_group, sum_group);
     return FE_OK;
 }
 

@@ -22,7 +22,8 @@ Argument conventions kept from the reference:
                exist in this build, so a callable (or ``None``) is ignored and
                selects the default kernel variant, while a ``str`` / ``dict``
                (``"mfma"``, ``"generic"``, ``{"variant": "generic"}``) selects
-               a variant explicitly; in a dict, ``"prepared": True`` lets a
+               a variant explicitly (``"contraction"``: the einsum as strided batched
+               contractions on the matrix cores, ``feinsum_amd.contraction``); in a dict, ``"prepared": True`` lets a
                bound launch (``timeit``) use a prepared copy of its operator
                matrices; ``"placement"`` (or ``$FEINSUM_PLACEMENT``): ``timeit``
                allocates one array per operand as the reference does; with the
@@ -30,7 +31,8 @@ Argument conventions kept from the reference:
                (``feinsum_amd.placement.zeros``; ``evaluate`` allocates the outputs it
                is not handed the same way), ``"separate"`` takes every array
                from torch; ``timeit_details(...).placement`` reports which was used.
-``schedule``   accepted and ignored: the kernels implement the optimal schedule.
+``schedule``   followed by the ``"contraction"`` transform (default: the optimal one); the
+               other kernels implement the optimal schedule and ignore it.
 
 Inputs are drawn from ``numpy.random.default_rng(0)`` in **sorted argument-name
 order** (the reference draws in hash order, which is not reproducible).
@@ -48,6 +50,7 @@ from typing import Any, Dict, Mapping, Optional, Sequence, Tuple
 import numpy as np
 
 from feinsum_amd import _hip
+from feinsum_amd.contraction import ContractionLaunch, auto_picks_contraction
 from feinsum_amd.contraction_schedule import ContractionSchedule, count_ops
 from feinsum_amd.diagnostics import (HipLibraryError, InvalidParameterError,
                                      NoDevicePeaksInfoError, TransformValidationError)
@@ -424,41 +427,42 @@ class _GenericLaunch:
         self._keep = (arg_dict, outs)
         self.launches = []
         for row, out in zip(einsum.args, outs):
-            d = _hip.EinsumDesc()
-            d.n_operands, d.n_out, d.n_sum = einsum.n, len(einsum.out_idx_set), len(einsum.sum_indices)
-            d.dtype = 0 if dtype == np.dtype("float64") else 1
-            for k, idx in enumerate(einsum.out_idx_set):
-                d.out_extent[k] = extent[idx]
-            for k, idx in enumerate(einsum.sum_indices):
-                d.sum_extent[k] = extent[idx]
-            for p, (arg, idxs) in enumerate(zip(row, einsum.in_idx_sets)):
-                strides = arg_dict[arg.name].stride()
-                for axis, idx in enumerate(idxs):
-                    if idx in einsum.out_idx_set:
-                        d.op_out_stride[p][einsum.out_idx_set.index(idx)] += strides[axis]
-                    else:
-                        d.op_sum_stride[p][einsum.sum_indices.index(idx)] += strides[axis]
-            self.launches.append((d, [arg_dict[a.name].data_ptr() for a in row], out.data_ptr()))
+            tensors = [arg_dict[a.name] for a in row]
+            d = _hip.einsum_desc(einsum.in_idx_sets, einsum.out_idx_set, einsum.sum_indices, extent, tensors,
+                                 dtype == np.dtype("float64"))
+            self.launches.append((d, [t.data_ptr() for t in tensors], out.data_ptr()))
 
     def launch(self, stream_ptr: int) -> None:
         for d, ops, out in self.launches:
             _hip.einsum_generic(d, ops, out, stream_ptr)
 
     def time_batch(self, n: int, stream_ptr: int) -> float:
-        import torch
+        return _hip.time_with_events(self.launch, n, stream_ptr)
 
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        stream = torch.cuda.ExternalStream(stream_ptr) if stream_ptr else torch.cuda.current_stream()
-        t0.record(stream)
-        for _ in range(n):
-            self.launch(stream_ptr)
-        t1.record(stream)
-        t1.synchronize()
-        return t0.elapsed_time(t1) * 1e-3
+
+def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int]) -> str:
+    """
+    Which kernels run *einsum* under *transform* (size parameters *sizes*): ``"contraction"`` (the transform of that
+    name, or ``"auto"`` on a two-operand einsum outside the DG families where ``contraction.auto_picks_contraction``
+    says the contraction kernel wins), ``"family"`` (a DG family kernel) or ``"generic"``.
+    """
+    variant = _variant_from_transform(transform)
+    if variant == "contraction":
+        return "contraction"
+    if match_family(einsum) is not None:
+        return "family"
+    if variant not in (None, "auto", "generic", 0, 1):
+        raise NotImplementedError(
+            f"einsum '{einsum.get_subscripts()}' is outside the DG kernel families;"
+            " only the generic and contraction kernels are available for it")
+    if variant in (None, "auto", 0) and auto_picks_contraction(einsum, sizes):
+        return "contraction"
+    return "generic"
 
 
 def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
-          out_dict: Optional[Mapping[str, Any]], transform: Any, prepare: bool = False):
+          out_dict: Optional[Mapping[str, Any]], transform: Any, prepare: bool = False,
+          schedule: Optional[ContractionSchedule] = None):
     import torch
 
     q = _as_queue(cq)
@@ -481,18 +485,15 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
             tensor, how = _allocate_output(out_shape, getattr(torch, dt.name), q.torch_device, transform)
             outs.append(tensor)
             allocated[name] = how
-    plan = match_family(einsum)
-    variant = _variant_from_transform(transform)
-    if plan is not None:
-        bound = _FamilyLaunch(plan, einsum, arg_dict, outs, variant)
+    kind = launch_kind(einsum, transform, sizes)
+    if kind == "contraction":
+        bound = ContractionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
+    elif kind == "family":
+        bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform))
         if _prepared_from_transform(transform, prepare):
             with torch.cuda.device(q.torch_device):
                 bound.prepare_operators(q.stream_ptr)
     else:
-        if variant not in (None, "auto", "generic", 0, 1):
-            raise NotImplementedError(
-                f"einsum '{einsum.get_subscripts()}' is outside the DG kernel families;"
-                " only the generic kernel is available for it")
         bound = _GenericLaunch(einsum, arg_dict, outs)
     # byte ranges the launch reads and writes (operator.py checks them before reordering launches)
     span = lambda t: (int(t.data_ptr()), int(t.numel()) * int(t.element_size()))   # noqa: E731
@@ -535,16 +536,16 @@ def _allocate_output(shape: Tuple[int, ...], dtype: Any, device: Any, transform:
 
 def evaluate(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *,
              out_dict: Optional[Mapping[str, Any]] = None, transform: Any = None,
-             wait: bool = False) -> Mapping[str, Any]:
+             wait: bool = False, schedule: Optional[ContractionSchedule] = None) -> Mapping[str, Any]:
     """
     Enqueue *einsum* on the queue's stream and return ``{"_fe_out": tensor, ...}``
     (the replacement for ``t_unit.executor(cq, ...)(cq, **arg_dict)``,
     reference measure.py:163-165).  Asynchronous unless *wait*; outputs are
-    fully overwritten.
+    fully overwritten.  *schedule*: see the module docstring.
     """
     import torch
 
-    q, bound, outs = _bind(einsum, cq, arg_dict, out_dict, transform)
+    q, bound, outs = _bind(einsum, cq, arg_dict, out_dict, transform, schedule=schedule)
     with torch.cuda.device(q.torch_device):
         bound.launch(q.stream_ptr)
     if wait:
@@ -574,7 +575,6 @@ def validate_batched_einsum_transform(einsum: BatchedEinsum, cq: Any, transform:
     :class:`~feinsum_amd.diagnostics.TransformValidationError` on mismatch.
     (reference: measure.py:111-194)
     """
-    del schedule
     long_dim_length = 100
     q = _as_queue(cq)
     host = generate_host_input_arrays(einsum, long_dim_length)
@@ -584,7 +584,7 @@ def validate_batched_einsum_transform(einsum: BatchedEinsum, cq: Any, transform:
     ref_outs = {name: np.einsum(einsum.get_subscripts(), *[host[arg.name] for arg in row],
                                 optimize="optimal")
                 for name, row in zip(einsum.output_names, einsum.args)}
-    outs = evaluate(einsum, q, arg_dict, transform=transform, wait=True)
+    outs = evaluate(einsum, q, arg_dict, transform=transform, wait=True, schedule=schedule)
     if set(ref_outs) != set(outs):
         raise RuntimeError("Output names mismatch")
     for name in sorted(ref_outs):
@@ -674,7 +674,7 @@ def timeit_details(einsum: BatchedEinsum, *, transform: Any = None, cq: Any = No
     # `transform={"prepared": True}`: the operator matrices are written once in fragment layout (see
     # _FamilyLaunch.prepare_operators) instead of being rebuilt by every launch
     prepare = _prepared_from_transform(transform, False)
-    _, bound, _ = _bind(einsum, q, arg_dict, out_dict, transform, prepare=prepare)
+    _, bound, _ = _bind(einsum, q, arg_dict, out_dict, transform, prepare=prepare, schedule=schedule)
     with torch.cuda.device(q.torch_device):
         for _ in range(N_WARMUP_ROUNDS):
             bound.launch(q.stream_ptr)

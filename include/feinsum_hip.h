@@ -522,6 +522,23 @@ typedef struct fe_einsum_ptrs {
 int fe_einsum_generic(const fe_einsum_desc* desc, const void* const* operands,
                       void* out, void* stream);
 
+/* Same descriptor, operands and output contract as fe_einsum_generic; n_operands must be 2
+ * (FE_EUNSUPPORTED otherwise).  Evaluated on the matrix cores as a strided batched contraction
+ * C[b,m,n] = sum_k A[b,m,k] B[b,n,k] (feinsum_amd/csrc/fe_contract.h): an output index carried by both
+ * operands (or by neither) is a batch index, one carried by one operand an m / n index, every summed
+ * index a k index.  Operands of any strides (8-byte alignment suffices); asynchronous on `stream`, no
+ * allocation.  A summed extent of 0 writes zeros; an empty output launches nothing. */
+int fe_einsum_contract(const fe_einsum_desc* desc, const void* const* operands, void* out, void* stream);
+
+/* The index groups fe_einsum_contract forms for `desc` (host only, no device work): out_group[k] for output index k,
+ * sum_group[k] for summed index k, each FE_CONTRACT_*; m / n are named before the launcher's orientation swap. */
+#define FE_CONTRACT_DROPPED -1 /* extent 1: adds nothing to any offset */
+#define FE_CONTRACT_BATCH    0 /* output index carried by both operands, or by neither (a broadcast) */
+#define FE_CONTRACT_M        1 /* output index carried by operand 0 only */
+#define FE_CONTRACT_N        2 /* output index carried by operand 1 only */
+#define FE_CONTRACT_K        3 /* summed index */
+int fe_einsum_contract_groups(const fe_einsum_desc* desc, int32_t* out_group, int32_t* sum_group);
+
 #ifdef __cplusplus
 }
 #endif
