@@ -15,6 +15,8 @@ import os
 from pathlib import Path
 from typing import Optional, Sequence
 
+import numpy as np
+
 from feinsum_amd.diagnostics import HipLibraryError, InvalidParameterError
 
 FE_OK, FE_EINVAL, FE_EUNSUPPORTED, FE_EHIP = 0, -1, -2, -3
@@ -61,6 +63,14 @@ class ArgPack(C.Structure):
 
 FE_MAX_EINSUM_OPERANDS = 8
 FE_MAX_EINSUM_INDICES = 8
+FE_DTYPE_F64 = 0
+FE_DTYPE_F32 = 1
+FE_DTYPE_OPERAND_F32_MASK = ((1 << FE_MAX_EINSUM_OPERANDS) - 1) << 8
+
+
+def FE_DTYPE_OPERAND_F32(p: int) -> int:   # noqa: N802  (the header's macro)
+    """Flag of an einsum descriptor's dtype: operand *p* is stored as float32 (with ``FE_DTYPE_F64`` only)."""
+    return 1 << (8 + p)
 
 
 class EinsumDesc(C.Structure):
@@ -438,18 +448,30 @@ def einsum_generic(desc: EinsumDesc, operands: Sequence[int], out: int, stream: 
     check(load_library().fe_einsum_generic(C.byref(desc), _ptr_array(operands), out, stream))
 
 
+def einsum_dtype_code(float64: bool, operand_dtypes: Optional[Sequence] = None) -> int:
+    """The ``dtype`` field of an einsum descriptor: ``FE_DTYPE_F64`` / ``FE_DTYPE_F32``, and with float64 compute one
+    ``FE_DTYPE_OPERAND_F32(p)`` flag per float32 operand p of *operand_dtypes* (numpy dtypes; ``None``: no flags)."""
+    code = FE_DTYPE_F64 if float64 else FE_DTYPE_F32
+    if float64 and operand_dtypes is not None:
+        for p, dt in enumerate(operand_dtypes):
+            if np.dtype(dt) == np.dtype("float32"):
+                code |= FE_DTYPE_OPERAND_F32(p)
+    return code
+
+
 def einsum_desc(in_idxs: Sequence[str], out_idxs: Sequence[str], sum_idxs: Sequence[str], extent, tensors: Sequence,
-                float64: bool) -> EinsumDesc:
+                float64: bool, operand_dtypes: Optional[Sequence] = None) -> EinsumDesc:
     """The descriptor of ``fe_einsum_generic`` / ``fe_einsum_contract`` for operands *tensors* (torch tensors, any strides)
     whose axes carry the indices *in_idxs* (one string per operand); the output is C-contiguous in *out_idxs* order.
-    A repeated index adds its strides."""
+    A repeated index adds its strides.  *operand_dtypes* (with *float64*): the float32 operands of a mixed einsum, which
+    the kernels widen to float64 as they load them (:func:`einsum_dtype_code`)."""
     if len(in_idxs) > FE_MAX_EINSUM_OPERANDS or len(out_idxs) > FE_MAX_EINSUM_INDICES \
             or len(sum_idxs) > FE_MAX_EINSUM_INDICES:
         raise NotImplementedError("einsum has more operands / indices than the generic kernel supports")
     out_idxs, sum_idxs = list(out_idxs), list(sum_idxs)
     d = EinsumDesc()
     d.n_operands, d.n_out, d.n_sum = len(in_idxs), len(out_idxs), len(sum_idxs)
-    d.dtype = 0 if float64 else 1
+    d.dtype = einsum_dtype_code(float64, operand_dtypes)
     for k, idx in enumerate(out_idxs):
         d.out_extent[k] = extent[idx]
     for k, idx in enumerate(sum_idxs):

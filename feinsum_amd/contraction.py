@@ -163,10 +163,43 @@ def intermediate_shapes(steps: Sequence[Step], extent: Mapping[str, int]) -> Dic
             for st in steps if st.result is not None}
 
 
-def _desc(subscripts: str, tensors: Sequence[Any], extent: Mapping[str, int], dtype: np.dtype) -> "_hip.EinsumDesc":
+_REAL = (np.dtype("float64"), np.dtype("float32"))
+
+
+def plan_step_dtypes(einsum: BatchedEinsum, steps: Sequence[Step]) -> Tuple[np.dtype, ...]:
+    """
+    The result dtype of every step of *steps* (``plan_steps``): ``np.result_type`` of the step's own operands, as the
+    reference types each intermediate (codegen/loopy.py:258-260) -- a step over float32 operands stays float32, one
+    that meets a float64 operand is float64.  The intermediates are allocated in these dtypes.  The rows of the einsum
+    share the intermediates, so they must agree: rows whose operands differ in dtype where a step meets them are
+    ``NotImplementedError``, as is any operand that is not float32 or float64.
+    """
+    bad = sorted({str(np.dtype(d)) for d in einsum.arg_to_dtype.values()} - {str(d) for d in _REAL})
+    if bad:
+        raise NotImplementedError(f"the contraction kernel is compiled for float64 / float32 operands; got {bad}")
+    result: Optional[Tuple[np.dtype, ...]] = None
+    for row in einsum.args:
+        tmp: Dict[str, np.dtype] = {}
+        dts = []
+        for st in steps:
+            dt = np.result_type(*[np.dtype(row[x].dtype) if kind == "op" else tmp[x] for kind, x in st.inputs])
+            if st.result is not None:
+                tmp[st.result] = dt
+            dts.append(dt)
+        if result is not None and tuple(dts) != result:
+            raise NotImplementedError("the rows of this einsum would need intermediates of different dtypes")
+        result = tuple(dts)
+    return result or ()
+
+
+def _desc(subscripts: str, tensors: Sequence[Any], extent: Mapping[str, int],
+          operand_dtypes: Sequence[np.dtype]) -> "_hip.EinsumDesc":
+    """Descriptor of one step: ``np.result_type`` of its operands is the compute type; float32 operands of a float64 step
+    are flagged (mixed: the kernels widen them as they load them)."""
     ins, rhs = _split(subscripts)
     sums = [c for c in dict.fromkeys("".join(ins)) if c not in rhs]
-    return _hip.einsum_desc(ins, rhs, sums, extent, tensors, dtype == np.dtype("float64"))
+    return _hip.einsum_desc(ins, rhs, sums, extent, tensors,
+                            np.result_type(*operand_dtypes) == np.dtype("float64"), operand_dtypes)
 
 
 class ContractionLaunch:
@@ -184,27 +217,25 @@ class ContractionLaunch:
 
         import torch
 
-        dtype = _uniform_real_dtype(einsum)
-        if dtype is None:
-            raise NotImplementedError(
-                "the contraction kernel is compiled for all-float64 or all-float32 operands;"
-                f" got {sorted(str(np.dtype(d)) for d in einsum.arg_to_dtype.values())}")
         extent = _extents(einsum, sizes)
         self.steps = plan_steps(einsum, schedule)
+        self.step_dtypes = plan_step_dtypes(einsum, self.steps)
+        tmp_dtype = {st.result: dt for st, dt in zip(self.steps, self.step_dtypes) if st.result is not None}
         device = outs[0].device
-        tdtype = getattr(torch, dtype.name)
-        # intermediates: one set, reused by every row (the rows run one after the other on one stream)
+        # intermediates: one set, reused by every row (the rows run one after the other on one stream), each in the
+        # dtype of its own step (plan_step_dtypes)
         self._stream_ptr = int(stream.cuda_stream) if stream is not None else None
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            self.intermediates = {name: torch.empty(shape, dtype=tdtype, device=device)
+            self.intermediates = {name: torch.empty(shape, dtype=getattr(torch, tmp_dtype[name].name), device=device)
                                   for name, shape in intermediate_shapes(self.steps, extent).items()}
         self._keep = (arg_dict, outs)
         self.launches = []
         for row, out in zip(einsum.args, outs):
             for st in self.steps:
                 tensors = [arg_dict[row[x].name] if kind == "op" else self.intermediates[x] for kind, x in st.inputs]
+                dtypes = [np.dtype(row[x].dtype) if kind == "op" else tmp_dtype[x] for kind, x in st.inputs]
                 target = out if st.result is None else self.intermediates[st.result]
-                d = _desc(st.subscripts, tensors, extent, dtype)
+                d = _desc(st.subscripts, tensors, extent, dtypes)
                 fn = _hip.einsum_contract if len(tensors) == 2 else _hip.einsum_generic
                 self.launches.append((fn, d, [t.data_ptr() for t in tensors], target.data_ptr()))
 

@@ -18,6 +18,11 @@
 // direction's innermost extent is a multiple of V (so a group never straddles an index or the
 // ragged edge); the group is then one vector load when its stride is 1 and the host found the
 // operand 16-byte aligned, V strided scalar loads otherwise.  All offsets are int64.
+//
+// Mixed operands: contract_mfma_kernel<double, VA, TA, TB, VB> with A or B stored as float.  Each operand has its own
+// group width (16 bytes of ITS elements: 4 floats, 2 doubles) and loads its own type; stage() widens a float to double
+// as it writes LDS, so the LDS image, the f64 MFMA loop and the stores are those of the all-double kernel.  With the
+// defaults (TA = TB = T, VB = V) the template is the uniform kernel, instruction for instruction.
 #pragma once
 #include "fe_common.h"
 
@@ -106,24 +111,27 @@ __device__ __forceinline__ int64_t ct_koff(const int64_t (&idx)[kCtMaxIdx], int 
     return o;
 }
 
-template <typename T, int V>
-__global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan P, const T* __restrict__ A,
-                                                                   const T* __restrict__ B, T* __restrict__ C) {
+template <typename T, int V, typename TA = T, typename TB = T, int VB = V>
+__global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan P, const TA* __restrict__ A,
+                                                                   const TB* __restrict__ B, T* __restrict__ C) {
     typedef CtMfma<T> Mfma;
     typedef typename Mfma::acc_t acc_t;
-    typedef T vec_t __attribute__((ext_vector_type(V)));
-    constexpr int R = 4 / V;                       // V-groups per thread and operand
-    constexpr int RSTEP = 16 * V;                  // rows between a thread's groups
+    constexpr int VA = V;
+    typedef TA veca_t __attribute__((ext_vector_type(VA)));
+    typedef TB vecb_t __attribute__((ext_vector_type(VB)));
+    constexpr int RA = 4 / VA, RB = 4 / VB;        // V-groups per thread and operand
+    constexpr int R = RA > RB ? RA : RB;
+    constexpr int RSTEPA = 16 * VA, RSTEPB = 16 * VB;   // rows between a thread's groups
     constexpr int LD = kCtBM + 64 / (int)sizeof(T);   // padded LDS row: k rows 0..3 of an MFMA read hit distinct banks
     __shared__ T lds[2][2][kCtBK][LD];             // [buffer][A, B][k][row]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     // loading slot of operand X: its k column kk and first row rr
-    const int kkA = P.a_mfast ? tid >> 4 : V * (tid % (16 / V));
-    const int rrA = P.a_mfast ? V * (tid & 15) : tid / (16 / V);
-    const int kkB = P.b_mfast ? tid >> 4 : V * (tid % (16 / V));
-    const int rrB = P.b_mfast ? V * (tid & 15) : tid / (16 / V);
+    const int kkA = P.a_mfast ? tid >> 4 : VA * (tid % (16 / VA));
+    const int rrA = P.a_mfast ? VA * (tid & 15) : tid / (16 / VA);
+    const int kkB = P.b_mfast ? tid >> 4 : VB * (tid % (16 / VB));
+    const int rrB = P.b_mfast ? VB * (tid & 15) : tid / (16 / VB);
     const int64_t nsteps = (P.K + kCtBK - 1) / kCtBK;
 
     for (int64_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
@@ -137,9 +145,9 @@ __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan 
         bool rvA[R], rvB[R];
 #pragma unroll
         for (int g = 0; g < R; ++g) {
-            const int64_t ra = m0 + rrA + g * RSTEP, rb = n0 + rrB + g * RSTEP;
-            rvA[g] = ra < P.M;
-            rvB[g] = rb < P.N;
+            const int64_t ra = m0 + rrA + g * RSTEPA, rb = n0 + rrB + g * RSTEPB;
+            rvA[g] = g < RA && ra < P.M;   // (g >= RA / RB: only when the operands' V differ)
+            rvB[g] = g < RB && rb < P.N;
             rowA[g] = rowB[g] = 0;
             if (rvA[g]) ct_decode(ra, P.nm, P.m_ext, P.m_sa, P.m_sa, P.m_sa, rowA[g], unused0, unused1);
             if (rvB[g]) ct_decode(rb, P.nn, P.n_ext, P.n_sb, P.n_sb, P.n_sb, rowB[g], unused0, unused1);
@@ -153,51 +161,56 @@ __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan 
             ct_advance(kiB, P.nk, P.k_ext, kkB);
         }
 
-        T ra[R][V], rb[R][V];
+        TA ra[R][VA];
+        TB rb[R][VB];
         auto load = [&](int64_t k0) {
             const int64_t koA = ct_koff(kiA, P.nk, P.k_sa), koB = ct_koff(kiB, P.nk, P.k_sb);
             const bool kvA = k0 + kkA < P.K, kvB = k0 + kkB < P.K;
 #pragma unroll
             for (int g = 0; g < R; ++g) {
                 if (rvA[g] && kvA) {
-                    const T* p = A + (boffA + rowA[g] + koA);
-                    if (V > 1 && P.a_vec) {
-                        const vec_t x = *reinterpret_cast<const vec_t*>(p);
+                    const TA* p = A + (boffA + rowA[g] + koA);
+                    if (VA > 1 && P.a_vec) {
+                        const veca_t x = *reinterpret_cast<const veca_t*>(p);
 #pragma unroll
-                        for (int v = 0; v < V; ++v) ra[g][v] = x[v];
+                        for (int v = 0; v < VA; ++v) ra[g][v] = x[v];
                     } else {
 #pragma unroll
-                        for (int v = 0; v < V; ++v) ra[g][v] = p[v * P.a_vstep];
+                        for (int v = 0; v < VA; ++v) ra[g][v] = p[v * P.a_vstep];
                     }
                 } else {
 #pragma unroll
-                    for (int v = 0; v < V; ++v) ra[g][v] = T(0);
+                    for (int v = 0; v < VA; ++v) ra[g][v] = TA(0);
                 }
                 if (rvB[g] && kvB) {
-                    const T* p = B + (boffB + rowB[g] + koB);
-                    if (V > 1 && P.b_vec) {
-                        const vec_t x = *reinterpret_cast<const vec_t*>(p);
+                    const TB* p = B + (boffB + rowB[g] + koB);
+                    if (VB > 1 && P.b_vec) {
+                        const vecb_t x = *reinterpret_cast<const vecb_t*>(p);
 #pragma unroll
-                        for (int v = 0; v < V; ++v) rb[g][v] = x[v];
+                        for (int v = 0; v < VB; ++v) rb[g][v] = x[v];
                     } else {
 #pragma unroll
-                        for (int v = 0; v < V; ++v) rb[g][v] = p[v * P.b_vstep];
+                        for (int v = 0; v < VB; ++v) rb[g][v] = p[v * P.b_vstep];
                     }
                 } else {
 #pragma unroll
-                    for (int v = 0; v < V; ++v) rb[g][v] = T(0);
+                    for (int v = 0; v < VB; ++v) rb[g][v] = TB(0);
                 }
             }
         };
-        auto stage = [&](int buf) {
+        auto stage = [&](int buf) {   // T(x): a float operand of a double contraction is widened here
 #pragma unroll
             for (int g = 0; g < R; ++g)
 #pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    if (P.a_mfast) lds[buf][0][kkA][rrA + g * RSTEP + v] = ra[g][v];
-                    else lds[buf][0][kkA + v][rrA + g * RSTEP] = ra[g][v];
-                    if (P.b_mfast) lds[buf][1][kkB][rrB + g * RSTEP + v] = rb[g][v];
-                    else lds[buf][1][kkB + v][rrB + g * RSTEP] = rb[g][v];
+                for (int v = 0; v < (VA > VB ? VA : VB); ++v) {
+                    if (g < RA && v < VA) {
+                        if (P.a_mfast) lds[buf][0][kkA][rrA + g * RSTEPA + v] = T(ra[g][v]);
+                        else lds[buf][0][kkA + v][rrA + g * RSTEPA] = T(ra[g][v]);
+                    }
+                    if (g < RB && v < VB) {
+                        if (P.b_mfast) lds[buf][1][kkB][rrB + g * RSTEPB + v] = T(rb[g][v]);
+                        else lds[buf][1][kkB + v][rrB + g * RSTEPB] = T(rb[g][v]);
+                    }
                 }
         };
 

@@ -16,7 +16,10 @@ namespace fe {
 // picks G > 1 when the fastest summation index is contiguous in an operand, so that a group reads
 // consecutive addresses (one thread per output walks that operand with a stride of a whole row
 // per lane: 64 cache lines per load instruction).  G = 1 is the plain restatement.
-template <typename T, int G>
+//
+// MIXED (T = double): an einsum whose operands are float64 or float32 each (d.dtype's FE_DTYPE_OPERAND_F32 flags: uniform over
+// the grid, a scalar branch per load); a float32 value is widened when it is loaded.
+template <typename T, int G, bool MIXED = false>
 __global__ __launch_bounds__(256) void einsum_generic_kernel(fe_einsum_desc d, fe_einsum_ptrs ops,
                                                              T* __restrict__ out,
                                                              int64_t n_out_entries, int64_t n_sum_points) {
@@ -52,7 +55,10 @@ __global__ __launch_bounds__(256) void einsum_generic_kernel(fe_einsum_desc d, f
         for (int p = 0; p < d.n_operands; ++p) {
             int64_t off = base[p];
             for (int k = 0; k < d.n_sum; ++k) off += sidx[k] * d.op_sum_stride[p][k];
-            prod *= static_cast<const T*>(ops.p[p])[off];
+            if (MIXED && (d.dtype & FE_DTYPE_OPERAND_F32(p)))
+                prod *= T(static_cast<const float*>(ops.p[p])[off]);
+            else
+                prod *= static_cast<const T*>(ops.p[p])[off];
         }
         acc += prod;
         if (d.n_sum > 0) {
@@ -89,6 +95,46 @@ __global__ __launch_bounds__(256) void einsum_pointwise_kernel(fe_einsum_ptrs op
     for (int64_t i = (aligned ? 2 * pairs : 0) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         T acc = static_cast<const T*>(ops.p[0])[i];
         for (int p = 1; p < n_operands; ++p) acc *= static_cast<const T*>(ops.p[p])[i];
+        out[i] = acc;
+    }
+}
+
+// The pointwise stream of a float64 einsum with float32 operands (bit p of f32_mask: operand p is float32): pairs of
+// 16 bytes (float64) or 8 bytes (float32) per operand, each operand aligned to its own pair size.
+__global__ __launch_bounds__(256) void einsum_pointwise_mixed_kernel(fe_einsum_ptrs ops, int n_operands,
+                                                                     unsigned f32_mask, double* __restrict__ out,
+                                                                     int64_t n) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const int64_t pairs = n / 2;
+    const bool aligned = [&] {
+        bool ok = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+        for (int p = 0; p < n_operands; ++p)
+            ok &= (reinterpret_cast<uintptr_t>(ops.p[p]) & ((f32_mask >> p & 1) ? 7 : 15)) == 0;
+        return ok;
+    }();
+    auto pair = [&](int p, int64_t q) -> d2 {
+        if (f32_mask >> p & 1) {
+            const f2 x = __builtin_nontemporal_load(static_cast<const f2*>(ops.p[p]) + q);
+            return d2{x[0], x[1]};
+        }
+        return __builtin_nontemporal_load(static_cast<const d2*>(ops.p[p]) + q);
+    };
+    auto one = [&](int p, int64_t i) -> double {
+        return (f32_mask >> p & 1) ? double(static_cast<const float*>(ops.p[p])[i])
+                                   : static_cast<const double*>(ops.p[p])[i];
+    };
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    if (aligned) {
+        for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < pairs; q += stride) {
+            d2 acc = pair(0, q);
+            for (int p = 1; p < n_operands; ++p) acc *= pair(p, q);
+            __builtin_nontemporal_store(acc, reinterpret_cast<d2*>(out) + q);
+        }
+    }
+    for (int64_t i = (aligned ? 2 * pairs : 0) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        double acc = one(0, i);
+        for (int p = 1; p < n_operands; ++p) acc *= one(p, i);
         out[i] = acc;
     }
 }

@@ -1366,6 +1366,26 @@ void contract_groups(const fe_einsum_desc* d, int32_t* out_group, int32_t* sum_g
     for (int k = 0; k < d->n_sum; ++k) sum_group[k] = d->sum_extent[k] == 1 ? FE_CONTRACT_DROPPED : FE_CONTRACT_K;
 }
 
+// The dtype field of an einsum descriptor: the compute type in the low byte, FE_DTYPE_OPERAND_F32 flags above it (float64
+// compute only, operands < n_operands).  FE_OK with the flags in *f32_mask (bit p: operand p is float32).
+int einsum_dtype(const char* who, const fe_einsum_desc* d, unsigned* f32_mask) {
+    const unsigned bits = (unsigned)d->dtype, code = bits & 0xffu, flags = bits & ~0xffu;
+    *f32_mask = 0;
+    if (flags & ~(unsigned)FE_DTYPE_OPERAND_F32_MASK) return fail(FE_EINVAL, "%s: unknown dtype bits 0x%x", who, bits);
+    if (flags) {
+        if (code != FE_DTYPE_F64)
+            return fail(FE_EINVAL, "%s: float32 operand flags need the float64 compute type (dtype 0x%x)", who, bits);
+        if ((flags >> 8) >> d->n_operands)
+            return fail(FE_EINVAL, "%s: float32 flag of a missing operand (dtype 0x%x, %d operands)", who, bits,
+                        d->n_operands);
+        *f32_mask = flags >> 8;
+        return FE_OK;
+    }
+    if (code != FE_DTYPE_F64 && code != FE_DTYPE_F32)
+        return fail(FE_EUNSUPPORTED, "%s: dtype code %d not compiled (float64 / float32 only)", who, d->dtype);
+    return FE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2115,8 +2135,8 @@ int fe_einsum_generic(const fe_einsum_desc* d, const void* const* operands, void
         d->n_out > FE_MAX_EINSUM_INDICES || d->n_sum < 0 || d->n_sum > FE_MAX_EINSUM_INDICES)
         return fail(FE_EINVAL, "einsum: %d operands / %d output / %d summation indices out of range",
                     d->n_operands, d->n_out, d->n_sum);
-    if (d->dtype != FE_DTYPE_F64 && d->dtype != FE_DTYPE_F32)
-        return fail(FE_EUNSUPPORTED, "einsum: dtype code %d not compiled (float64 / float32 only)", d->dtype);
+    unsigned f32_mask = 0;
+    if (int rc = einsum_dtype("einsum", d, &f32_mask)) return rc;
     int64_t n_out = 1, n_sum = 1;
     for (int k = 0; k < d->n_out; ++k) {
         if (d->out_extent[k] < 0) return fail(FE_EINVAL, "einsum: negative extent");
@@ -2134,10 +2154,13 @@ int fe_einsum_generic(const fe_einsum_desc* d, const void* const* operands, void
     for (int p = 0; p < d->n_operands; ++p) {
         if (!operands[p] && n_sum > 0) return fail(FE_EINVAL, "einsum: null operand %d", p);
         P.p[p] = operands[p];
+        if (f32_mask && reinterpret_cast<uintptr_t>(operands[p]) % ((f32_mask >> p & 1) ? 4 : 8))
+            return fail(FE_EINVAL, "einsum: operand %d not aligned to its element size", p);
     }
+    if (f32_mask && reinterpret_cast<uintptr_t>(out) % 8) return fail(FE_EINVAL, "einsum: output not 8-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 block(256);
-    const bool f64 = d->dtype == FE_DTYPE_F64;
+    const bool f64 = d->dtype == FE_DTYPE_F64 || f32_mask;
     if (d->n_sum > 0 && n_sum == 0) {   // a summation index of extent 0: every output entry is an empty sum
         FE_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n_out * (f64 ? 8 : 4), s));
         return FE_OK;
@@ -2155,7 +2178,10 @@ int fe_einsum_generic(const fe_einsum_desc* d, const void* const* operands, void
     if (pointwise) {
         const int64_t want = (n_out / 2 + 255) / 256 + 1, cap = 32 * (int64_t)device_cu_count();
         const dim3 grid((unsigned)(want < cap ? want : cap));
-        if (f64)
+        if (f32_mask)
+            hipLaunchKernelGGL(fe::einsum_pointwise_mixed_kernel, grid, block, 0, s, P, d->n_operands, f32_mask,
+                               static_cast<double*>(out), n_out);
+        else if (f64)
             hipLaunchKernelGGL(fe::einsum_pointwise_kernel<double>, grid, block, 0, s, P, d->n_operands,
                                static_cast<double*>(out), n_out);
         else
@@ -2176,7 +2202,14 @@ int fe_einsum_generic(const fe_einsum_desc* d, const void* const* operands, void
     const dim3 grid((unsigned)((n_out * group + 255) / 256));
 #define FE_EINSUM_CASE(T, G) \
     hipLaunchKernelGGL((fe::einsum_generic_kernel<T, G>), grid, block, 0, s, *d, P, static_cast<T*>(out), n_out, n_sum)
-    if (f64) {
+#define FE_EINSUM_MIXED_CASE(G)                                                                                 \
+    hipLaunchKernelGGL((fe::einsum_generic_kernel<double, G, true>), grid, block, 0, s, *d, P, static_cast<double*>(out), n_out, \
+                       n_sum)
+    if (f32_mask) {
+        if (group == 16) FE_EINSUM_MIXED_CASE(16);
+        else if (group == 4) FE_EINSUM_MIXED_CASE(4);
+        else FE_EINSUM_MIXED_CASE(1);
+    } else if (f64) {
         if (group == 16) FE_EINSUM_CASE(double, 16);
         else if (group == 4) FE_EINSUM_CASE(double, 4);
         else FE_EINSUM_CASE(double, 1);
@@ -2186,6 +2219,7 @@ int fe_einsum_generic(const fe_einsum_desc* d, const void* const* operands, void
         else FE_EINSUM_CASE(float, 1);
     }
 #undef FE_EINSUM_CASE
+#undef FE_EINSUM_MIXED_CASE
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
@@ -2196,8 +2230,8 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
         return fail(FE_EUNSUPPORTED, "contract: %d operands (the contraction kernel takes exactly 2)", d->n_operands);
     if (d->n_out < 0 || d->n_out > FE_MAX_EINSUM_INDICES || d->n_sum < 0 || d->n_sum > FE_MAX_EINSUM_INDICES)
         return fail(FE_EINVAL, "contract: %d output / %d summation indices out of range", d->n_out, d->n_sum);
-    if (d->dtype != FE_DTYPE_F64 && d->dtype != FE_DTYPE_F32)
-        return fail(FE_EUNSUPPORTED, "contract: dtype code %d not compiled (float64 / float32 only)", d->dtype);
+    unsigned f32_mask = 0;
+    if (int rc = einsum_dtype("contract", d, &f32_mask)) return rc;
     int64_t n_out = 1;
     for (int k = 0; k < d->n_out; ++k) {
         if (d->out_extent[k] < 0) return fail(FE_EINVAL, "contract: negative extent");
@@ -2208,7 +2242,7 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
     if (n_out == 0) return FE_OK;
     if (!out) return fail(FE_EINVAL, "contract: null output pointer");
     if (n_out >= ((int64_t)1 << 39)) return fail(FE_EINVAL, "contract: output too large");
-    const bool f64 = d->dtype == FE_DTYPE_F64;
+    const bool f64 = d->dtype == FE_DTYPE_F64 || f32_mask;
     const size_t esize = f64 ? 8 : 4;
     if (reinterpret_cast<uintptr_t>(out) % esize)
         return fail(FE_EINVAL, "contract: output pointer not aligned to its element size");
@@ -2248,8 +2282,10 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
     const void* opA = operands[0];
     const void* opB = operands[1];
     int ia = 0, ib = 1;
+    bool a_f32 = f32_mask & 1, b_f32 = f32_mask & 2;   // (mixed: which operand is stored as float32)
     if (tail == 'm') {
         std::swap(opA, opB);
+        std::swap(a_f32, b_f32);
         std::swap(ia, ib);
         std::swap(P.nm, P.nn);
         for (int j = 0; j < FE_MAX_EINSUM_INDICES; ++j) {
@@ -2275,7 +2311,8 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
         P.K *= P.k_ext[j];
     }
     if (P.K > 0 && (!opA || !opB)) return fail(FE_EINVAL, "contract: null operand");
-    if ((reinterpret_cast<uintptr_t>(opA) | reinterpret_cast<uintptr_t>(opB)) % esize)
+    const size_t esizeA = a_f32 ? 4 : esize, esizeB = b_f32 ? 4 : esize;
+    if (reinterpret_cast<uintptr_t>(opA) % esizeA || reinterpret_cast<uintptr_t>(opB) % esizeB)
         return fail(FE_EINVAL, "contract: operand pointer not aligned to its element size");
     P.M = P.N = 1;
     int64_t nbatch = 1;
@@ -2291,19 +2328,23 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
     const int64_t fastB = P.b_mfast ? P.n_ext[nlast] : (klast >= 0 ? P.k_ext[klast] : 1);
     P.a_vstep = P.a_mfast ? P.m_sa[mlast] : (klast >= 0 ? P.k_sa[klast] : 0);
     P.b_vstep = P.b_mfast ? P.n_sb[nlast] : (klast >= 0 ? P.k_sb[klast] : 0);
-    const int vmax = f64 ? 2 : 4;   // 16-byte groups
+    // 16-byte groups: one width for both operands of one dtype, each operand's own when they are mixed
+    const int vmax = f64 ? 2 : 4, vmaxA = (int)(16 / esizeA), vmaxB = (int)(16 / esizeB);
     const int V = (fastA % vmax == 0 && fastB % vmax == 0) ? vmax : 1;
+    int VA = f32_mask ? (fastA % vmaxA == 0 ? vmaxA : 1) : V;
+    int VB = f32_mask ? (fastB % vmaxB == 0 ? vmaxB : 1) : V;
+    if (a_f32 && b_f32) VA = VB = (VA > 1 && VB > 1) ? 4 : 1;   // (both float32 under float64: one width)
     // one vector load per group: unit stride inside it, a 16-byte aligned base, every other stride a multiple of V
-    auto vec_ok = [&](const void* p, bool mfast, int64_t vstep, const int64_t* sb_, const int64_t* srow, int nrow,
-                      const int64_t* sk) {
+    auto vec_ok = [&](const void* p, int V, size_t esize, bool mfast, int64_t vstep, const int64_t* sb_,
+                      const int64_t* srow, int nrow, const int64_t* sk) {
         if (V == 1 || vstep != 1 || reinterpret_cast<uintptr_t>(p) % (V * esize)) return false;
         for (int j = 0; j < P.nb; ++j) if (sb_[j] % V) return false;
         for (int j = 0; j < nrow; ++j) if (srow[j] % V && !(mfast && j == nrow - 1)) return false;
         for (int j = 0; j < nk; ++j) if (sk[j] % V && !(!mfast && j == nk - 1)) return false;
         return true;
     };
-    P.a_vec = vec_ok(opA, P.a_mfast, P.a_vstep, P.b_sa, P.m_sa, P.nm, P.k_sa);
-    P.b_vec = vec_ok(opB, P.b_mfast, P.b_vstep, P.b_sb, P.n_sb, P.nn, P.k_sb);
+    P.a_vec = vec_ok(opA, VA, esizeA, P.a_mfast, P.a_vstep, P.b_sa, P.m_sa, P.nm, P.k_sa);
+    P.b_vec = vec_ok(opB, VB, esizeB, P.b_mfast, P.b_vstep, P.b_sb, P.n_sb, P.nn, P.k_sb);
 
     P.tiles_m = (P.M + fe::kCtBM - 1) / fe::kCtBM;
     P.tiles_n = (P.N + fe::kCtBM - 1) / fe::kCtBM;
@@ -2319,7 +2360,29 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
         hipLaunchKernelGGL((fe::contract_mfma_kernel<T, VV>), grid, block, 0, s, P, static_cast<const T*>(opA),        \
                            static_cast<const T*>(opB), static_cast<T*>(out));                                          \
     } while (0)
-    if (f64) {
+#define FE_CONTRACT_MIXED_CASE(TA, TB, VVA, VVB, NAME)                                                          \
+    do {                                                                                                                \
+        static PerDeviceOnce once;                                                                                      \
+        if (int rc = configured(once, fe::contract_mfma_kernel<double, VVA, TA, TB, VVB>, NAME, 0, fe::kCtThreads,       \
+                                fe::kCtBlocksPerCu))                                                                    \
+            return rc;                                                                                                  \
+        hipLaunchKernelGGL((fe::contract_mfma_kernel<double, VVA, TA, TB, VVB>), grid, block, 0, s, P,                    \
+                           static_cast<const TA*>(opA), static_cast<const TB*>(opB), static_cast<double*>(out));        \
+    } while (0)
+    if (a_f32 && b_f32) {
+        if (VA > 1) FE_CONTRACT_MIXED_CASE(float, float, 4, 4, "contract f32 x f32 -> f64 (16-byte groups)");
+        else FE_CONTRACT_MIXED_CASE(float, float, 1, 1, "contract f32 x f32 -> f64");
+    } else if (a_f32) {
+        if (VA > 1 && VB > 1) FE_CONTRACT_MIXED_CASE(float, double, 4, 2, "contract f32 x f64 (16-byte groups)");
+        else if (VA > 1) FE_CONTRACT_MIXED_CASE(float, double, 4, 1, "contract f32 x f64 (A 16-byte groups)");
+        else if (VB > 1) FE_CONTRACT_MIXED_CASE(float, double, 1, 2, "contract f32 x f64 (B 16-byte groups)");
+        else FE_CONTRACT_MIXED_CASE(float, double, 1, 1, "contract f32 x f64");
+    } else if (b_f32) {
+        if (VA > 1 && VB > 1) FE_CONTRACT_MIXED_CASE(double, float, 2, 4, "contract f64 x f32 (16-byte groups)");
+        else if (VA > 1) FE_CONTRACT_MIXED_CASE(double, float, 2, 1, "contract f64 x f32 (A 16-byte groups)");
+        else if (VB > 1) FE_CONTRACT_MIXED_CASE(double, float, 1, 4, "contract f64 x f32 (B 16-byte groups)");
+        else FE_CONTRACT_MIXED_CASE(double, float, 1, 1, "contract f64 x f32");
+    } else if (f64) {
         if (V > 1) FE_CONTRACT_CASE(double, 2, "contract f64 (16-byte groups)");
         else FE_CONTRACT_CASE(double, 1, "contract f64");
     } else {
@@ -2327,6 +2390,7 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
         else FE_CONTRACT_CASE(float, 1, "contract f32");
     }
 #undef FE_CONTRACT_CASE
+#undef FE_CONTRACT_MIXED_CASE
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }

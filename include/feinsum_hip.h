@@ -505,6 +505,12 @@ int fe_time_launches(int32_t family, const fe_argpack* args, int32_t n_launches,
 #define FE_MAX_EINSUM_INDICES  8
 #define FE_DTYPE_F64 0
 #define FE_DTYPE_F32 1
+/* dtype's low byte is the compute and output type.  With FE_DTYPE_F64, FE_DTYPE_OPERAND_F32(p) marks operand p
+ * (p < FE_MAX_EINSUM_OPERANDS) as stored in float32: its elements are widened to float64 when loaded, and every
+ * product and sum is float64 (np.result_type of float32 and float64).  The flags with any other compute type, and any
+ * other bit, are FE_EINVAL.  A float32 operand needs 4-byte, a float64 operand and the output 8-byte alignment. */
+#define FE_DTYPE_OPERAND_F32(p) (1 << (8 + (p)))
+#define FE_DTYPE_OPERAND_F32_MASK (((1 << FE_MAX_EINSUM_OPERANDS) - 1) << 8)
 
 typedef struct fe_einsum_desc {
     int32_t n_operands, n_out, n_sum, dtype;
@@ -526,12 +532,13 @@ int fe_einsum_generic(const fe_einsum_desc* desc, const void* const* operands,
  * (FE_EUNSUPPORTED otherwise).  Evaluated on the matrix cores as a strided batched contraction
  * C[b,m,n] = sum_k A[b,m,k] B[b,n,k] (feinsum_amd/csrc/fe_contract.h): an output index carried by both
  * operands (or by neither) is a batch index, one carried by one operand an m / n index, every summed
- * index a k index.  Operands of any strides (8-byte alignment suffices); asynchronous on `stream`, no
- * allocation.  A summed extent of 0 writes zeros; an empty output launches nothing. */
+ * index a k index.  Operands of any strides (alignment to the element size suffices); asynchronous on
+ * `stream`, no allocation.  Mixed float32 / float64 operands (FE_DTYPE_OPERAND_F32) run the float64 kernel.  A summed extent of 0 writes zeros; an empty output launches nothing. */
 int fe_einsum_contract(const fe_einsum_desc* desc, const void* const* operands, void* out, void* stream);
 
 /* The index groups fe_einsum_contract forms for `desc` (host only, no device work): out_group[k] for output index k,
- * sum_group[k] for summed index k, each FE_CONTRACT_*; m / n are named before the launcher's orientation swap. */
+ * sum_group[k] for summed index k, each FE_CONTRACT_*; m / n are named before the launcher's orientation swap.
+ * The dtype field is ignored: the groups depend on the strides alone. */
 #define FE_CONTRACT_DROPPED -1 /* extent 1: adds nothing to any offset */
 #define FE_CONTRACT_BATCH    0 /* output index carried by both operands, or by neither (a broadcast) */
 #define FE_CONTRACT_M        1 /* output index carried by operand 0 only */
