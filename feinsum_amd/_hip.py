@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from pathlib import Path
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -34,7 +34,8 @@ EXPORTED_SYMBOLS = (
     "fe_grad_f64", "fe_div_f64",
     "fe_graddiv3d_f64", "fe_waveop3d_f64",
     "fe_facemass_f64",
-    "fe_flops_per_element", "fe_time_launches", "fe_einsum_generic", "fe_einsum_contract", "fe_einsum_contract_groups", "fe_kernel_resources",
+    "fe_flops_per_element", "fe_time_launches", "fe_einsum_generic", "fe_einsum_contract", "fe_einsum_contract_groups", "fe_einsum_reduce_plan", "fe_einsum_reduce",
+    "fe_kernel_resources",
     "fe_prepare_operator", "fe_grad3d_prepared_f64", "fe_div3d_prepared_f64", "fe_facemass_prepared_f64",
     "fe_graddiv3d_prepared_f64", "fe_waveop3d_prepared_f64", "fe_divcomp_f64", "fe_release_prepared",
     "fe_split_alloc", "fe_split_free", "fe_split_info", "fe_split_stats", "fe_split_reserve", "fe_split_trim", "fe_launch_f32", "fe_set_tail_rounds", "fe_set_tail_min_rounds",
@@ -66,6 +67,7 @@ FE_MAX_EINSUM_INDICES = 8
 FE_DTYPE_F64 = 0
 FE_DTYPE_F32 = 1
 FE_DTYPE_OPERAND_F32_MASK = ((1 << FE_MAX_EINSUM_OPERANDS) - 1) << 8
+FE_REDUCE_VALU, FE_REDUCE_MFMA = 0, 1   # fe_einsum_reduce_plan paths
 
 
 def FE_DTYPE_OPERAND_F32(p: int) -> int:   # noqa: N802  (the header's macro)
@@ -248,6 +250,12 @@ def load_library() -> C.CDLL:
                                        C.c_void_p]
     lib.fe_einsum_contract_groups.restype = C.c_int
     lib.fe_einsum_contract_groups.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.fe_einsum_reduce_plan.restype = C.c_int
+    lib.fe_einsum_reduce_plan.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_size_t)]
+    lib.fe_einsum_reduce.restype = C.c_int
+    lib.fe_einsum_reduce.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]
     _lib = lib
     return lib
 
@@ -515,6 +523,25 @@ def einsum_contract_groups(desc: EinsumDesc):
 def einsum_contract(desc: EinsumDesc, operands: Sequence[int], out: int, stream: int = 0) -> None:
     """Two-operand einsum on the matrix cores (``fe_einsum_contract``); same descriptor as :func:`einsum_generic`."""
     check(load_library().fe_einsum_contract(C.byref(desc), _ptr_array(operands), out, stream))
+
+
+REDUCE_PATH_NAMES = {FE_REDUCE_VALU: "valu", FE_REDUCE_MFMA: "mfma"}
+
+
+def einsum_reduce_plan(desc: EinsumDesc) -> Tuple[str, int, int]:
+    """``(path, slices, workspace bytes)`` of the split reduction of *desc* (``fe_einsum_reduce_plan``, host only):
+    path ``"valu"`` or ``"mfma"``."""
+    path, slices, nbytes = C.c_int32(), C.c_int64(), C.c_size_t()
+    check(load_library().fe_einsum_reduce_plan(C.byref(desc), C.byref(path), C.byref(slices), C.byref(nbytes)))
+    return REDUCE_PATH_NAMES[path.value], int(slices.value), int(nbytes.value)
+
+
+def einsum_reduce(desc: EinsumDesc, operands: Sequence[int], out: int, workspace: int, workspace_bytes: int,
+                  stream: int = 0) -> None:
+    """Split reduction (``fe_einsum_reduce``): same descriptor as :func:`einsum_generic`, plus a 256-byte aligned device
+    workspace of at least the bytes :func:`einsum_reduce_plan` reports."""
+    check(load_library().fe_einsum_reduce(C.byref(desc), _ptr_array(operands), out, workspace,
+                                          C.c_size_t(int(workspace_bytes)), stream))
 
 
 def set_tail_rounds(rounds: int) -> int:

@@ -45,6 +45,7 @@ struct ContractPlan {
     int64_t m_ext[kCtMaxIdx], m_sa[kCtMaxIdx], m_sc[kCtMaxIdx];
     int64_t n_ext[kCtMaxIdx], n_sb[kCtMaxIdx], n_sc[kCtMaxIdx];
     int64_t k_ext[kCtMaxIdx], k_sa[kCtMaxIdx], k_sb[kCtMaxIdx];
+    int64_t k_slices, k_slice_len, c_size;   // split-K only: k slices (of a multiple of kCtBK), entries of C
 };
 
 template <typename T>
@@ -111,7 +112,11 @@ __device__ __forceinline__ int64_t ct_koff(const int64_t (&idx)[kCtMaxIdx], int 
     return o;
 }
 
-template <typename T, int V, typename TA = T, typename TB = T, int VB = V>
+// SPLIT (split-K, fe_einsum_reduce): a work item is (batch, m tile, n tile, k slice); the item sums the k of its slice
+// only, [kb, ke), and writes its masked partial tile into slice ks of the workspace C[ks * c_size + ...] (the layout of
+// the output), which reduce_combine_kernel then sums in slice order.  The MFMA loop, the staging and the loads are
+// those of the plain kernel; SPLIT = false is the plain kernel.
+template <typename T, int V, typename TA = T, typename TB = T, int VB = V, bool SPLIT = false>
 __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan P, const TA* __restrict__ A,
                                                                    const TB* __restrict__ B, T* __restrict__ C) {
     typedef CtMfma<T> Mfma;
@@ -132,9 +137,15 @@ __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan 
     const int rrA = P.a_mfast ? VA * (tid & 15) : tid / (16 / VA);
     const int kkB = P.b_mfast ? tid >> 4 : VB * (tid % (16 / VB));
     const int rrB = P.b_mfast ? VB * (tid & 15) : tid / (16 / VB);
-    const int64_t nsteps = (P.K + kCtBK - 1) / kCtBK;
+    const int64_t n_items = SPLIT ? P.n_tiles * P.k_slices : P.n_tiles;
 
-    for (int64_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int64_t tile = SPLIT ? item % P.n_tiles : item;
+        const int64_t ks = SPLIT ? item / P.n_tiles : 0;
+        const int64_t kb = SPLIT ? ks * P.k_slice_len : 0;   // the item's k: [kb, ke)
+        const int64_t ke = SPLIT ? (kb + P.k_slice_len < P.K ? kb + P.k_slice_len : P.K) : P.K;
+        const int64_t nsteps = (ke - kb + kCtBK - 1) / kCtBK;
+        T* __restrict__ Cs = SPLIT ? C + ks * P.c_size : C;
         const int64_t tn = tile % P.tiles_n, rest = tile / P.tiles_n;
         const int64_t tm = rest % P.tiles_m, bi = rest / P.tiles_m;
         const int64_t m0 = tm * kCtBM, n0 = tn * kCtBM;
@@ -157,15 +168,15 @@ __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan 
 #pragma unroll
         for (int t = 0; t < kCtMaxIdx; ++t) kiA[t] = kiB[t] = 0;
         if (nsteps > 0) {   // (an extent of 0 would divide by zero)
-            ct_advance(kiA, P.nk, P.k_ext, kkA);
-            ct_advance(kiB, P.nk, P.k_ext, kkB);
+            ct_advance(kiA, P.nk, P.k_ext, kb + kkA);
+            ct_advance(kiB, P.nk, P.k_ext, kb + kkB);
         }
 
         TA ra[R][VA];
         TB rb[R][VB];
         auto load = [&](int64_t k0) {
             const int64_t koA = ct_koff(kiA, P.nk, P.k_sa), koB = ct_koff(kiB, P.nk, P.k_sb);
-            const bool kvA = k0 + kkA < P.K, kvB = k0 + kkB < P.K;
+            const bool kvA = k0 + kkA < ke, kvB = k0 + kkB < ke;
 #pragma unroll
             for (int g = 0; g < R; ++g) {
                 if (rvA[g] && kvA) {
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan 
             for (int g = 0; g < 2; ++g) acc[f][g] = acc_t{0, 0, 0, 0};
 
         if (nsteps > 0) {
-            load(0);
+            load(kb);
             stage(0);
             __syncthreads();
         }
@@ -231,7 +242,7 @@ __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan 
             if (more) {
                 ct_advance(kiA, P.nk, P.k_ext, kCtBK);
                 ct_advance(kiB, P.nk, P.k_ext, kCtBK);
-                load((s + 1) * kCtBK);
+                load(kb + (s + 1) * kCtBK);
             }
 #pragma unroll
             for (int ks = 0; ks < kCtBK / 4; ++ks) {
@@ -270,7 +281,7 @@ __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan 
                 ct_decode(row, P.nm, P.m_ext, P.m_sc, P.m_sc, P.m_sc, rowC, unused0, unused1);
 #pragma unroll
                 for (int g = 0; g < 2; ++g)
-                    if (cv[g]) C[boffC + rowC + colC[g]] = acc[f][g][r];
+                    if (cv[g]) Cs[boffC + rowC + colC[g]] = acc[f][g][r];
             }
     }
 }

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <string>
@@ -21,6 +22,7 @@
 #include "fe_contract.h"
 #include "fe_div.h"
 #include "fe_einsum.h"
+#include "fe_reduce.h"
 #include "fe_facemass.h"
 #include "fe_fused.h"
 #include "fe_generic.h"
@@ -1386,6 +1388,148 @@ int einsum_dtype(const char* who, const fe_einsum_desc* d, unsigned* f32_mask) {
     return FE_OK;
 }
 
+// ---- split reductions (fe_einsum_reduce_plan / fe_einsum_reduce, fe_reduce.h) ----
+// The plan depends on the descriptor alone -- never on the device, its CU count or a knob -- so that a result is
+// bitwise reproducible on every device of the architecture.  The limits mirror feinsum_amd/reduction.py
+// (REDUCE_MAX_OUT, REDUCE_MAX_TILES) and contraction.py (AUTO_MIN_*): the MFMA path is taken where "auto" would run
+// the two-operand einsum on the contraction kernel and its grid has few tiles.
+constexpr int64_t kReduceMaxOut = 4096;        // output entries per row
+constexpr int64_t kReduceMaxTiles = 256;       // MFMA path: batch x m tiles x n tiles below this
+constexpr int64_t kReduceValuBlocks = 2048;    // VALU: slices x output chunks aimed at (8 blocks of 256 on 256 CUs)
+constexpr int64_t kReduceMinPerWalker = 16;    // VALU: summation points per walker and slice, at least
+constexpr int64_t kReduceMfmaItems = 512;      // MFMA: tiles x k slices aimed at (the persistent grid of 256 CUs)
+constexpr int64_t kReduceMinKSteps = 8;        // MFMA: k steps of kCtBK per slice, at least
+constexpr size_t kReduceWsAlign = 256;
+
+struct SplitK {   // split-K launch of contract_launch: slices of slice_len k each, partials into ws
+    int64_t slices, slice_len;
+    void* ws;
+};
+
+struct ReduceSetup {
+    int path;               // FE_REDUCE_VALU / FE_REDUCE_MFMA
+    int64_t n_out, slices;
+    size_t ws_bytes, esize;
+    unsigned f32_mask;
+    int64_t k_slice_len;    // MFMA
+    int64_t out_chunks;     // VALU
+    fe::ReducePlan V;       // VALU
+};
+
+int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+int reduce_setup(const char* who, const fe_einsum_desc* d, ReduceSetup* r) {
+    if (!d) return fail(FE_EINVAL, "%s: null descriptor", who);
+    if (d->n_operands < 1 || d->n_operands > FE_MAX_EINSUM_OPERANDS || d->n_out < 0 ||
+        d->n_out > FE_MAX_EINSUM_INDICES || d->n_sum < 0 || d->n_sum > FE_MAX_EINSUM_INDICES)
+        return fail(FE_EINVAL, "%s: %d operands / %d output / %d summation indices out of range", who, d->n_operands,
+                    d->n_out, d->n_sum);
+    memset(r, 0, sizeof(*r));
+    if (int rc = einsum_dtype(who, d, &r->f32_mask)) return rc;
+    const bool f64 = (d->dtype & 0xff) == FE_DTYPE_F64;
+    r->esize = f64 ? 8 : 4;
+    int64_t n_out = 1, n_sum = 1;
+    for (int k = 0; k < d->n_out; ++k) {
+        if (d->out_extent[k] < 0) return fail(FE_EINVAL, "%s: negative extent", who);
+        n_out *= d->out_extent[k];
+    }
+    for (int k = 0; k < d->n_sum; ++k) {
+        if (d->sum_extent[k] < 0) return fail(FE_EINVAL, "%s: negative extent", who);
+        n_sum *= d->sum_extent[k];
+    }
+    r->n_out = n_out;
+    r->path = FE_REDUCE_VALU;
+    if (n_out == 0) return FE_OK;   // nothing to launch, no workspace
+    if (n_out > kReduceMaxOut)
+        return fail(FE_EUNSUPPORTED, "%s: %lld output entries; a split reduction writes at most %lld", who,
+                    (long long)n_out, (long long)kReduceMaxOut);
+
+    if (d->n_operands == 2) {   // the contraction's groups (contract_groups) and the "auto" sizes
+        int32_t og[FE_MAX_EINSUM_INDICES], sg[FE_MAX_EINSUM_INDICES];
+        contract_groups(d, og, sg);
+        int64_t M = 1, N = 1, B = 1, K = 1;
+        for (int k = 0; k < d->n_out; ++k) {
+            if (og[k] == FE_CONTRACT_M) M *= d->out_extent[k];
+            else if (og[k] == FE_CONTRACT_N) N *= d->out_extent[k];
+            else if (og[k] == FE_CONTRACT_BATCH) B *= d->out_extent[k];
+        }
+        for (int k = 0; k < d->n_sum; ++k) K *= d->sum_extent[k];
+        const int64_t tiles = B * ceil_div(M, fe::kCtBM) * ceil_div(N, fe::kCtBM);
+        if (M >= 16 && N >= 8 && K >= 8 && M * N >= 512 && tiles < kReduceMaxTiles) {
+            int64_t S = std::min(ceil_div(kReduceMfmaItems, tiles), ceil_div(K, kReduceMinKSteps * fe::kCtBK));
+            S = std::max<int64_t>(S, 1);
+            r->k_slice_len = ceil_div(ceil_div(K, S), fe::kCtBK) * fe::kCtBK;
+            r->path = FE_REDUCE_MFMA;
+            r->slices = ceil_div(K, r->k_slice_len);
+            r->ws_bytes = (size_t)ceil_div((int64_t)(r->slices * n_out * r->esize), kReduceWsAlign) * kReduceWsAlign;
+            return FE_OK;
+        }
+    }
+
+    // VALU: summation indices of extent 1 dropped, neighbours contiguous in every operand merged (outermost first)
+    fe::ReducePlan& P = r->V;
+    P.n_ops = d->n_operands;
+    P.f32_mask = r->f32_mask;
+    for (int k = 0; k < d->n_out; ++k) {
+        if (d->out_extent[k] == 1) continue;
+        P.out_ext[P.n_out] = d->out_extent[k];
+        for (int p = 0; p < d->n_operands; ++p) P.out_st[p][P.n_out] = d->op_out_stride[p][k];
+        ++P.n_out;
+    }
+    if (n_sum > 0)
+        for (int k = 0; k < d->n_sum; ++k) {
+            if (d->sum_extent[k] == 1) continue;
+            bool merge = P.n_sum > 0;
+            for (int p = 0; p < d->n_operands && merge; ++p)
+                merge = P.sum_st[p][P.n_sum - 1] == d->op_sum_stride[p][k] * d->sum_extent[k];
+            if (merge) {
+                P.sum_ext[P.n_sum - 1] *= d->sum_extent[k];
+                for (int p = 0; p < d->n_operands; ++p) P.sum_st[p][P.n_sum - 1] = d->op_sum_stride[p][k];
+                continue;
+            }
+            P.sum_ext[P.n_sum] = d->sum_extent[k];
+            for (int p = 0; p < d->n_operands; ++p) P.sum_st[p][P.n_sum] = d->op_sum_stride[p][k];
+            ++P.n_sum;
+        }
+    P.n_out_entries = n_out;
+    P.n_sum_points = n_sum;
+    // lanes along the output when the largest operand's unit stride is an output index and no summation index
+    int big = 0;
+    double big_n = -1;
+    for (int p = 0; p < d->n_operands; ++p) {
+        double nel = 1;
+        for (int k = 0; k < P.n_out; ++k) if (P.out_st[p][k]) nel *= (double)P.out_ext[k];
+        for (int k = 0; k < P.n_sum; ++k) if (P.sum_st[p][k]) nel *= (double)P.sum_ext[k];
+        if (nel > big_n) big = p, big_n = nel;
+    }
+    bool out_unit = false, sum_unit = false;
+    for (int k = 0; k < P.n_out; ++k) out_unit |= std::abs(P.out_st[big][k]) == 1;
+    for (int k = 0; k < P.n_sum; ++k) sum_unit |= std::abs(P.sum_st[big][k]) == 1;
+    P.C = (out_unit && !sum_unit) ? (int32_t)std::min<int64_t>(n_out, fe::kRdThreads) : 1;
+    P.R = fe::kRdThreads / P.C;
+    P.R2 = 1;
+    while (P.R2 < P.R) P.R2 *= 2;
+    r->out_chunks = ceil_div(n_out, P.C);
+    int64_t S = std::min(ceil_div(kReduceValuBlocks, r->out_chunks), ceil_div(n_sum, kReduceMinPerWalker * P.R));
+    S = std::max<int64_t>(S, 1);
+    P.slice_len = ceil_div(ceil_div(n_sum, S), 4) * 4;   // (a multiple of every vector width)
+    P.slices = n_sum > 0 ? ceil_div(n_sum, P.slice_len) : 1;
+    // one step of R points as digits of the summation space, and the offsets they and each wrap add
+    int64_t rem = P.R;
+    for (int t = 0; t < P.n_sum; ++t) {
+        const int k = P.n_sum - 1 - t;
+        P.step_dig[t] = k > 0 ? rem % P.sum_ext[k] : rem;
+        rem = k > 0 ? rem / P.sum_ext[k] : 0;
+        for (int p = 0; p < d->n_operands; ++p) {
+            P.step_off[p] += P.step_dig[t] * P.sum_st[p][k];
+            if (k > 0) P.wrap_off[p][k] = P.sum_st[p][k - 1] - P.sum_ext[k] * P.sum_st[p][k];
+        }
+    }
+    r->slices = P.slices;
+    r->ws_bytes = (size_t)ceil_div((int64_t)(r->slices * n_out * r->esize), kReduceWsAlign) * kReduceWsAlign;
+    return FE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2224,7 +2368,10 @@ int fe_einsum_generic(const fe_einsum_desc* d, const void* const* operands, void
     return FE_OK;
 }
 
-int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, void* out, void* stream) {
+// fe_einsum_contract, and (split: not null) the split-K launch of fe_einsum_reduce, which writes split->slices partial
+// outputs into split->ws instead of `out`.
+static int contract_launch(const fe_einsum_desc* d, const void* const* operands, void* out, void* stream,
+                           const SplitK* split) {
     if (!d || !operands) return fail(FE_EINVAL, "contract: null descriptor");
     if (d->n_operands != 2)
         return fail(FE_EUNSUPPORTED, "contract: %d operands (the contraction kernel takes exactly 2)", d->n_operands);
@@ -2351,6 +2498,45 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
     P.n_tiles = nbatch * P.tiles_m * P.tiles_n;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t cap = (int64_t)fe::kCtBlocksPerCu * device_cu_count();
+    if (split) {
+        P.k_slices = split->slices;
+        P.k_slice_len = split->slice_len;
+        P.c_size = n_out;
+        const int64_t items = P.n_tiles * P.k_slices;
+        const dim3 sgrid((unsigned)(items < cap ? items : cap)), sblock(fe::kCtThreads);
+#define FE_CONTRACT_SPLIT_CASE(T, TA, TB, VVA, VVB, NAME)                                                               \
+    do {                                                                                                                \
+        static PerDeviceOnce once;                                                                                      \
+        if (int rc = configured(once, fe::contract_mfma_kernel<T, VVA, TA, TB, VVB, true>, NAME, 0, fe::kCtThreads,     \
+                                fe::kCtBlocksPerCu))                                                                    \
+            return rc;                                                                                                  \
+        hipLaunchKernelGGL((fe::contract_mfma_kernel<T, VVA, TA, TB, VVB, true>), sgrid, sblock, 0, s, P,               \
+                           static_cast<const TA*>(opA), static_cast<const TB*>(opB), static_cast<T*>(split->ws));       \
+    } while (0)
+        if (a_f32 && b_f32) {
+            if (VA > 1) FE_CONTRACT_SPLIT_CASE(double, float, float, 4, 4, "contract split-K f32 x f32 -> f64 (16-byte groups)");
+            else FE_CONTRACT_SPLIT_CASE(double, float, float, 1, 1, "contract split-K f32 x f32 -> f64");
+        } else if (a_f32) {
+            if (VA > 1 && VB > 1) FE_CONTRACT_SPLIT_CASE(double, float, double, 4, 2, "contract split-K f32 x f64 (16-byte groups)");
+            else if (VA > 1) FE_CONTRACT_SPLIT_CASE(double, float, double, 4, 1, "contract split-K f32 x f64 (A 16-byte groups)");
+            else if (VB > 1) FE_CONTRACT_SPLIT_CASE(double, float, double, 1, 2, "contract split-K f32 x f64 (B 16-byte groups)");
+            else FE_CONTRACT_SPLIT_CASE(double, float, double, 1, 1, "contract split-K f32 x f64");
+        } else if (b_f32) {
+            if (VA > 1 && VB > 1) FE_CONTRACT_SPLIT_CASE(double, double, float, 2, 4, "contract split-K f64 x f32 (16-byte groups)");
+            else if (VA > 1) FE_CONTRACT_SPLIT_CASE(double, double, float, 2, 1, "contract split-K f64 x f32 (A 16-byte groups)");
+            else if (VB > 1) FE_CONTRACT_SPLIT_CASE(double, double, float, 1, 4, "contract split-K f64 x f32 (B 16-byte groups)");
+            else FE_CONTRACT_SPLIT_CASE(double, double, float, 1, 1, "contract split-K f64 x f32");
+        } else if (f64) {
+            if (V > 1) FE_CONTRACT_SPLIT_CASE(double, double, double, 2, 2, "contract split-K f64 (16-byte groups)");
+            else FE_CONTRACT_SPLIT_CASE(double, double, double, 1, 1, "contract split-K f64");
+        } else {
+            if (V > 1) FE_CONTRACT_SPLIT_CASE(float, float, float, 4, 4, "contract split-K f32 (16-byte groups)");
+            else FE_CONTRACT_SPLIT_CASE(float, float, float, 1, 1, "contract split-K f32");
+        }
+#undef FE_CONTRACT_SPLIT_CASE
+        FE_HIP_CHECK(hipGetLastError());
+        return FE_OK;
+    }
     const dim3 grid((unsigned)(P.n_tiles < cap ? P.n_tiles : cap)), block(fe::kCtThreads);
 #define FE_CONTRACT_CASE(T, VV, NAME)                                                                                   \
     do {                                                                                                                \
@@ -2391,6 +2577,91 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
     }
 #undef FE_CONTRACT_CASE
 #undef FE_CONTRACT_MIXED_CASE
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, void* out, void* stream) {
+    return contract_launch(d, operands, out, stream, nullptr);
+}
+
+int fe_einsum_reduce_plan(const fe_einsum_desc* d, int32_t* path, int64_t* slices, size_t* workspace_bytes) {
+    if (!path || !slices || !workspace_bytes) return fail(FE_EINVAL, "reduce plan: null pointer");
+    ReduceSetup r;
+    if (int rc = reduce_setup("reduce plan", d, &r)) return rc;
+    *path = r.path;
+    *slices = r.slices;
+    *workspace_bytes = r.ws_bytes;
+    return FE_OK;
+}
+
+int fe_einsum_reduce(const fe_einsum_desc* d, const void* const* operands, void* out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (!operands) return fail(FE_EINVAL, "reduce: null operand array");
+    ReduceSetup r;
+    if (int rc = reduce_setup("reduce", d, &r)) return rc;
+    if (r.n_out == 0) return FE_OK;
+    if (!out) return fail(FE_EINVAL, "reduce: null output pointer");
+    if (reinterpret_cast<uintptr_t>(out) % r.esize) return fail(FE_EINVAL, "reduce: output not aligned to its element size");
+    if (!workspace) return fail(FE_EINVAL, "reduce: null workspace (fe_einsum_reduce_plan: %zu bytes)", r.ws_bytes);
+    if (workspace_bytes < r.ws_bytes)
+        return fail(FE_EINVAL, "reduce: workspace of %zu bytes, the plan needs %zu", workspace_bytes, r.ws_bytes);
+    if (reinterpret_cast<uintptr_t>(workspace) % kReduceWsAlign)
+        return fail(FE_EINVAL, "reduce: workspace not %zu-byte aligned", kReduceWsAlign);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool f64 = r.esize == 8;
+    if (r.path == FE_REDUCE_MFMA) {
+        const SplitK split = {r.slices, r.k_slice_len, workspace};
+        if (int rc = contract_launch(d, operands, out, stream, &split)) return rc;
+    } else {
+        fe::ReducePlan& P = r.V;
+        fe_einsum_ptrs ops;
+        for (int p = 0; p < FE_MAX_EINSUM_OPERANDS; ++p) ops.p[p] = nullptr;
+        bool vec = P.n_sum == 1 && P.C == 1;
+        for (int p = 0; p < d->n_operands; ++p) {
+            const size_t es = (r.f32_mask >> p & 1) ? 4 : r.esize;
+            if (!operands[p] && P.n_sum_points > 0) return fail(FE_EINVAL, "reduce: null operand %d", p);
+            if (reinterpret_cast<uintptr_t>(operands[p]) % es)
+                return fail(FE_EINVAL, "reduce: operand %d not aligned to its element size", p);
+            ops.p[p] = operands[p];
+            // one vector load per V points: unit stride, every output entry's base a multiple of V, the pointer aligned
+            const int64_t Vw = f64 ? 2 : 4;
+            if (vec && (P.sum_st[p][0] != 1 || reinterpret_cast<uintptr_t>(operands[p]) % (Vw * es))) vec = false;
+            for (int k = 0; k < P.n_out && vec; ++k) vec = P.out_st[p][k] % Vw == 0;
+        }
+        P.vec = vec;
+        const dim3 grid((unsigned)P.slices, (unsigned)r.out_chunks), block(fe::kRdThreads);
+#define FE_REDUCE_CASE(T, MIXED, VEC, NAME)                                                                             \
+    do {                                                                                                                \
+        static PerDeviceOnce once;                                                                                      \
+        if (int rc = configured(once, fe::reduce_partial_kernel<T, MIXED, VEC>, NAME, 0, fe::kRdThreads, 1)) return rc; \
+        hipLaunchKernelGGL((fe::reduce_partial_kernel<T, MIXED, VEC>), grid, block, 0, s, P, ops,                       \
+                           static_cast<T*>(workspace));                                                                 \
+    } while (0)
+        if (r.f32_mask) {
+            if (vec) FE_REDUCE_CASE(double, true, true, "reduce partials mixed (16-byte loads)");
+            else FE_REDUCE_CASE(double, true, false, "reduce partials mixed");
+        } else if (f64) {
+            if (vec) FE_REDUCE_CASE(double, false, true, "reduce partials f64 (16-byte loads)");
+            else FE_REDUCE_CASE(double, false, false, "reduce partials f64");
+        } else {
+            if (vec) FE_REDUCE_CASE(float, false, true, "reduce partials f32 (16-byte loads)");
+            else FE_REDUCE_CASE(float, false, false, "reduce partials f32");
+        }
+#undef FE_REDUCE_CASE
+        FE_HIP_CHECK(hipGetLastError());
+    }
+    const dim3 cgrid((unsigned)ceil_div(r.n_out, fe::kRdThreads / 64)), cblock(fe::kRdThreads);
+#define FE_COMBINE_CASE(T, NAME)                                                                                        \
+    do {                                                                                                                \
+        static PerDeviceOnce once;                                                                                      \
+        if (int rc = configured(once, fe::reduce_combine_kernel<T>, NAME, 0, fe::kRdThreads, 1)) return rc;            \
+        hipLaunchKernelGGL((fe::reduce_combine_kernel<T>), cgrid, cblock, 0, s, static_cast<const T*>(workspace),       \
+                           static_cast<T*>(out), r.n_out, r.slices);                                                    \
+    } while (0)
+    if (f64) FE_COMBINE_CASE(double, "reduce combine f64");
+    else FE_COMBINE_CASE(float, "reduce combine f32");
+#undef FE_COMBINE_CASE
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }

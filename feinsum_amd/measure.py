@@ -23,7 +23,9 @@ Argument conventions kept from the reference:
                selects the default kernel variant, while a ``str`` / ``dict``
                (``"mfma"``, ``"generic"``, ``{"variant": "generic"}``) selects
                a variant explicitly (``"contraction"``: the einsum as strided batched
-               contractions on the matrix cores, ``feinsum_amd.contraction``); in a dict, ``"prepared": True`` lets a
+               contractions on the matrix cores, ``feinsum_amd.contraction``; ``"reduction"``: a long summation
+               space summed into a small output as a split reduction over the whole chip,
+               ``feinsum_amd.reduction``); in a dict, ``"prepared": True`` lets a
                bound launch (``timeit``) use a prepared copy of its operator
                matrices; ``"placement"`` (or ``$FEINSUM_PLACEMENT``): ``timeit``
                allocates one array per operand as the reference does; with the
@@ -31,7 +33,8 @@ Argument conventions kept from the reference:
                (``feinsum_amd.placement.zeros``; ``evaluate`` allocates the outputs it
                is not handed the same way), ``"separate"`` takes every array
                from torch; ``timeit_details(...).placement`` reports which was used.
-``schedule``   followed by the ``"contraction"`` transform (default: the optimal one); the
+``schedule``   followed by the ``"contraction"`` transform (default: the optimal one) and by the
+               ``"reduction"`` transform where the einsum does not stream in one launch; the
                other kernels implement the optimal schedule and ignore it.
 
 Inputs are drawn from ``numpy.random.default_rng(0)`` in **sorted argument-name
@@ -51,6 +54,7 @@ import numpy as np
 
 from feinsum_amd import _hip
 from feinsum_amd.contraction import ContractionLaunch, auto_picks_contraction
+from feinsum_amd.reduction import ReductionLaunch, auto_picks_reduction, check_reduction
 from feinsum_amd.contraction_schedule import ContractionSchedule, count_ops
 from feinsum_amd.diagnostics import (HipLibraryError, InvalidParameterError,
                                      NoDevicePeaksInfoError, TransformValidationError)
@@ -443,19 +447,27 @@ class _GenericLaunch:
 
 def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int]) -> str:
     """
-    Which kernels run *einsum* under *transform* (size parameters *sizes*): ``"contraction"`` (the transform of that
-    name, or ``"auto"`` on a two-operand einsum outside the DG families where ``contraction.auto_picks_contraction``
-    says the contraction kernel wins), ``"family"`` (a DG family kernel) or ``"generic"``.
+    Which kernels run *einsum* under *transform* (size parameters *sizes*): ``"reduction"`` (the transform of that
+    name -- ``NotImplementedError`` above ``reduction.REDUCE_MAX_OUT`` output entries -- or ``"auto"`` outside the DG
+    families where ``reduction.auto_picks_reduction`` finds a long summation space summed into a small output),
+    ``"contraction"`` (the transform of that name, or ``"auto"`` on a two-operand einsum outside the DG families where
+    ``contraction.auto_picks_contraction`` says the contraction kernel wins), ``"family"`` (a DG family kernel) or
+    ``"generic"``.  The reduction rule is checked before the contraction rule.
     """
     variant = _variant_from_transform(transform)
     if variant == "contraction":
         return "contraction"
+    if variant == "reduction":
+        check_reduction(einsum, sizes)
+        return "reduction"
     if match_family(einsum) is not None:
         return "family"
     if variant not in (None, "auto", "generic", 0, 1):
         raise NotImplementedError(
             f"einsum '{einsum.get_subscripts()}' is outside the DG kernel families;"
-            " only the generic and contraction kernels are available for it")
+            " only the generic, contraction and reduction kernels are available for it")
+    if variant in (None, "auto", 0) and auto_picks_reduction(einsum, sizes):
+        return "reduction"
     if variant in (None, "auto", 0) and auto_picks_contraction(einsum, sizes):
         return "contraction"
     return "generic"
@@ -489,6 +501,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     kind = launch_kind(einsum, transform, sizes)
     if kind == "contraction":
         bound = ContractionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
+    elif kind == "reduction":
+        bound = ReductionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
     elif kind == "family":
         bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform))
         if _prepared_from_transform(transform, prepare):

@@ -21,5 +21,5 @@ class ToStr(Protocol):
 
 
 #: what ``transform=`` accepts here: a reference-style callable (ignored), None, a variant name
-#: ("auto" | "mfma" | "generic" | "contraction") or ``{"variant": name}``
+#: ("auto" | "mfma" | "generic" | "contraction" | "reduction") or ``{"variant": name}``
 VariantSelectorT = Union[TransformT, None, str, Mapping[str, Any]]

@@ -546,6 +546,34 @@ int fe_einsum_contract(const fe_einsum_desc* desc, const void* const* operands, 
 #define FE_CONTRACT_K        3 /* summed index */
 int fe_einsum_contract_groups(const fe_einsum_desc* desc, int32_t* out_group, int32_t* sum_group);
 
+/* ---- split reductions: einsums that sum a long summation space into a small output ----
+ * ('ei,ei->', 'ej,ej->j', 'ei,ej->ij', 'e,ei,ei->'.)  The summation space is cut into S slices; one launch writes a
+ * partial output per slice into a caller-provided workspace, a second sums the partials of every output entry in slice
+ * order (feinsum_amd/csrc/fe_reduce.h).  Two paths:
+ *   FE_REDUCE_MFMA  two operands that the contraction kernel takes (M >= 16, N >= 8, K >= 8, M N >= 512 as
+ *                   fe_einsum_contract groups them) with fewer than 256 (batch x m x n) tiles of 64 x 64: the
+ *                   contraction kernel, split along k (fe_contract.h);
+ *   FE_REDUCE_VALU  everything else: flattened summation points on the VALU, lanes along the summation or along the
+ *                   output, whichever is contiguous in the largest operand.
+ * S, the slices and every order of summation depend on the descriptor alone: a result is bitwise the same across runs,
+ * streams, graph replays and devices of one architecture (not bitwise that of fe_einsum_generic: the order differs).
+ * At most 4096 output entries (FE_EUNSUPPORTED above). */
+#define FE_REDUCE_VALU 0
+#define FE_REDUCE_MFMA 1
+
+/* Host only, no device work: the path (FE_REDUCE_*), S (0 for an empty output) and the workspace size in bytes
+ * fe_einsum_reduce needs for `desc` (0 for an empty output).  FE_EINVAL / FE_EUNSUPPORTED as fe_einsum_generic. */
+int fe_einsum_reduce_plan(const fe_einsum_desc* desc, int32_t* path, int64_t* slices, size_t* workspace_bytes);
+
+/* Same descriptor, operands and output contract as fe_einsum_generic, plus a device workspace of at least the bytes
+ * fe_einsum_reduce_plan reports, 256-byte aligned (FE_EINVAL before any device work if it is null, short or misaligned);
+ * it is overwritten, and nothing is allocated.  Asynchronous on `stream`.  Mixed float32 / float64 operands
+ * (FE_DTYPE_OPERAND_F32) are widened as they are loaded, as in fe_einsum_generic / fe_einsum_contract: the same path,
+ * slices and order as the float64 einsum of the pre-converted operands, hence the same bits.  A summed extent of 0
+ * writes zeros; an empty output launches nothing. */
+int fe_einsum_reduce(const fe_einsum_desc* desc, const void* const* operands, void* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
