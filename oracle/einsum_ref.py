@@ -22,7 +22,7 @@ Error-bounded reference (:func:`bounded_reference`, :func:`bound_violations`)
 from __future__ import annotations
 
 import math
-from typing import List, Mapping, Sequence, Tuple
+from typing import List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -199,6 +199,147 @@ def f32_step_possible(dtypes: Sequence, n_ops: int) -> bool:
     return unit_roundoff(dtypes, n_ops) == U32
 
 
+def _xp(a):
+    """numpy for numpy arrays, torch for torch tensors (the checkers below take either, on any device)."""
+    if isinstance(a, np.ndarray):
+        return np
+    import torch
+
+    return torch
+
+
+def differing_entries(got, ref) -> int:
+    """Entries of *got* that are not bitwise *ref* (``-0.0`` and ``0.0`` are equal, as in :func:`bitwise_equal`;
+    a NaN anywhere differs); every entry when the shapes or dtypes differ.  numpy arrays or torch tensors."""
+    n = int(np.prod(tuple(ref.shape), dtype=np.int64))
+    if tuple(got.shape) != tuple(ref.shape) or got.dtype != ref.dtype:
+        return max(n, 1)
+    return int((got != ref).sum())
+
+
+def nonfinite_violations(got, ref, dep, planted: float) -> int:
+    """Entries that break the rule of a planted non-finite value: for a NaN exactly the dependency set *dep* is NaN,
+    for an Inf exactly *dep* is non-finite (NaN or either infinity: the kernel may bracket the sum differently from
+    numpy), and every other entry is bitwise the exact reference *ref*.  Every entry when the shapes differ.  numpy
+    arrays or torch tensors (the GPU sweep calls it on device tensors)."""
+    n = int(np.prod(tuple(ref.shape), dtype=np.int64))
+    if tuple(got.shape) != tuple(ref.shape) or tuple(dep.shape) != tuple(ref.shape):
+        return max(n, 1)
+    xp = _xp(got)
+    hit = xp.isnan(got) if math.isnan(planted) else ~xp.isfinite(got)
+    return int((hit != dep).sum()) + int((got[~dep] != ref[~dep]).sum())
+
+
+# --------------------------------------------------------------------------
+# DG einsums: arrays shared by name, range cases, dependency sets, a device reference
+# --------------------------------------------------------------------------
+
+#: (exponent of the largest total, exponent of the subnormal quantum) per dtype: the range cases
+RANGE = {np.dtype("float64"): (900, -1074), np.dtype("float32"): (100, -149)}
+
+
+def rows_fit(rows: Sequence[Tuple[Sequence[str], int]], bits: Mapping[str, int], significand: int) -> bool:
+    """Whether :func:`bits_fit` holds for every row: ``(names of its operands, terms per output entry)``."""
+    return all(bits_fit([bits[nm] for nm in names], n_terms, significand) for names, n_terms in rows)
+
+
+def shared_exact_bits(rows: Sequence[Tuple[Sequence[str], int]], f32_names: Sequence[str], significand: int,
+                      rng: np.random.Generator) -> dict:
+    """Mantissa bits per array NAME for einsums whose rows (and stages) share arrays: the budget of :func:`bits_fit`
+    holds for every row that reads the array.  Each name starts at its share of the tightest row it is in; the bits
+    left are then handed out one at a time in random order while every row still fits.  float32 names take at most 24
+    bits, every name at least 1."""
+    names = list(dict.fromkeys(nm for r, _ in rows for nm in r))
+    w = {nm: float(rng.random()) + 0.25 for nm in names}
+    cap = {nm: 24 if nm in f32_names else significand for nm in names}
+    bits = {}
+    for nm in names:
+        share = []
+        for r, n_terms in rows:
+            if nm in r:
+                budget = max(significand - max(int(n_terms), 1).bit_length(), len(r))
+                share.append(budget * w[nm] / sum(w[x] for x in r))
+        bits[nm] = max(1, min(cap[nm], int(min(share))))
+    while not rows_fit(rows, bits, significand):   # (tiny budgets: give back until it fits)
+        nm = max(bits, key=lambda x: bits[x])
+        if bits[nm] == 1:
+            raise AssertionError("no bit budget fits these rows")
+        bits[nm] -= 1
+    grown = True
+    while grown:
+        grown = False
+        for k in rng.permutation(len(names)):
+            nm = names[int(k)]
+            if bits[nm] < cap[nm]:
+                bits[nm] += 1
+                if rows_fit(rows, bits, significand):
+                    grown = True
+                else:
+                    bits[nm] -= 1
+    return bits
+
+
+def range_scales(positions: Sequence[Sequence[str]], bits: Mapping[str, int], significand: int, dtype, kind: str,
+                 rng: np.random.Generator) -> dict:
+    """Power-of-two scale per array name.  *positions* lists the names each operand position can hold (every row
+    takes one name per position, so every row has the same total scale).  *kind*:
+
+    ``"normal"``     scales in [-8, 8];
+    ``"overflow"``   all scales >= 0, totals near ``2**900`` (float64) / ``2**100`` (float32);
+    ``"subnormal"``  all scales <= 0, their sum the subnormal quantum ``-1074`` / ``-149``.
+
+    Under one sign every partial product lies between 1 and the final result, so the exactness argument of the bit
+    budget holds unchanged; subnormal arithmetic is fixed point, so those results are exact too (pass a *significand*
+    a few bits short of the dtype's to keep every sum below the smallest normal)."""
+    top, quantum = RANGE[np.dtype(dtype)]
+    n = len(positions)
+    if kind == "normal":
+        per = [int(s) for s in rng.integers(-8, 9, size=n)]
+    else:
+        total = top - significand if kind == "overflow" else quantum
+        w = rng.random(n) + 0.1
+        per = [int(total * x / w.sum()) for x in w]
+        per[int(rng.integers(n))] += total - sum(per)
+        assert sum(per) == total and all((s >= 0) if kind == "overflow" else (s <= 0) for s in per)
+    return {nm: per[p] for p, names in enumerate(positions) for nm in names}
+
+
+def dependency_set(subscripts: str, shapes: Sequence[Tuple[int, ...]], operand: int, index: Tuple[int, ...]) -> np.ndarray:
+    """Output entries that structurally depend on entry *index* of operand *operand*: the nonzero entries of the
+    einsum of a one-hot array there with all-ones arrays for the other operands (a sum of non-negative terms is zero
+    only when it has no term)."""
+    ops = [np.ones(s) for s in shapes]
+    ops[operand] = np.zeros(shapes[operand])
+    ops[operand][tuple(index)] = 1.0
+    return np.asarray(np.einsum(subscripts, *ops, optimize=True)) != 0
+
+
+def int_reference(subscripts: str, mants: Sequence[np.ndarray], scale: int, out_dtype, significand: int) -> np.ndarray:
+    """:func:`exact_reference` with one total *scale*, in any contraction order (integer sums are exact in any order:
+    every partial sum is bounded by the absolute einsum, at most ``2**significand``)."""
+    absum = np.einsum(subscripts, *[np.abs(m) for m in mants], optimize=True)
+    assert (np.asarray(absum) <= (1 << significand)).all(), "exact-data budget exceeded"
+    ints = np.asarray(np.einsum(subscripts, *mants, optimize=True), dtype=np.int64)
+    return np.ldexp(ints.astype(np.float64), int(scale)).astype(np.dtype(out_dtype))
+
+
+def torch_exact_reference(torch, subscripts: str, operands: Sequence, e_axes: Sequence[Optional[int]], out_e_axis: int,
+                          out_dtype, chunk: int = 1 << 16):
+    """Whole-array reference on the device for exact data: torch's float64 ``einsum`` of the operands (every partial
+    sum of exact data fits the significand, so any order is exact), in chunks of *chunk* elements along E (*e_axes*:
+    each operand's E axis, ``None`` for operands without one).  float32 data is widened and the result cast back,
+    which is exact.  Not trusted on its own: :func:`check_torch_reference` compares it with :func:`int_reference`."""
+    E = next(int(t.shape[a]) for t, a in zip(operands, e_axes) if a is not None)
+    wide = [t.to(torch.float64) for t in operands]
+    parts = []
+    for e0 in range(0, max(E, 1), chunk):
+        sl = [t if a is None else t.narrow(a, e0, min(chunk, E - e0)) for t, a in zip(wide, e_axes)]
+        parts.append(torch.einsum(subscripts, *sl))
+    return torch.cat(parts, dim=out_e_axis).to(getattr(torch, np.dtype(out_dtype).name))
+
+
 __all__ = ["SIGNIFICAND", "U64", "U32", "summed_points", "compute_significand", "exact_bits", "bits_fit",
            "exact_operands", "exact_reference", "needs_more_than_f32", "bitwise_equal", "gamma", "bound_terms",
-           "bounded_reference", "bound_ratio", "bound_violations", "unit_roundoff", "f32_step_possible"]
+           "bounded_reference", "bound_ratio", "bound_violations", "unit_roundoff", "f32_step_possible", "RANGE", "rows_fit",
+           "shared_exact_bits", "range_scales", "dependency_set", "int_reference", "torch_exact_reference",
+           "nonfinite_violations", "differing_entries"]
