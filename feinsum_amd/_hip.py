@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "fe_graddiv3d_prepared_f64", "fe_waveop3d_prepared_f64", "fe_divcomp_f64", "fe_release_prepared",
     "fe_split_alloc", "fe_split_free", "fe_split_info", "fe_split_stats", "fe_split_reserve", "fe_split_trim", "fe_launch_f32", "fe_set_tail_rounds", "fe_set_tail_min_rounds",
     "fe_set_cu_limit", "fe_set_phase_priority_p5", "fe_set_div_interleave", "fe_set_div_quarter_tail", "fe_set_grad_quarter_tail", "fe_set_grad_staggered_start", "fe_last_launch_info", "fe_stream_retired", "fe_capture_id", "fe_graph_retired", "fe_tail_stats", "fe_tail_check", "fe_tail_plant", "fe_set_temporal_loads_mib", "fe_set_write_through_mib",
+    "fe_geomadj_f64", "fe_facemass_adj_f64",
 )
 FAMILY_F32 = 0x100    # FE_FAMILY_F32
 
@@ -256,6 +257,11 @@ def load_library() -> C.CDLL:
     lib.fe_einsum_reduce.restype = C.c_int
     lib.fe_einsum_reduce.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]
+    lib.fe_geomadj_f64.restype = C.c_int
+    lib.fe_geomadj_f64.argtypes = [C.c_void_p] * 4 + [C.c_int64] + [C.c_int32] * 4 + [C.c_int64] * 3 + [C.c_void_p]
+    lib.fe_facemass_adj_f64.restype = C.c_int
+    lib.fe_facemass_adj_f64.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p]
     _lib = lib
     return lib
 
@@ -376,6 +382,24 @@ def facemass(J: int, R: int, v: Sequence[int], out: Sequence[int], E: int, Np: i
         raise InvalidParameterError("face-mass: need as many outputs as fields")
     check(load_library().fe_facemass_f64(J, R, _ptr_array(v), _ptr_array(out), E, Np, nf, Nfp,
                                          len(v), layout_flags, variant_code(variant), stream))
+
+
+def geomadj(D: int, a: int, b: int, out: int, E: int, X: int, R: int, Np: int, strides: Sequence[int],
+            op_flags: int = 0, stream: int = 0) -> None:
+    """``out[x sx + r sr + e se] = sum_i (sum_j K[r, i, j] a[e, j]) b[x, e, i]`` (fe_geomadj_f64; *strides* = (sx, sr, se))."""
+    sx, sr, se = (int(v) for v in strides)
+    check(load_library().fe_geomadj_f64(D, a, b, out, E, X, R, Np, op_flags, sx, sr, se, stream))
+
+
+def facemass_adj(J: Optional[int], R: int, g: Sequence[int], v: Optional[Sequence[int]], dv: Optional[Sequence[int]],
+                 dJ: Optional[int], E: int, Np: int, nf: int, Nfp: int, layout_flags: int = 0, stream: int = 0) -> None:
+    """The face-mass adjoint (fe_facemass_adj_f64): *dv* (None: skipped) and *dJ* summed over the fields (*v* None:
+    skipped)."""
+    if dv is not None and len(dv) != len(g) or v is not None and len(v) != len(g):
+        raise InvalidParameterError("face-mass adjoint: need as many v / dv arrays as output gradients")
+    check(load_library().fe_facemass_adj_f64(J, R, _ptr_array(g), _ptr_array(v) if v is not None else None,
+                                             _ptr_array(dv) if dv is not None else None, dJ, E, Np, nf, Nfp,
+                                             len(g), layout_flags, stream))
 
 
 PREPARED_OPERATOR_BYTES = 96 * 1024   # FE_PREPARED_OPERATOR_BYTES

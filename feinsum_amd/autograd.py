@@ -1,0 +1,244 @@
+"""
+Differentiate einsum evaluations through ``torch.autograd``.
+
+Every einsum is linear in each operand, so the vector-Jacobian product with respect to an input array A is a sum of
+einsums: for every occurrence of A (every row, every operand position), the row's other operands times the gradient
+of that row's output, summed to A's subscripts.  :func:`adjoint_einsums` builds those terms with the existing
+builders; :func:`evaluate_differentiable` evaluates the forward with :func:`~feinsum_amd.measure.evaluate` and the
+terms in its backward pass -- on the DG family kernels where a term is a family einsum (grad's u-adjoint is div with
+the transposed operator, ...), on the adjoint kernels where :func:`~feinsum_amd.family.match_adjoint_family`
+recognises it (the geometric-factor and face-mass adjoints), and with ``"auto"`` otherwise.
+"""
+
+from __future__ import annotations
+
+from collections import Counter
+from dataclasses import dataclass
+from types import MappingProxyType
+from typing import Any, List, Mapping, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+
+from feinsum_amd.contraction_schedule import ContractionSchedule
+from feinsum_amd.einsum import BatchedEinsum, SizeParam
+from feinsum_amd.family import ADJ_FACEMASS_J, match_adjoint_family, match_family
+from feinsum_amd.make_einsum import array
+
+#: prefix of the output-gradient operands of the adjoint einsums; no user array may start with it
+GRAD_PREFIX = "_fe_grad"
+
+#: launches of the backward passes of this process, by route: "family", "geomadj", "facemass_v", "facemass_j", "auto"
+launch_counts: Counter = Counter()
+
+
+def output_grad_name(out_name: str) -> str:
+    """Name of the operand that carries the gradient of output *out_name* (``_fe_out`` -> ``_fe_grad_fe_out``)."""
+    return GRAD_PREFIX + out_name
+
+
+class AdjointTerm(NamedTuple):
+    """One adjoint einsum of :func:`adjoint_terms`: each row is one occurrence of ``wrt``; ``wrt_subscripts`` are
+    ``wrt``'s subscripts at that operand position.  ``einsum.out_idx_set`` is ``wrt_subscripts`` without the indices
+    that no other operand and not the output carry: the term's value is broadcast along those."""
+
+    einsum: BatchedEinsum
+    wrt_subscripts: Tuple[str, ...]
+    forward_rows: Tuple[int, ...]
+
+
+def adjoint_terms(einsum: BatchedEinsum, wrt: str) -> List[AdjointTerm]:
+    """The adjoint einsums of *einsum* with respect to input array *wrt*, one :class:`AdjointTerm` per operand position
+    at which *wrt* occurs (its rows: the forward rows with *wrt* there).  The outputs of all rows of all terms, each
+    broadcast to *wrt*'s shape (:func:`expand_to_operand`), sum to the vector-Jacobian product."""
+    if wrt not in einsum.all_args:
+        raise ValueError(f"'{wrt}' is not an input array of '{einsum.get_subscripts()}'")
+    clash = sorted(name for name in einsum.all_args if name.startswith(GRAD_PREFIX))
+    if clash:
+        raise ValueError(f"array names starting with '{GRAD_PREFIX}' are reserved for output gradients: {clash}")
+    positions: dict = {}
+    for k, row in enumerate(einsum.args):
+        for p, arg in enumerate(row):
+            if arg.name == wrt:
+                positions.setdefault(p, []).append(k)
+    terms = []
+    for p, rows in sorted(positions.items()):
+        w_idx = einsum.in_idx_sets[p]
+        if len(set(w_idx)) != len(w_idx):
+            raise NotImplementedError(
+                f"operand '{wrt}' repeats an index in its subscripts '{''.join(w_idx)}' (a diagonal): its gradient "
+                "is not an einsum of the other operands")
+        others = [q for q in range(einsum.n) if q != p]
+        in_sets = tuple(einsum.in_idx_sets[q] for q in others) + (einsum.out_idx_set,)
+        present = {i for s in in_sets for i in s}
+        out_idx = tuple(i for i in w_idx if i in present)
+        args = []
+        for k in rows:
+            dt = np.result_type(*[a.dtype for a in einsum.args[k]])
+            args.append(tuple(einsum.args[k][q] for q in others)
+                        + (array(output_grad_name(einsum.output_names[k]), einsum.shape, dt),))
+        terms.append(AdjointTerm(BatchedEinsum(out_idx, in_sets, tuple(args)), w_idx, tuple(rows)))
+    return terms
+
+
+def adjoint_einsums(einsum: BatchedEinsum, wrt: str) -> List[BatchedEinsum]:
+    """The einsums whose outputs sum to the vector-Jacobian product of *einsum* for input array *wrt*: one output row per
+    occurrence of *wrt*; the gradient of output ``name`` is the operand ``output_grad_name(name)`` (0-d for a scalar
+    output); indices of *wrt* that no other operand carries are left out of a term's output (broadcast, see
+    :func:`adjoint_terms`).  ``NotImplementedError`` for an operand with a repeated index (``ii->i``)."""
+    return [t.einsum for t in adjoint_terms(einsum, wrt)]
+
+
+def expand_to_operand(value: Any, term_out: Sequence[str], wrt_subscripts: Sequence[str], shape: Sequence[int]) -> Any:
+    """Broadcast a term's output (numpy or torch; axes *term_out*) to the operand's axes *wrt_subscripts* / *shape*."""
+    view = tuple(int(shape[k]) if i in term_out else 1 for k, i in enumerate(wrt_subscripts))
+    value = value.reshape(view)
+    if hasattr(value, "expand"):      # torch
+        return value.expand(*[int(d) for d in shape])
+    return np.broadcast_to(value, tuple(int(d) for d in shape))
+
+
+# --------------------------------------------------------------------------
+# torch.autograd
+# --------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class _Spec:
+    einsum: BatchedEinsum
+    names: Tuple[str, ...]
+    queue: Any
+    transform: Any
+    schedule: Optional[ContractionSchedule]
+
+
+def _concrete(shape, sizes) -> Tuple[int, ...]:
+    return tuple(sizes[d.name] if isinstance(d, SizeParam) else int(d) for d in shape)
+
+
+def _run_term(term: BatchedEinsum, args: Mapping[str, Any], q: Any) -> Any:
+    """Sum of the rows of an adjoint einsum, on q's stream, in ordinary torch allocations."""
+    import torch
+
+    from feinsum_amd import measure
+    from feinsum_amd.adjoint import AdjointLaunch
+
+    sizes = measure._long_length(term, args)
+    shape = _concrete(term.shape, sizes)
+    dtypes = [getattr(torch, measure.result_dtype(term, k).name) for k in range(term.b)]
+    plan = match_adjoint_family(term)
+    if plan is not None and plan.kind == ADJ_FACEMASS_J and len({row[plan.roles["R"]].name for row in term.args}) == 1:
+        # every field into one dJ, summed inside the kernel in row order
+        out = torch.empty(shape, dtype=dtypes[0], device=q.torch_device)
+        with torch.cuda.device(q.torch_device):
+            AdjointLaunch(plan, term, args, [out], sum_rows=True).launch(q.stream_ptr)
+        launch_counts[plan.kind] += 1
+        return out
+    outs = {name: torch.empty(shape, dtype=dt, device=q.torch_device) for name, dt in zip(term.output_names, dtypes)}
+    if plan is not None:
+        measure.evaluate(term, q, args, out_dict=outs, transform="adjoint")
+        launch_counts[plan.kind] += 1
+    else:
+        measure.evaluate(term, q, args, out_dict=outs)
+        launch_counts["family" if match_family(term) is not None else "auto"] += 1
+    total = None
+    for name in term.output_names:
+        total = outs[name] if total is None else total.add_(outs[name])
+    return total
+
+
+def _backward(ctx, spec: _Spec, grads) -> List[Any]:
+    einsum, q = spec.einsum, spec.queue
+    saved = ctx.saved_tensors
+    args = dict(zip(spec.names, saved))
+    have = set()
+    for name, g in zip(einsum.output_names, grads):
+        if g is not None:                        # an output without a gradient contributes nothing
+            args[output_grad_name(name)] = g.contiguous()
+            have.add(name)
+    result = []
+    for pos, name in enumerate(spec.names):
+        if not ctx.needs_input_grad[pos + 1]:
+            result.append(None)
+            continue
+        target = saved[pos]
+        total = None
+        for term in adjoint_terms(einsum, name):
+            rows = tuple(row for row, k in zip(term.einsum.args, term.forward_rows) if einsum.output_names[k] in have)
+            if not rows:
+                continue
+            sub = term.einsum.copy(args=rows)
+            value = expand_to_operand(_run_term(sub, args, q), sub.out_idx_set, term.wrt_subscripts, target.shape)
+            total = value.contiguous() if total is None else total.add_(value)
+        if total is not None and total.dtype != target.dtype:
+            total = total.to(target.dtype)       # float32 operand of a float64 einsum: computed in float64, rounded once
+        result.append(total)
+    return result
+
+
+def _function():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _EinsumFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, spec: _Spec, *tensors):
+            from feinsum_amd import measure
+
+            ctx.set_materialize_grads(False)
+            q = spec.queue
+            cur = torch.cuda.current_stream(q.torch_device)
+            own = q.stream != cur
+            if own:
+                q.stream.wait_stream(cur)
+            outs = measure.evaluate(spec.einsum, q, dict(zip(spec.names, tensors)), transform=spec.transform,
+                                    schedule=spec.schedule)
+            if own:
+                cur.wait_stream(q.stream)
+            ctx.spec = spec
+            ctx.save_for_backward(*tensors)
+            return tuple(outs[name] for name in spec.einsum.output_names)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, *grads):
+            spec = ctx.spec
+            q = spec.queue
+            cur = torch.cuda.current_stream(q.torch_device)
+            if q.stream == cur:
+                return (None, *_backward(ctx, spec, grads))
+            # a queue of its own stream: everything below (launches, allocations, sums) runs on it, after the work that
+            # produced the output gradients, and torch's current stream waits for it before it uses the gradients
+            q.stream.wait_stream(cur)
+            with torch.cuda.stream(q.stream):
+                result = _backward(ctx, spec, grads)
+            cur.wait_stream(q.stream)
+            for t in result:
+                if t is not None:
+                    t.record_stream(cur)
+            return (None, *result)
+
+    return _EinsumFunction
+
+
+_FN = None
+
+
+def evaluate_differentiable(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *, transform: Any = None,
+                            schedule: Optional[ContractionSchedule] = None) -> Mapping[str, Any]:
+    """:func:`~feinsum_amd.measure.evaluate` as a ``torch.autograd.Function``: returns ``{name: tensor}``, bitwise the
+    outputs of ``evaluate`` with the same *transform*, carrying a ``grad_fn`` when an input requires grad.  The backward
+    pass computes the gradients ``ctx.needs_input_grad`` asks for, on the stream it runs on (with a ``DeviceQueue`` of
+    its own stream: ordered against torch's current stream by events both ways), into ordinary torch allocations.
+    Double backward is not supported (``once_differentiable``)."""
+    global _FN
+    from feinsum_amd.diagnostics import InvalidParameterError
+    from feinsum_amd.measure import _as_queue
+
+    if _FN is None:
+        _FN = _function()
+    q = _as_queue(cq)
+    names = tuple(sorted(einsum.all_args))
+    missing = [n for n in names if n not in arg_dict]
+    if missing:
+        raise InvalidParameterError(f"missing input arrays: {missing}")
+    outs = _FN.apply(_Spec(einsum, names, q, transform, schedule), *[arg_dict[n] for n in names])
+    return MappingProxyType(dict(zip(einsum.output_names, outs)))

@@ -19,6 +19,7 @@
 
 #include "../../include/feinsum_hip.h"
 #include "fe_common.h"
+#include "fe_adjoint.h"
 #include "fe_contract.h"
 #include "fe_div.h"
 #include "fe_einsum.h"
@@ -3134,6 +3135,148 @@ int fe_time_launches(int32_t family, const fe_argpack* args, int32_t n_launches,
     hipEventDestroy(t1);
     if (rc != FE_OK) return rc;
     if (e != hipSuccess) return fail(FE_EHIP, "fe_time_launches: %s", hipGetErrorString(e));
+    return FE_OK;
+}
+
+}  // extern "C"
+
+// ---- adjoint kernels (fe_adjoint.h) ----
+namespace {
+
+template <int NP>
+int launch_geomadj(const fe::GeomAdjArgs& g, hipStream_t s) {
+    using G = fe::GeomAdjGeom<NP>;
+    const int lds = g.R * G::LDS_DOUBLES_PER_R * (int)sizeof(double);
+    static PerDeviceOnce once;   // LDS attribute sized for R = 3; the residency is checked at the largest R
+    if (int rc = configured(once, fe::geomadj_kernel<NP>, "geomadj", 3 * G::LDS_DOUBLES_PER_R * (int)sizeof(double),
+                            fe::kAdjThreads, 2))
+        return rc;
+    const int64_t n_tiles = (g.E + 15) / 16;
+    const unsigned grid = persistent_grid(n_tiles, fe::kAdjWaves);
+    hipLaunchKernelGGL(fe::geomadj_kernel<NP>, dim3(grid), dim3(fe::kAdjThreads), lds, s, g);
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+template <int NP, int NFP, int NF>
+int launch_facemass_adj(const fe::FmAdjArgs& g, hipStream_t s) {
+    using G = fe::FmAdjGeom<NP, NFP, NF>;
+    const int lds = G::LDS_DOUBLES * (int)sizeof(double);
+    static PerDeviceOnce once;
+    if (int rc = configured(once, fe::facemass_adj_kernel<NP, NFP, NF>, "facemass adjoint", lds, fe::kAdjThreads, 2))
+        return rc;
+    const int64_t n_tiles = (g.E + 15) / 16;
+    const unsigned grid = persistent_grid(n_tiles, fe::kAdjWaves);
+    hipLaunchKernelGGL((fe::facemass_adj_kernel<NP, NFP, NF>), dim3(grid), dim3(fe::kAdjThreads), lds, s, g);
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int fe_geomadj_f64(const double* D, const double* a, const double* b, double* out, int64_t E, int32_t X, int32_t R,
+                   int32_t Np, int32_t op_flags, int64_t sx, int64_t sr, int64_t se, void* stream) {
+    if (E < 0) return fail(FE_EINVAL, "geomadj: E must be >= 0 (got %lld)", (long long)E);
+    if (X < 1 || X > 3 || R < 1 || R > 3) return fail(FE_EUNSUPPORTED, "geomadj: X = %d, R = %d not compiled (1..3)", X, R);
+    if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "geomadj: bad operator flags %d", op_flags);
+    if (E > 0 && (!D || !a || !b || !out)) return fail(FE_EINVAL, "geomadj: null device pointer");
+    if (!aligned8(D) || !aligned8(a) || !aligned8(b) || !aligned8(out))
+        return fail(FE_EINVAL, "geomadj: device pointers must be 8-byte aligned (float64 arrays)");
+    if (E * (int64_t)(Np > 0 ? Np : 1) * X >= (int64_t)1 << 39) return fail(FE_EINVAL, "geomadj: E too large");
+    fe::GeomAdjArgs g = {D, a, b, out, E, sx, sr, se, X, R, (op_flags & FE_OP_TRANSPOSED) ? 1 : 0};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc;
+    switch (Np) {
+        case 3: rc = E ? launch_geomadj<3>(g, s) : FE_OK; break;
+        case 4: rc = E ? launch_geomadj<4>(g, s) : FE_OK; break;
+        case 6: rc = E ? launch_geomadj<6>(g, s) : FE_OK; break;
+        case 10: rc = E ? launch_geomadj<10>(g, s) : FE_OK; break;
+        case 15: rc = E ? launch_geomadj<15>(g, s) : FE_OK; break;
+        case 20: rc = E ? launch_geomadj<20>(g, s) : FE_OK; break;
+        case 21: rc = E ? launch_geomadj<21>(g, s) : FE_OK; break;
+        case 35: rc = E ? launch_geomadj<35>(g, s) : FE_OK; break;
+        default: return fail(FE_EUNSUPPORTED, "geomadj: Np = %d not compiled (3, 4, 6, 10, 15, 20, 21, 35)", Np);
+    }
+    return rc;
+}
+
+int fe_facemass_adj_f64(const double* J, const double* R, const double* const* g, const double* const* v,
+                        double* const* dv, double* dJ, int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
+                        int32_t layout_flags, void* stream) {
+    if (E < 0) return fail(FE_EINVAL, "facemass adjoint: E must be >= 0 (got %lld)", (long long)E);
+    if (b < 1) return fail(FE_EINVAL, "facemass adjoint: b=%d, need at least one field", b);
+    if (!g) return fail(FE_EINVAL, "facemass adjoint: null pointer table");
+    if (layout_flags & ~(FE_FM_J_FE | FE_FM_R_IFJ | FE_FM_R_T))
+        return fail(FE_EINVAL, "facemass adjoint: bad layout flags %d", layout_flags);
+    const bool with_dv = dv != nullptr, with_dJ = v != nullptr && dJ != nullptr;
+    if (E > 0 && !with_dv && !with_dJ) return fail(FE_EINVAL, "facemass adjoint: neither dv nor (v, dJ) given");
+    int kind = -1;   // compiled shapes
+    if (nf == 4 && Np == 4 && Nfp == 3) kind = 0;
+    else if (nf == 4 && Np == 10 && Nfp == 6) kind = 1;
+    else if (nf == 4 && Np == 20 && Nfp == 10) kind = 2;
+    else if (nf == 4 && Np == 35 && Nfp == 15) kind = 3;
+    else if (nf == 3 && Np == 3 && Nfp == 2) kind = 4;
+    else if (nf == 3 && Np == 6 && Nfp == 3) kind = 5;
+    else if (nf == 3 && Np == 10 && Nfp == 4) kind = 6;
+    else if (nf == 3 && Np == 15 && Nfp == 5) kind = 7;
+    else if (nf == 3 && Np == 21 && Nfp == 6) kind = 8;
+    if (kind < 0)
+        return fail(FE_EUNSUPPORTED, "facemass adjoint: (nf, Np, Nfp) = (%d, %d, %d) not compiled", nf, Np, Nfp);
+    if (E > 0) {
+        if (!R || (with_dv && !J)) return fail(FE_EINVAL, "facemass adjoint: null device pointer");
+        for (int k = 0; k < b; ++k)
+            if (!g[k] || (with_dv && !dv[k]) || (with_dJ && !v[k]))
+                return fail(FE_EINVAL, "facemass adjoint: null device pointer (field %d)", k);
+    }
+    if (!aligned8(J) || !aligned8(R) || !aligned8(dJ)) return fail(FE_EINVAL, "facemass adjoint: device pointers must be 8-byte aligned");
+    for (int k = 0; k < b; ++k)
+        if (!aligned8(g[k]) || (with_dv && !aligned8(dv[k])) || (with_dJ && !aligned8(v[k])))
+            return fail(FE_EINVAL, "facemass adjoint: device pointers must be 8-byte aligned");
+    if (E * (int64_t)Np * b >= (int64_t)1 << 39) return fail(FE_EINVAL, "facemass adjoint: E too large");
+    if (E == 0) return FE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // R's strides of (f, i, j): 'fij', 'ifj', 'fji', 'jfi' (as the face-mass kernels read it)
+    const int rl = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) | ((layout_flags & FE_FM_R_T) ? 2 : 0);
+    const int sF = rl == 0 ? Np * Nfp : rl == 1 ? Nfp : rl == 2 ? Nfp * Np : Np;
+    const int sI = rl == 0 ? Nfp : rl == 1 ? nf * Nfp : 1;
+    const int sJ = rl == 0 || rl == 1 ? 1 : rl == 2 ? Np : nf * Np;
+    const bool jfe = (layout_flags & FE_FM_J_FE) != 0;
+    for (int k0 = 0; k0 < b; k0 += FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch; dJ accumulates over launches
+        const int nb = std::min(b - k0, FE_MAX_FIELDS);
+        fe::FmAdjArgs a = {};
+        a.J = J;
+        a.R = R;
+        for (int k = 0; k < nb; ++k) {
+            a.g.v[k] = g[k0 + k];
+            a.g.out[k] = with_dv ? dv[k0 + k] : nullptr;
+            a.v.v[k] = with_dJ ? v[k0 + k] : nullptr;
+        }
+        a.dJ = with_dJ ? dJ : nullptr;
+        a.E = E;
+        a.sje = jfe ? 1 : nf;
+        a.sjf = jfe ? E : 1;
+        a.sF = sF, a.sI = sI, a.sJ = sJ;
+        a.nb = nb;
+        a.with_dv = with_dv ? 1 : 0;
+        a.accumulate = k0 > 0 ? 1 : 0;
+        int rc;
+        switch (kind) {
+            case 0: rc = launch_facemass_adj<4, 3, 4>(a, s); break;
+            case 1: rc = launch_facemass_adj<10, 6, 4>(a, s); break;
+            case 2: rc = launch_facemass_adj<20, 10, 4>(a, s); break;
+            case 3: rc = launch_facemass_adj<35, 15, 4>(a, s); break;
+            case 4: rc = launch_facemass_adj<3, 2, 3>(a, s); break;
+            case 5: rc = launch_facemass_adj<6, 3, 3>(a, s); break;
+            case 6: rc = launch_facemass_adj<10, 4, 3>(a, s); break;
+            case 7: rc = launch_facemass_adj<15, 5, 3>(a, s); break;
+            default: rc = launch_facemass_adj<21, 6, 3>(a, s); break;
+        }
+        if (rc != FE_OK) return rc;
+    }
     return FE_OK;
 }
 

@@ -144,3 +144,77 @@ def match_family(einsum: BatchedEinsum) -> Optional[KernelPlan]:
         return KernelPlan(family, flags, {role: perm[k] for k, role in enumerate(roles)},
                           mapping["e"], params)
     return None
+
+
+# --------------------------------------------------------------------------
+# adjoint-only shapes: the einsums that the gradients of the DG families need and that no forward
+# family kernel covers.  Kept apart from match_family on purpose -- "auto" on a user-built einsum of one of these shapes
+# keeps its kernel; only the autograd path and the "adjoint" transform reach these kernels.
+# --------------------------------------------------------------------------
+
+ADJ_GEOM, ADJ_FACEMASS_V, ADJ_FACEMASS_J = "geomadj", "facemass_v", "facemass_j"
+GEOMADJ_NP = (3, 4, 6, 10, 15, 20, 21, 35)      # fe_geomadj_f64
+FACEMASS_ADJ_SHAPES = ((4, 4, 3), (4, 10, 6), (4, 20, 10), (4, 35, 15),               # fe_facemass_adj_f64: (nf, Np, Nfp)
+                       (3, 3, 2), (3, 6, 3), (3, 10, 4), (3, 15, 5), (3, 21, 6))
+
+# geometric-factor adjoint  out[x, r, e] = sum_i (sum_j K[r, i, j] a[e, j]) b[x, e, i]  in J's layouts; the div family's
+# J-adjoint ('rij,xej,ei->xre') is the grad template of the transposed operator up to operand order
+_ADJ_TEMPLATES = tuple(
+    (ADJ_GEOM, flag, f"{dsub},ej,{bsub}->{osub}", ("D", "a", "b"))
+    for bsub, osub, dsubs in (("xei", "xre", ("rij", "rji")), ("ei", "re", ("rij", "rji")), ("ei", "er", ("rij", "rji")),
+                              ("ei", "e", ("ij", "ji")))
+    for flag, dsub in zip((0, OP_TRANSPOSED), dsubs)
+) + tuple(
+    (ADJ_FACEMASS_V, jflag | rflag, f"{jsub},{rsub},ei->fej", ("J", "R", "g"))
+    for jflag, jsub in ((0, "ef"), (FM_J_FE, "fe"))
+    for rflag, rsub in ((0, "fij"), (FM_R_IFJ, "ifj"), (FM_R_T, "fji"), (FM_R_IFJ | FM_R_T, "jfi"))
+) + tuple(
+    (ADJ_FACEMASS_J, jflag | rflag, f"{rsub},fej,ei->{jsub}", ("R", "v", "g"))
+    for jflag, jsub in ((0, "ef"), (FM_J_FE, "fe"))
+    for rflag, rsub in ((0, "fij"), (FM_R_IFJ, "ifj"), (FM_R_T, "fji"), (FM_R_IFJ | FM_R_T, "jfi"))
+)
+
+
+@dataclass(frozen=True)
+class AdjointPlan:
+    """How the adjoint kernels evaluate an einsum: ``kind`` (``ADJ_GEOM`` / ``ADJ_FACEMASS_V`` / ``ADJ_FACEMASS_J``),
+    layout flags (``OP_TRANSPOSED``; ``FM_*``), ``roles`` (role -> operand position), the einsum's own letters of the
+    template's indices (``letters``: template letter -> einsum letter) and ``params`` (Np, X, R / nf, Nfp)."""
+
+    kind: str
+    layout_flags: int
+    roles: Dict[str, int]
+    letters: Dict[str, str]
+    params: Dict[str, int]
+
+    @property
+    def name(self) -> str:
+        return self.kind
+
+
+def match_adjoint_family(einsum: BatchedEinsum) -> Optional[AdjointPlan]:
+    """The :class:`AdjointPlan` of an adjoint-only einsum of a DG family (float64, compiled shapes), else ``None``."""
+    if {np.dtype(dt) for dt in einsum.arg_to_dtype.values()} != {np.dtype("float64")}:
+        return None
+    for kind, flags, subscripts, roles in _ADJ_TEMPLATES:
+        m = _match_template(einsum, subscripts)
+        if m is None:
+            continue
+        perm, mapping = m
+        dim = lambda t: einsum.index_to_dim_length[mapping[t]]  # noqa: E731
+        if any(isinstance(dim(t), SizeParam) for t in mapping if t != "e"):
+            continue
+        if kind == ADJ_GEOM:
+            X = int(dim("x")) if "x" in mapping else 1
+            R = int(dim("r")) if "r" in mapping else 1
+            Np = int(dim("i"))
+            if int(dim("j")) != Np or Np not in GEOMADJ_NP or not (1 <= X <= 3 and 1 <= R <= 3):
+                continue
+            params = {"Np": Np, "X": X, "R": R}
+        else:
+            shape = (int(dim("f")), int(dim("i")), int(dim("j")))
+            if shape not in FACEMASS_ADJ_SHAPES:
+                continue
+            params = {"nf": shape[0], "Np": shape[1], "Nfp": shape[2]}
+        return AdjointPlan(kind, flags, {role: perm[k] for k, role in enumerate(roles)}, dict(mapping), params)
+    return None

@@ -25,7 +25,8 @@ Argument conventions kept from the reference:
                a variant explicitly (``"contraction"``: the einsum as strided batched
                contractions on the matrix cores, ``feinsum_amd.contraction``; ``"reduction"``: a long summation
                space summed into a small output as a split reduction over the whole chip,
-               ``feinsum_amd.reduction``); in a dict, ``"prepared": True`` lets a
+               ``feinsum_amd.reduction``; ``"adjoint"``: the adjoint kernels of the DG families, for the einsums
+               ``family.match_adjoint_family`` recognises only); in a dict, ``"prepared": True`` lets a
                bound launch (``timeit``) use a prepared copy of its operator
                matrices; ``"placement"`` (or ``$FEINSUM_PLACEMENT``): ``timeit``
                allocates one array per operand as the reference does; with the
@@ -59,9 +60,10 @@ from feinsum_amd.contraction_schedule import ContractionSchedule, count_ops
 from feinsum_amd.diagnostics import (HipLibraryError, InvalidParameterError,
                                      NoDevicePeaksInfoError, TransformValidationError)
 from feinsum_amd.einsum import INT_CLASSES, BatchedEinsum, SizeParam
+from feinsum_amd.adjoint import AdjointLaunch
 from feinsum_amd.family import (FAMILY_DIV, FAMILY_DIVCOMP, FAMILY_FACEMASS, FAMILY_GRAD,
                                 FAMILY_GRADPLANES, FAMILY_MATAPPLY, OP_J_ES, KernelPlan,
-                                match_family)
+                                match_adjoint_family, match_family)
 
 logger = logging.getLogger(__name__)
 
@@ -452,9 +454,16 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     families where ``reduction.auto_picks_reduction`` finds a long summation space summed into a small output),
     ``"contraction"`` (the transform of that name, or ``"auto"`` on a two-operand einsum outside the DG families where
     ``contraction.auto_picks_contraction`` says the contraction kernel wins), ``"family"`` (a DG family kernel) or
-    ``"generic"``.  The reduction rule is checked before the contraction rule.
+    ``"generic"``.  The reduction rule is checked before the contraction rule.  ``"adjoint"`` (that transform only: an
+    einsum that ``family.match_adjoint_family`` recognises, else ``NotImplementedError``) runs the adjoint kernels.
     """
     variant = _variant_from_transform(transform)
+    if variant == "adjoint":
+        if match_adjoint_family(einsum) is None:
+            raise NotImplementedError(
+                f"einsum '{einsum.get_subscripts()}' is not one of the adjoint kernels' shapes"
+                " (feinsum_amd.family.match_adjoint_family)")
+        return "adjoint"
     if variant == "contraction":
         return "contraction"
     if variant == "reduction":
@@ -503,6 +512,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
         bound = ContractionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
     elif kind == "reduction":
         bound = ReductionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
+    elif kind == "adjoint":
+        bound = AdjointLaunch(match_adjoint_family(einsum), einsum, arg_dict, outs)
     elif kind == "family":
         bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform))
         if _prepared_from_transform(transform, prepare):

@@ -574,6 +574,28 @@ int fe_einsum_reduce_plan(const fe_einsum_desc* desc, int32_t* path, int64_t* sl
 int fe_einsum_reduce(const fe_einsum_desc* desc, const void* const* operands, void* out, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- adjoint kernels of the DG families (feinsum_amd/csrc/fe_adjoint.h) ----
+ *
+ * The gradient of grad / div / div component / element-local operator with respect to the geometric factors:
+ *   out[x * sx + r * sr + e * se] = sum_i (sum_j K[r][i][j] a[e][j]) b[x][e][i]      0 <= x < X, 0 <= r < R
+ * with K = D[R][Np][Np], or D stored [R][Np(j)][Np(i)] with FE_OP_TRANSPOSED in op_flags; a [E][Np]; b [X][E][Np];
+ * X, R in 1..3 and Np in {3, 4, 6, 10, 15, 20, 21, 35} (tetrahedra p = 1..4, triangles p = 1..5), else FE_EUNSUPPORTED.
+ * The strides place the output in J's layout ('xre', 're', 'er', 'e').  Every output entry is written; E == 0 launches
+ * nothing.  Asynchronous on `stream`; bitwise reproducible. */
+int fe_geomadj_f64(const double* D, const double* a, const double* b, double* out, int64_t E, int32_t X, int32_t R,
+                   int32_t Np, int32_t op_flags, int64_t sx, int64_t sr, int64_t se, void* stream);
+
+/* The gradient of face-mass ('ef,fij,fej->ei' and its layout siblings, FE_FM_* in layout_flags) for b fields that share
+ * J and R, given the output gradients g_k [E][Np]:
+ *   dv_k[f][e][j] = J[e, f] sum_i R[f, i, j] g_k[e][i]                              (dv != NULL; J is read)
+ *   dJ[e, f]      = sum_k sum_j (sum_i R[f, i, j] g_k[e][i]) v_k[f][e][j]            (v != NULL and dJ != NULL)
+ * dJ has J's layout; the fields are summed in their order, so dJ is bitwise reproducible.  v == NULL skips dJ and reads
+ * no v; dv == NULL skips dv and reads no J.  (nf, Np, Nfp) in {(4, 4, 3), (4, 10, 6), (4, 20, 10), (4, 35, 15)} and
+ * (3, (p + 1)(p + 2) / 2, p + 1) for triangles p = 1..5, else FE_EUNSUPPORTED. */
+int fe_facemass_adj_f64(const double* J, const double* R, const double* const* g, const double* const* v,
+                        double* const* dv, double* dJ, int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
+                        int32_t layout_flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
