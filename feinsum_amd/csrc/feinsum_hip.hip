@@ -12,6 +12,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <unordered_map>
 #include <utility>
@@ -434,6 +435,8 @@ struct LastLaunch {
     long long tiles = 0, static_tiles = 0;
 };
 thread_local LastLaunch g_last_launch;
+// (at the entry of every family's entry point: a call that runs only tiled or generic kernels reports no launch)
+void forget_last_launch() { g_last_launch.valid = 0; }
 void note_launch(bool dynamic, int flags, unsigned blocks, int waves_per_block, int64_t tiles, int64_t static_tiles, int kind = 0, int bodies = 1) {
     LastLaunch& L = g_last_launch;
     L.valid = 1;
@@ -448,45 +451,119 @@ void note_launch(bool dynamic, int flags, unsigned blocks, int waves_per_block, 
     L.static_tiles = dynamic ? static_tiles : tiles;
 }
 
-// Persistent-style grid for the per-wave-tile kernels: 2 blocks of 4 waves per
-// CU (their VGPR / LDS residency), fewer when there is less work.
+// Persistent-style grid: a block per `wavesPerBlock` tiles, at most `per_cu` blocks per CU.
 // (a per-wave-equal grid -- every wave the same number of tiles, on fewer waves -- was measured in round 3 and is slower at
 // every size: profiles/r03/balanced_grid_ab.txt)
-unsigned persistent_grid(int64_t nTiles, int wavesPerBlock) {
+unsigned grid_for(int64_t nTiles, int wavesPerBlock, int per_cu) {
     const int64_t blocks = (nTiles + wavesPerBlock - 1) / wavesPerBlock;
-    const int64_t cap = (8 / wavesPerBlock) * (int64_t)device_cu_count();   // 8 waves per CU
+    const int64_t cap = per_cu * (int64_t)device_cu_count();
     return (unsigned)(blocks < cap ? blocks : cap);
 }
+// ... of 8 waves per CU (2 blocks of 4 waves: the VGPR / LDS residency of the per-wave-tile kernels)
+unsigned persistent_grid(int64_t nTiles, int wavesPerBlock) { return grid_for(nTiles, wavesPerBlock, 8 / wavesPerBlock); }
 
-// grad of tetrahedra p = 5 (Np = 56): grad by components with the A fragments in LDS, one block per CU
+// ---- one persistent MFMA launch: every DG family launcher goes through mfma_launch below, which owns the four rules the
+// launchers share -- which once-flag configures a kernel, how large the grid is, which walk the launch takes, what is recorded.
+
+// configure_kernel once per (kernel INSTANTIATION, device): the flag is keyed on the kernel itself.  Many instantiations share
+// one signature (grad3d_mfma_kernel<35, 1, 0> and <20, 2, 0>); a flag keyed on the pointer's type would configure only the
+// first of them and silently skip the LDS attribute of the rest.  A failure of one instantiation (say the opt-in
+// prepared-operator one) cannot fail the launches of its siblings for the rest of the process.
+template <auto K>
+int configured(const char* what, int lds_bytes, int threads, int blocks_per_cu) {
+    static PerDeviceOnce once;
+    return once.run([&] { return configure_kernel(K, what, lds_bytes, threads, blocks_per_cu); });
+}
+
+// A kernel's launch geometry: blocks of `waves` waves (`threads` threads, `lds` bytes of dynamic LDS), `resident` of them per
+// CU (configure_kernel checks that), and the launcher's grid rule: at most `per_cu` blocks per CU.
+struct Geometry {
+    int waves, threads, lds, resident, per_cu;
+};
+
+// Which tiles may come by tickets (fe_common.h, dynamic walk): bit b of `tickets` for body b -- one body, or the div, grad and
+// lift bodies of a fused launch, each walked on its own over one counter set of a group (tail_slot(s, bodies)).
+struct Walk {
+    int64_t tiles[3];
+    int bodies;
+    unsigned tickets;
+    bool units;   // tail_static_tiles' `units` (face-mass x 4); its `fused` is bodies > 1
+};
+Walk walk_static(int64_t tiles) { return {{tiles, 0, 0}, 1, 0u, false}; }
+Walk walk_tickets(int64_t tiles, bool tickets = true, bool units = false) { return {{tiles, 0, 0}, 1, tickets ? 1u : 0u, units}; }
+
+// What mfma_launch decided: the grid, the tiles each body walks statically, the counters of a dynamic walk (or null).
+struct Launch {
+    unsigned grid;
+    int waves_per_block;
+    int64_t t_static[3];
+    unsigned* tail;
+    int64_t waves() const { return (int64_t)grid * waves_per_block; }
+};
+
+// The kernel arguments of one launch, with the flags and `kind` bits (fe_last_launch_info) recorded for it.
+template <typename... A>
+struct Call {
+    int flags, kind;
+    std::tuple<A...> args;
+};
+template <typename... A>
+Call<A...> call(int flags, int kind, A... args) { return {flags, kind, std::tuple<A...>(args...)}; }
+
+// Configure K (and KT when it runs), size the grid, walk statically or by tickets, enqueue, record.  `static_call(L)` gives K's
+// arguments; when tickets were granted and KT is a kernel, `tail_call(L)` gives KT's (the counters are L.tail, behind
+// L.t_static[0] tiles).  A null KT walks statically -- except a fused launch, whose kernel takes the counters itself: it passes
+// itself as KT and the same arguments for both.
+template <auto K, auto KT = nullptr, typename SC, typename TC = std::nullptr_t>
+int mfma_launch(hipStream_t s, const Walk& w, const Geometry& g, const char* what, SC static_call, const char* tail_what = nullptr,
+                TC tail_call = nullptr) {
+    if (int rc = configured<K>(what, g.lds, g.threads, g.resident)) return rc;
+    int64_t most = 0, tiles = 0, t_static = 0;
+    for (int b = 0; b < w.bodies; ++b) {
+        most = w.tiles[b] > most ? w.tiles[b] : most;
+        tiles += w.tiles[b];
+    }
+    Launch L = {grid_for(most, g.waves, g.per_cu), g.waves, {w.tiles[0], w.tiles[1], w.tiles[2]}, nullptr};
+    bool dynamic = false;
+    if constexpr (KT != nullptr) {
+        for (int b = 0; b < w.bodies; ++b)
+            if (w.tickets & (1u << b)) {
+                L.t_static[b] = tail_static_tiles(w.tiles[b], L.grid, g.waves, w.bodies > 1, w.units);
+                dynamic = dynamic || L.t_static[b] < w.tiles[b];
+            }
+        if (dynamic) L.tail = tail_slot(s, w.bodies);
+    }
+    for (int b = 0; b < w.bodies; ++b) t_static += L.t_static[b];
+    auto enqueue = [&](auto kernel, const auto& c) {
+        std::apply([&](auto... a) { hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(g.threads), g.lds, s, a...); }, c.args);
+        note_launch(L.tail != nullptr, c.flags, L.grid, g.waves, tiles, t_static, c.kind, w.bodies);
+        return FE_OK;
+    };
+    if constexpr (KT != nullptr) {
+        if (L.tail) {
+            if (int rc = configured<KT>(tail_what, g.lds, g.threads, g.resident)) return rc;
+            return enqueue(KT, tail_call(L));
+        }
+    }
+    return enqueue(K, static_call(L));
+}
+
+// The p = 5 kernels (Np = 56): eight waves per block share the A fragments in LDS, one block per CU
+template <typename G>
+constexpr Geometry w8_geometry() { return {G::WAVES, G::THREADS, G::LDS_BYTES, G::BLOCKS_PER_CU, 1}; }
+
+// grad of tetrahedra p = 5: grad by components
 int launch_grad_p5(const double* J, const double* D, const fe::FieldPtrs& P, int nb, int64_t E, int opT,
                    hipStream_t s, bool* launched, int dbg = 0) {
-    using G = fe::DivGeom<56, 1, 4, 3, true, true>;   // eight waves per block, one block per CU
+    using G = fe::DivGeom<56, 1, 4, 3, true, true>;
     const int64_t nTiles = E / G::TEL;
     *launched = nTiles > 0;   // the launch covers the elements behind the last tile too
     if (nTiles == 0) return FE_OK;
-    static PerDeviceOnce once;
-    const int attr_rc =
-        once.run([] {
-        return configure_kernel(fe::div3d_mfma_kernel<56, 1, 0, 4, 3, true, true>, "grad p5 (components, A in LDS)", G::LDS_BYTES,
-                                G::THREADS, G::BLOCKS_PER_CU);
-    });
-    if (attr_rc != FE_OK) return attr_rc;
     opT |= phase_priority_flag_p5();
-    const int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES, cap = device_cu_count();
+    auto args = [&](const Launch&) { return call(opT, 0, J, D, nullptr, P, nb, E, nTiles, opT, 0); };
 #ifdef FE_EXPERIMENTS
-#define FE_P5_CASE(DBG)                                                                                                   \
-    case DBG: {                                                                                                           \
-        static PerDeviceOnce once_dbg;                                                                                    \
-        once_dbg.run([] {                                                                                                 \
-            return configure_kernel(fe::div3d_mfma_kernel<56, 1, DBG, 4, 3, true, true>, "experiment", G::LDS_BYTES,      \
-                                    G::THREADS, G::BLOCKS_PER_CU);                                                        \
-        });                                                                                                               \
-        hipLaunchKernelGGL((fe::div3d_mfma_kernel<56, 1, DBG, 4, 3, true, true>),                                         \
-                           dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(G::THREADS), G::LDS_BYTES, s, J, D,        \
-                           nullptr, P, nb, E, nTiles, opT, 0);                                                            \
-        return FE_OK;                                                                                                     \
-    }
+#define FE_P5_CASE(DBG) \
+    case DBG: return mfma_launch<fe::div3d_mfma_kernel<56, 1, DBG, 4, 3, true, true>>(s, walk_static(nTiles), w8_geometry<G>(), "experiment", args);
     switch (dbg) {
         FE_P5_CASE(1) FE_P5_CASE(2) FE_P5_CASE(3) FE_P5_CASE(4) FE_P5_CASE(5) FE_P5_CASE(6) FE_P5_CASE(8) FE_P5_CASE(9) FE_P5_CASE(10) FE_P5_CASE(11) FE_P5_CASE(32) FE_P5_CASE(16) FE_P5_CASE(64) FE_P5_CASE(80)
         default: break;
@@ -495,97 +572,41 @@ int launch_grad_p5(const double* J, const double* D, const fe::FieldPtrs& P, int
 #else
     (void)dbg;
 #endif
-    const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
-    if (nb == 1) {   // behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk)
-        const int64_t t_static = tail_static_tiles(nTiles, grid, G::WAVES);
-        unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-        if (tail) {
-            static PerDeviceOnce once_tail;
-            if (int rc = configured(once_tail, fe::grad_w8_tail_kernel<56>, "grad p5 (components, A in LDS), dynamic walk", G::LDS_BYTES,
-                                    G::THREADS, G::BLOCKS_PER_CU))
-                return rc;
-            hipLaunchKernelGGL((fe::grad_w8_tail_kernel<56>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, J, D, P, nb, E, nTiles, opT, tail,
-                               t_static);
-            return FE_OK;
-        }
-    }
-    hipLaunchKernelGGL((fe::div3d_mfma_kernel<56, 1, 0, 4, 3, true, true>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, J, D, nullptr,
-                       P, nb, E, nTiles, opT, 0);
-    return FE_OK;
+    // one field: behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk)
+    return mfma_launch<fe::div3d_mfma_kernel<56, 1, 0, 4, 3, true, true>, fe::grad_w8_tail_kernel<56>>(
+        s, walk_tickets(nTiles, nb == 1), w8_geometry<G>(), "grad p5 (components, A in LDS)", args,
+        "grad p5 (components, A in LDS), dynamic walk",
+        [&](const Launch& L) { return call(opT, 0, J, D, P, nb, E, nTiles, opT, L.tail, L.t_static[0]); });
 }
 
-// grad-type planes of tetrahedra p = 5 (MODE 5 of the div template): D u once per field, eight waves per block
+// grad-type planes of tetrahedra p = 5 (MODE 5 of the div template): D u once per field
 int launch_gradplanes_p5(const fe::GradFields& Q, const double* D, int nb, int64_t E, int opT, hipStream_t s,
                          bool* launched) {
     using G = fe::DivGeom<56, 1, 5, 3, true, true>;
     const int64_t nTiles = E / G::TEL;
     *launched = nTiles > 0;   // the launch covers the elements behind the last tile too
     if (nTiles == 0) return FE_OK;
-    static PerDeviceOnce once;
-    const int attr_rc = once.run([] {
-        return configure_kernel(fe::gradplanes_bycomp_kernel<56>, "grad planes p5 (components, A in LDS)", G::LDS_BYTES,
-                                G::THREADS, G::BLOCKS_PER_CU);
-    });
-    if (attr_rc != FE_OK) return attr_rc;
     fe::FieldPtrs P = {};
     for (int k = 0; k < nb; ++k) P.v[k] = Q.u[k];
-    const int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES, cap = device_cu_count();
-    hipLaunchKernelGGL(fe::gradplanes_bycomp_kernel<56>, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(G::THREADS),
-                       G::LDS_BYTES, s, Q, D, P, nb, E, nTiles, opT);
-    return FE_OK;
+    return mfma_launch<fe::gradplanes_bycomp_kernel<56>>(s, walk_static(nTiles), w8_geometry<G>(), "grad planes p5 (components, A in LDS)",
+                                                         [&](const Launch&) { return call(opT, 0, Q, D, P, nb, E, nTiles, opT); });
 }
 
-// div of tetrahedra p = 5: the A fragments in LDS and the u planes streamed -- eight waves per block with one plane buffer each
-// (round 4; FEINSUM_DIV_P5_WAVES=4: round 2's four waves with two buffers each, kept for the A/B)
+// div of tetrahedra p = 5: the A fragments in LDS and the u planes streamed, one plane buffer per wave (round 4; round 2's four
+// waves with two buffers each measured slower at E = 1e6 -- profiles/r04/p5_div_eight_waves.txt -- and were removed)
 int launch_div_p5(const double* J, const double* D, const fe::FieldPtrs& P, int nb, int64_t E, int opT,
                   hipStream_t s, bool* launched) {
-    static const bool four_waves = [] { const char* e = getenv("FEINSUM_DIV_P5_WAVES"); return e && atoi(e) == 4; }();
-    if (!four_waves) {
-        using G = fe::DivGeom<56, 1, 0, 3, true, true>;
-        const int64_t nTiles = E / G::TEL;
-        *launched = nTiles > 0;   // the launch covers the elements behind the last tile too
-        if (nTiles == 0) return FE_OK;
-        static PerDeviceOnce once;
-        const int attr_rc = once.run([] {
-            return configure_kernel(fe::div3d_mfma_kernel<56, 1, 0, 0, 3, true, true>, "div p5 (A in LDS, planes streamed, eight waves)", G::LDS_BYTES,
-                                    G::THREADS, G::BLOCKS_PER_CU);
-        });
-        if (attr_rc != FE_OK) return attr_rc;
-        opT |= phase_priority_flag_p5();
-        const int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES, cap = device_cu_count();
-        const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
-        if (nb == 1) {   // behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk)
-            const int64_t t_static = tail_static_tiles(nTiles, grid, G::WAVES);
-            unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-            if (tail) {
-                static PerDeviceOnce once_tail;
-                if (int rc = configured(once_tail, fe::div_w8_tail_kernel<56>, "div p5 (A in LDS, planes streamed, eight waves), dynamic walk",
-                                        G::LDS_BYTES, G::THREADS, G::BLOCKS_PER_CU))
-                    return rc;
-                hipLaunchKernelGGL((fe::div_w8_tail_kernel<56>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, J, D, P, nb, E, nTiles, opT, tail,
-                                   t_static);
-                return FE_OK;
-            }
-        }
-        hipLaunchKernelGGL((fe::div3d_mfma_kernel<56, 1, 0, 0, 3, true, true>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, J, D, nullptr, P,
-                           nb, E, nTiles, opT, 0);
-        return FE_OK;
-    }
-    using G = fe::DivGeom<56, 1, 0, 3, true>;
+    using G = fe::DivGeom<56, 1, 0, 3, true, true>;
     const int64_t nTiles = E / G::TEL;
     *launched = nTiles > 0;   // the launch covers the elements behind the last tile too
     if (nTiles == 0) return FE_OK;
-    static PerDeviceOnce once;
-    const int attr_rc = once.run([] {
-        return configure_kernel(fe::div3d_mfma_kernel<56, 1, 0, 0, 3, true>, "div p5 (A in LDS, planes streamed)", G::LDS_BYTES, 256,
-                                G::BLOCKS_PER_CU);
-    });
-    if (attr_rc != FE_OK) return attr_rc;
-    const int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES, cap = device_cu_count();
-    const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
-    hipLaunchKernelGGL((fe::div3d_mfma_kernel<56, 1, 0, 0, 3, true>), dim3(grid), dim3(256), G::LDS_BYTES, s, J, D, nullptr, P, nb, E,
-                       nTiles, opT, 0);
-    return FE_OK;
+    opT |= phase_priority_flag_p5();
+    // one field: behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk)
+    return mfma_launch<fe::div3d_mfma_kernel<56, 1, 0, 0, 3, true, true>, fe::div_w8_tail_kernel<56>>(
+        s, walk_tickets(nTiles, nb == 1), w8_geometry<G>(), "div p5 (A in LDS, planes streamed, eight waves)",
+        [&](const Launch&) { return call(opT, 0, J, D, nullptr, P, nb, E, nTiles, opT, 0); },
+        "div p5 (A in LDS, planes streamed, eight waves), dynamic walk",
+        [&](const Launch& L) { return call(opT, 0, J, D, P, nb, E, nTiles, opT, L.tail, L.t_static[0]); });
 }
 
 // ---- the LDS-tiled VALU kernel (fe_tiled.h): any shape whose operator fits in LDS
@@ -654,131 +675,78 @@ int launch_grad(const fe::GradFields& P, bool plain, const double* D, const void
     *e_done = nTiles > 0 ? E : 0;   // the launch covers the elements behind the last tile too (remainder_items)
     if (nTiles == 0) return FE_OK;
     opT |= temporal_flag((9 + (int64_t)nb * NP) * E * 8);
-    static PerDeviceOnce once_plain, once_prepared, once_planes;
-    char what[64];
+    const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, 2, 8 / G::WAVES};
     const void* gsec = prep ? static_cast<const char*>(prep) + fe::kPrepGradOff : nullptr;
-    int attr_rc;
-    if (!plain) {
-        snprintf(what, sizeof(what), "grad planes Np=%d M=%d", NP, M);
-        attr_rc = configured(once_planes, fe::grad3d_mfma_kernel<NP, M, 0, false>, what, G::LDS_BYTES, 256, 2);
-    } else if (gsec) {
-        snprintf(what, sizeof(what), "grad Np=%d M=%d, prepared operator", NP, M);
-        attr_rc = configured(once_prepared, fe::grad3d_mfma_kernel<NP, M, 0, true, true>, what, G::LDS_BYTES, 256, 2);
-    } else {
-        snprintf(what, sizeof(what), "grad Np=%d M=%d", NP, M);
-        attr_rc = configured(once_plain, fe::grad3d_mfma_kernel<NP, M, 0>, what, G::LDS_BYTES, 256, 2);
-    }
-#ifdef FE_EXPERIMENTS
-    static PerDeviceOnce once_exp;
-    once_exp.run([] {
-        if (NP == 35) {
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 1>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 2>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 4>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 16>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 20>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 32>, "experiment", G::LDS_BYTES + fe::kDbgTileLdsBytes, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 64>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 96>, "experiment", G::LDS_BYTES + fe::kDbgTileLdsBytes, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 128>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 32, true, true>, "experiment", G::LDS_BYTES + fe::kDbgTileLdsBytes, 256, 1);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 0>, "grad (experiments build)", G::LDS_BYTES, 256, 2);
-            configure_kernel(fe::grad3d_mfma_kernel<NP, M, 0, true, true>, "grad prepared (experiments build)", G::LDS_BYTES, 256, 2);
-        }
-        return FE_OK;
-    });
-#endif
-    if (attr_rc != FE_OK) return attr_rc;
-    const dim3 g(persistent_grid(nTiles, G::WAVES)), b(256);
+    char what[64], tail_what[64];
+    auto args = [&](const Launch&) { return call(opT, 0, P, D, nullptr, nb, nx, E, nTiles, opT); };
+    auto tail_args = [&](const Launch& L) { return call(opT, 0, P, D, nb, E, nTiles, opT, L.tail, L.t_static[0]); };
     if (!plain) {   // general planes: per-plane geometry-factor and output pointers
-        hipLaunchKernelGGL((fe::grad3d_mfma_kernel<NP, M, 0, false>), g, b, G::LDS_BYTES, s, P, D, nullptr, nb, nx, E,
-                           nTiles, opT);
-        return FE_OK;
+        snprintf(what, sizeof(what), "grad planes Np=%d M=%d", NP, M);
+        return mfma_launch<fe::grad3d_mfma_kernel<NP, M, 0, false>>(s, walk_static(nTiles), geo, what, args);
     }
 #ifdef FE_EXPERIMENTS
-#define FE_GRAD_LDS(DBG) (G::LDS_BYTES + (((DBG) & 32) ? fe::kDbgTileLdsBytes : 0))   // (the per-tile stamps live behind the kernel's own LDS)
-#else
-#define FE_GRAD_LDS(DBG) G::LDS_BYTES
-#endif
-#define FE_GRAD_CASE(DBG) \
-    hipLaunchKernelGGL((fe::grad3d_mfma_kernel<NP, M, DBG>), g, b, FE_GRAD_LDS(DBG), s, P, D, nullptr, nb, nx, E, nTiles, opT)
+    // (the per-tile stamps of 32 and 96 live behind the kernel's own LDS)
+    const Geometry dbg_geo = {G::WAVES, 256, G::LDS_BYTES, 1, 8 / G::WAVES},
+                   stamps_geo = {G::WAVES, 256, G::LDS_BYTES + fe::kDbgTileLdsBytes, 1, 8 / G::WAVES};
+#define FE_GRAD_CASE(DBG, GEO) \
+    case DBG: return mfma_launch<fe::grad3d_mfma_kernel<NP, M, DBG>>(s, walk_static(nTiles), GEO, "experiment", args);
     switch (NP == 35 ? dbg : 0) {
-#ifdef FE_EXPERIMENTS
-        case 1: FE_GRAD_CASE(1); break;
-        case 2: FE_GRAD_CASE(2); break;
-        case 3: FE_GRAD_CASE(3); break;     // data movement in: loads only
-        case 4: FE_GRAD_CASE(4); break;     // temporal stores
-        case 8: FE_GRAD_CASE(8); break;     // no loads
-        case 9: FE_GRAD_CASE(9); break;     // stores + stage 2
-        case 10: FE_GRAD_CASE(10); break;   // arithmetic and LDS only
-        case 11: FE_GRAD_CASE(11); break;   // stage 2 and LDS only
-        case 16: FE_GRAD_CASE(16); break;   // temporal loads
-        case 20: FE_GRAD_CASE(20); break;   // both
-        case 32:
-            if (gsec) {
-                hipLaunchKernelGGL((fe::grad3d_mfma_kernel<NP, M, 32, true, true>), g, b, G::LDS_BYTES + fe::kDbgTileLdsBytes, s, P, D, gsec, nb, nx,
-                                   E, nTiles, opT);
-                break;
-            }
-            if (nb == 1) {   // per-wave time stamps of the dynamic walk
-                const int64_t t_static = tail_static_tiles(nTiles, g.x, G::WAVES);
-                unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-                if (tail) {
-                    static PerDeviceOnce once_stamps;
-                    once_stamps.run([] { return configure_kernel(fe::grad3d_mfma_tail_kernel<NP, M, 32>, "experiment", G::LDS_BYTES + fe::kDbgTileLdsBytes, 256, 1); });
-                    hipLaunchKernelGGL((fe::grad3d_mfma_tail_kernel<NP, M, 32>), g, b, G::LDS_BYTES + fe::kDbgTileLdsBytes, s, P, D, nb, E, nTiles, opT, tail, t_static);
-                    break;
-                }
-            }
-            if (nb == 1) opT |= write_through_flag(3 * (int64_t)NP * E * 8) | grad_quarter_flag(M, nb, nTiles, (int64_t)g.x * G::WAVES);   // (as the product's static walk)
-            hipLaunchKernelGGL((fe::grad3d_mfma_kernel<NP, M, 32>), g, b, G::LDS_BYTES + fe::kDbgTileLdsBytes, s, P, D, nullptr, nb, nx, E, nTiles, opT);
-            break;
-        case 64: FE_GRAD_CASE(64); break;
-        case 96: FE_GRAD_CASE(96); break;
-        case 128: FE_GRAD_CASE(128); break;
-#endif
-        default:
-            if (gsec) {
-                hipLaunchKernelGGL((fe::grad3d_mfma_kernel<NP, M, 0, true, true>), g, b, G::LDS_BYTES, s, P, D, gsec, nb, nx,
-                                   E, nTiles, opT);
-                break;
-            }
-            {
-                {   // behind two static rounds the tiles come by tickets (fe_common.h: dynamic walk); any number of fields
-                    const int64_t t_static = tail_static_tiles(nTiles, g.x, G::WAVES);
-                    unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-                    if (tail) {
-                        static PerDeviceOnce once_tail;
-                        if (nb == 1) {
-                            snprintf(what, sizeof(what), "grad Np=%d M=%d, dynamic walk", NP, M);
-                            if (int rc = configured(once_tail, fe::grad3d_mfma_tail_kernel<NP, M>, what, G::LDS_BYTES, 256, 2)) return rc;
-                            opT |= write_through_flag(3 * (int64_t)NP * E * 8);   // (short launches: the same rule as the static walk)
-                            hipLaunchKernelGGL((fe::grad3d_mfma_tail_kernel<NP, M>), g, b, G::LDS_BYTES, s, P, D, nb, E, nTiles, opT, tail, t_static);
-                            note_launch(true, opT, g.x, G::WAVES, nTiles, t_static);
-                            break;
-                        }
-                        {   // b fields
-                            static PerDeviceOnce once_tail_b;
-                            snprintf(what, sizeof(what), "grad Np=%d M=%d x b, dynamic walk", NP, M);
-                            if (int rc = configured(once_tail_b, fe::grad3d_mfma_tail_kernel<NP, M, 0, true>, what, G::LDS_BYTES, 256, 2)) return rc;
-                            hipLaunchKernelGGL((fe::grad3d_mfma_tail_kernel<NP, M, 0, true>), g, b, G::LDS_BYTES, s, P, D, nb, E, nTiles, opT, tail,
-                                               t_static);
-                            note_launch(true, opT, g.x, G::WAVES, nTiles, t_static);
-                            break;
-                        }
-                    }
-                }
-            }
-            if (nb == 1)   // (static walk, one field: a short launch)
-                opT |= write_through_flag(3 * (int64_t)NP * E * 8) | grad_quarter_flag(M, nb, nTiles, (int64_t)g.x * G::WAVES) |
-                       grad_stagger_flag(NP, M, nb, nTiles, (int64_t)g.x * G::WAVES);
-            FE_GRAD_CASE(0);
-            note_launch(false, opT, g.x, G::WAVES, nTiles, nTiles, ((opT & fe::kOpQuarterTail) ? 8 : 0) | ((opT & fe::kOpStaggeredStart) ? 16 : 0));
-            break;
+        FE_GRAD_CASE(1, dbg_geo)
+        FE_GRAD_CASE(2, dbg_geo)
+        FE_GRAD_CASE(3, dbg_geo)     // data movement in: loads only
+        FE_GRAD_CASE(4, dbg_geo)     // temporal stores
+        FE_GRAD_CASE(8, dbg_geo)     // no loads
+        FE_GRAD_CASE(9, dbg_geo)     // stores + stage 2
+        FE_GRAD_CASE(10, dbg_geo)    // arithmetic and LDS only
+        FE_GRAD_CASE(11, dbg_geo)    // stage 2 and LDS only
+        FE_GRAD_CASE(16, dbg_geo)    // temporal loads
+        FE_GRAD_CASE(20, dbg_geo)    // both
+        case 32:                     // per-wave time stamps, of the dynamic walk too (one field)
+            if (gsec)
+                return mfma_launch<fe::grad3d_mfma_kernel<NP, M, 32, true, true>>(
+                    s, walk_static(nTiles), stamps_geo, "experiment",
+                    [&](const Launch&) { return call(opT, 0, P, D, gsec, nb, nx, E, nTiles, opT); });
+            return mfma_launch<fe::grad3d_mfma_kernel<NP, M, 32>, fe::grad3d_mfma_tail_kernel<NP, M, 32>>(
+                s, walk_tickets(nTiles, nb == 1), stamps_geo, "experiment",
+                [&](const Launch& L) {   // (as the product's static walk)
+                    const int f = opT | (nb == 1 ? write_through_flag(3 * (int64_t)NP * E * 8) | grad_quarter_flag(M, nb, nTiles, L.waves()) : 0);
+                    return call(f, 0, P, D, nullptr, nb, nx, E, nTiles, f);
+                },
+                "experiment", tail_args);
+        FE_GRAD_CASE(64, dbg_geo)
+        FE_GRAD_CASE(96, stamps_geo)
+        FE_GRAD_CASE(128, dbg_geo)
+        default: break;
     }
 #undef FE_GRAD_CASE
-#undef FE_GRAD_LDS
-    return FE_OK;
+#else
+    (void)dbg;
+#endif
+    if (gsec) {
+        snprintf(what, sizeof(what), "grad Np=%d M=%d, prepared operator", NP, M);
+        return mfma_launch<fe::grad3d_mfma_kernel<NP, M, 0, true, true>>(
+            s, walk_static(nTiles), geo, what, [&](const Launch&) { return call(opT, 0, P, D, gsec, nb, nx, E, nTiles, opT); });
+    }
+    // behind two static rounds the tiles come by tickets (fe_common.h: dynamic walk); any number of fields.  One field (a short
+    // launch) writes through under either walk; under the static walk its ragged last round runs as quarter tiles and it starts
+    // staggered (the rules: grad_quarter_flag, grad_stagger_flag)
+    auto static_args = [&](const Launch& L) {
+        const int f = opT | (nb == 1 ? write_through_flag(3 * (int64_t)NP * E * 8) | grad_quarter_flag(M, nb, nTiles, L.waves()) |
+                                           grad_stagger_flag(NP, M, nb, nTiles, L.waves())
+                                     : 0);
+        return call(f, ((f & fe::kOpQuarterTail) ? 8 : 0) | ((f & fe::kOpStaggeredStart) ? 16 : 0), P, D, nullptr, nb, nx, E, nTiles, f);
+    };
+    snprintf(what, sizeof(what), "grad Np=%d M=%d", NP, M);
+    if (nb == 1) {
+        snprintf(tail_what, sizeof(tail_what), "grad Np=%d M=%d, dynamic walk", NP, M);
+        const int f = opT | write_through_flag(3 * (int64_t)NP * E * 8);
+        return mfma_launch<fe::grad3d_mfma_kernel<NP, M, 0>, fe::grad3d_mfma_tail_kernel<NP, M>>(
+            s, walk_tickets(nTiles), geo, what, static_args, tail_what,
+            [&](const Launch& L) { return call(f, 0, P, D, nb, E, nTiles, f, L.tail, L.t_static[0]); });
+    }
+    snprintf(tail_what, sizeof(tail_what), "grad Np=%d M=%d x b, dynamic walk", NP, M);
+    return mfma_launch<fe::grad3d_mfma_kernel<NP, M, 0>, fe::grad3d_mfma_tail_kernel<NP, M, 0, true>>(
+        s, walk_tickets(nTiles), geo, what, static_args, tail_what, tail_args);
 }
 
 template <int NP, int M>
@@ -789,117 +757,72 @@ int launch_div(const double* J, const double* D, const void* prep, const fe::Fie
     *e_done = nTiles > 0 ? E : 0;   // the launch covers the elements behind the last tile too (remainder_items)
     if (nTiles == 0) return FE_OK;
     opT |= temporal_flag((9 + 3 * (int64_t)nb * NP) * E * 8, kTemporalFloorDiv, kTemporalCapDivMib);
-    static PerDeviceOnce once_plain, once_prepared;
-    char what[64];
-    int attr_rc;
-    if (prep) {
-        snprintf(what, sizeof(what), "div Np=%d M=%d, prepared operator", NP, M);
-        attr_rc = configured(once_prepared, fe::div3d_mfma_kernel<NP, M, 0, 0, 3, false, false, true>, what, G::LDS_BYTES, 256,
-                             G::BLOCKS_PER_CU);
-    } else {
-        snprintf(what, sizeof(what), "div Np=%d M=%d", NP, M);
-        attr_rc = configured(once_plain, fe::div3d_mfma_kernel<NP, M, 0>, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU);
-    }
+    const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, 8 / G::WAVES};
+    char what[64], tail_what[64];
+    // (recorded: the static walk's stores are never write-through)
+    auto args = [&](const Launch&) { return call(opT & ~fe::kOpStoresWriteThrough, 0, J, D, nullptr, P, nb, E, nTiles, opT, 0); };
+    auto tail_args = [&](const Launch& L) { return call(opT, 0, J, D, P, nb, E, nTiles, opT, L.tail, L.t_static[0]); };
 #ifdef FE_EXPERIMENTS
-    static PerDeviceOnce once_exp;
-    once_exp.run([] {
-        if (NP == 35) {
-            configure_kernel(fe::div3d_mfma_kernel<NP, M, 1>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::div3d_mfma_kernel<NP, M, 2>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::div3d_mfma_kernel<NP, M, 3>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::div3d_mfma_kernel<NP, M, 8>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::div3d_mfma_kernel<NP, M, 32>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::div3d_mfma_kernel<NP, M, 64>, "experiment", G::LDS_BYTES, 256, 1);
-            configure_kernel(fe::div3d_mfma_kernel<NP, M, 128>, "experiment", G::LDS_BYTES + fe::kDbgTileLdsBytes, 256, 1);
-        }
-        return FE_OK;
-    });
-#endif
-    if (attr_rc != FE_OK) return attr_rc;
-    const dim3 g(persistent_grid(nTiles, G::WAVES)), b(256);
+    const Geometry dbg_geo = {G::WAVES, 256, G::LDS_BYTES, 1, 8 / G::WAVES},
+                   stamps_geo = {G::WAVES, 256, G::LDS_BYTES + fe::kDbgTileLdsBytes, 1, 8 / G::WAVES};
 #define FE_DIV_CASE(DBG) \
-    hipLaunchKernelGGL((fe::div3d_mfma_kernel<NP, M, DBG>), g, b, G::LDS_BYTES, s, J, D, nullptr, P, nb, E, nTiles, opT, 0)
+    case DBG: return mfma_launch<fe::div3d_mfma_kernel<NP, M, DBG>>(s, walk_static(nTiles), dbg_geo, "experiment", args);
     switch (NP == 35 ? dbg : 0) {
-#ifdef FE_EXPERIMENTS
-        case 1: FE_DIV_CASE(1); break;
-        case 2: FE_DIV_CASE(2); break;
-        case 3: FE_DIV_CASE(3); break;
-        case 8: FE_DIV_CASE(8); break;
-        case 32: FE_DIV_CASE(32); break;   // one u plane loaded instead of three (timing only)
-        case 64: FE_DIV_CASE(64); break;   // the tile after next touched line by line (L2 prefetch)
-        case 128:                          // per-wave, per-tile time stamps (fe_dbg_tile); FE_DIV_ILV=1: of the interleaved kernel
+        FE_DIV_CASE(1)
+        FE_DIV_CASE(2)
+        FE_DIV_CASE(3)
+        FE_DIV_CASE(8)
+        FE_DIV_CASE(32)   // one u plane loaded instead of three (timing only)
+        FE_DIV_CASE(64)   // the tile after next touched line by line (L2 prefetch)
+        case 128:         // per-wave, per-tile time stamps (fe_dbg_tile); FE_DIV_ILV=1: of the interleaved kernel
             if constexpr (NP == 35 && M == 1) {
-                if (getenv("FE_DIV_ILV")) {
-                    static PerDeviceOnce once_ilv_dbg;
-                    once_ilv_dbg.run([] { return configure_kernel(fe::div3d_mfma_ilv_kernel<NP, 128>, "experiment", G::LDS_BYTES + fe::kDbgTileLdsBytes, 256, 1); });
-                    hipLaunchKernelGGL((fe::div3d_mfma_ilv_kernel<NP, 128>), g, b, G::LDS_BYTES + fe::kDbgTileLdsBytes, s, J, D, P, nb, E, nTiles, opT);
-                    break;
-                }
+                if (getenv("FE_DIV_ILV"))
+                    return mfma_launch<fe::div3d_mfma_ilv_kernel<NP, 128>>(
+                        s, walk_static(nTiles), stamps_geo, "experiment",
+                        [&](const Launch&) { return call(opT, 0, J, D, P, nb, E, nTiles, opT); });
             }
-            hipLaunchKernelGGL((fe::div3d_mfma_kernel<NP, M, 128>), g, b, G::LDS_BYTES + fe::kDbgTileLdsBytes, s, J, D, nullptr, P, nb, E, nTiles, opT, 0);
-            break;
-#endif
-        default:
-            if (prep) {
-                hipLaunchKernelGGL((fe::div3d_mfma_kernel<NP, M, 0, 0, 3, false, false, true>), g, b, G::LDS_BYTES, s, J, D,
-                                   prep, P, nb, E, nTiles, opT, 0);
-                break;
-            }
-            if constexpr (NP == 35 && M == 1) {
-                if (!(opT & fe::kDivWalkSplit) && nTiles <= g_div_interleave_tiles.load(std::memory_order_relaxed) &&
-                    tail_static_tiles(nTiles, g.x, G::WAVES) == nTiles) {   // a short launch (static walk): the interleaved form
-                    static PerDeviceOnce once_ilv;
-                    if (int rc = configured(once_ilv, fe::div3d_mfma_ilv_kernel<NP>, "div Np=35, B build interleaved", G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
-                    const int64_t waves = (int64_t)g.x * G::WAVES, ragged = nTiles % waves;   // (the kernel's own rule: fe_div.h)
-                    const int qflag = (nb == 1 && ragged > 0 && 8 * ragged <= waves && g_div_quarter_tail.load(std::memory_order_relaxed)) ? fe::kOpQuarterTail : 0;
-                    hipLaunchKernelGGL((fe::div3d_mfma_ilv_kernel<NP>), g, b, G::LDS_BYTES, s, J, D, P, nb, E, nTiles, opT | qflag);
-                    note_launch(false, opT & ~fe::kOpStoresWriteThrough, g.x, G::WAVES, nTiles, nTiles, 4 | (qflag ? 8 : 0));
-                    break;
-                }
-            }
-            {
-                if (!(opT & fe::kDivWalkSplit)) {   // behind two static rounds the tiles come by tickets (fe_common.h); any number of fields
-                    const int64_t t_static = tail_static_tiles(nTiles, g.x, G::WAVES);
-                    unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-                    if (tail) {
-                        static PerDeviceOnce once_tail;
-                        if constexpr (NP == 35 && M == 1) {
-                            if (nb == 1 && nTiles <= g_div_interleave_tiles.load(std::memory_order_relaxed)) {   // the interleaved form, dynamic walk
-                                static PerDeviceOnce once_tail_ilv;
-                                if (int rc = configured(once_tail_ilv, fe::div3d_mfma_tail_kernel<NP, M, false, true>, "div Np=35, B build interleaved, dynamic walk",
-                                                        G::LDS_BYTES, 256, G::BLOCKS_PER_CU))
-                                    return rc;
-                                hipLaunchKernelGGL((fe::div3d_mfma_tail_kernel<NP, M, false, true>), g, b, G::LDS_BYTES, s, J, D, P, nb, E, nTiles, opT, tail, t_static);
-                                note_launch(true, opT, g.x, G::WAVES, nTiles, t_static, 4);
-                                break;
-                            }
-                        }
-                        if (nb == 1) {
-                            snprintf(what, sizeof(what), "div Np=%d M=%d, dynamic walk", NP, M);
-                            if (int rc = configured(once_tail, fe::div3d_mfma_tail_kernel<NP, M>, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
-                            hipLaunchKernelGGL((fe::div3d_mfma_tail_kernel<NP, M>), g, b, G::LDS_BYTES, s, J, D, P, nb, E, nTiles, opT, tail, t_static);
-                            note_launch(true, opT, g.x, G::WAVES, nTiles, t_static);
-                            break;
-                        }
-                        {   // b fields
-                            static PerDeviceOnce once_tail_b;
-                            snprintf(what, sizeof(what), "div Np=%d M=%d x b, dynamic walk", NP, M);
-                            if (int rc = configured(once_tail_b, fe::div3d_mfma_tail_kernel<NP, M, true>, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU))
-                                return rc;
-                            hipLaunchKernelGGL((fe::div3d_mfma_tail_kernel<NP, M, true>), g, b, G::LDS_BYTES, s, J, D, P, nb, E, nTiles, opT, tail,
-                                               t_static);
-                            note_launch(true, opT, g.x, G::WAVES, nTiles, t_static);
-                            break;
-                        }
-                    }
-                }
-            }
-            FE_DIV_CASE(0);
-            note_launch(false, opT & ~fe::kOpStoresWriteThrough, g.x, G::WAVES, nTiles, nTiles);
-            break;
+            return mfma_launch<fe::div3d_mfma_kernel<NP, M, 128>>(s, walk_static(nTiles), stamps_geo, "experiment", args);
+        default: break;
     }
 #undef FE_DIV_CASE
-    return FE_OK;
+#else
+    (void)dbg;
+#endif
+    if (prep) {
+        snprintf(what, sizeof(what), "div Np=%d M=%d, prepared operator", NP, M);
+        return mfma_launch<fe::div3d_mfma_kernel<NP, M, 0, 0, 3, false, false, true>>(
+            s, walk_static(nTiles), geo, what,
+            [&](const Launch&) { return call(opT & ~fe::kOpStoresWriteThrough, 0, J, D, prep, P, nb, E, nTiles, opT, 0); });
+    }
+    snprintf(what, sizeof(what), "div Np=%d M=%d", NP, M);
+    // behind two static rounds the tiles come by tickets (fe_common.h); any number of fields -- not under the split walk
+    const bool tickets = !(opT & fe::kDivWalkSplit);
+    if constexpr (NP == 35 && M == 1) {
+        const bool ilv = nTiles <= g_div_interleave_tiles.load(std::memory_order_relaxed);
+        if (tickets && ilv && tail_static_tiles(nTiles, persistent_grid(nTiles, G::WAVES), G::WAVES) == nTiles) {
+            // a short launch (static walk): the interleaved form, the ragged last round of one field as quarter tiles
+            if (int rc = configured<fe::div3d_mfma_kernel<NP, M, 0>>(what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
+            return mfma_launch<fe::div3d_mfma_ilv_kernel<NP>>(s, walk_static(nTiles), geo, "div Np=35, B build interleaved",
+                                                              [&](const Launch& L) {
+                const int64_t ragged = nTiles % L.waves();   // (the kernel's own rule: fe_div.h)
+                const int q = (nb == 1 && ragged > 0 && 8 * ragged <= L.waves() && g_div_quarter_tail.load(std::memory_order_relaxed))
+                                  ? fe::kOpQuarterTail : 0;
+                return call(opT & ~fe::kOpStoresWriteThrough, 4 | (q ? 8 : 0), J, D, P, nb, E, nTiles, opT | q);
+            });
+        }
+        if (nb == 1 && ilv)   // the interleaved form, dynamic walk
+            return mfma_launch<fe::div3d_mfma_kernel<NP, M, 0>, fe::div3d_mfma_tail_kernel<NP, M, false, true>>(
+                s, walk_tickets(nTiles, tickets), geo, what, args, "div Np=35, B build interleaved, dynamic walk",
+                [&](const Launch& L) { return call(opT, 4, J, D, P, nb, E, nTiles, opT, L.tail, L.t_static[0]); });
+    }
+    if (nb == 1) {
+        snprintf(tail_what, sizeof(tail_what), "div Np=%d M=%d, dynamic walk", NP, M);
+        return mfma_launch<fe::div3d_mfma_kernel<NP, M, 0>, fe::div3d_mfma_tail_kernel<NP, M>>(
+            s, walk_tickets(nTiles, tickets), geo, what, args, tail_what, tail_args);
+    }
+    snprintf(tail_what, sizeof(tail_what), "div Np=%d M=%d x b, dynamic walk", NP, M);
+    return mfma_launch<fe::div3d_mfma_kernel<NP, M, 0>, fe::div3d_mfma_tail_kernel<NP, M, true>>(
+        s, walk_tickets(nTiles, tickets), geo, what, args, tail_what, tail_args);
 }
 
 template <int NP, int M, bool ALDS = false>
@@ -909,22 +832,15 @@ int launch_divcomp(const double* J, const double* D, const double* u, double* ou
     const int64_t nTiles = E / G::TEL;
     *e_done = nTiles > 0 ? E : 0;   // the launch covers the elements behind the last tile too (remainder_items)
     if (nTiles == 0) return FE_OK;
-    static PerDeviceOnce once;
-    const int attr_rc =
-        once.run([] {
-            char what[64];
-            snprintf(what, sizeof(what), "div component Np=%d M=%d", NP, M);
-            return configure_kernel(fe::div3d_mfma_kernel<NP, M, 0, 1, 3, ALDS>, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU);
-        });
-    if (attr_rc != FE_OK) return attr_rc;
     fe::FieldPtrs P = {};
     P.v[0] = u;
     P.out[0] = out;
-    unsigned grid = persistent_grid(nTiles, G::WAVES);
-    if (G::BLOCKS_PER_CU == 1 && grid > (unsigned)device_cu_count()) grid = (unsigned)device_cu_count();
-    hipLaunchKernelGGL((fe::div3d_mfma_kernel<NP, M, 0, 1, 3, ALDS>), dim3(grid), dim3(256), G::LDS_BYTES, s, J, D,
-                       nullptr, P, 1, E, nTiles, opT, jes);
-    return FE_OK;
+    char what[64];
+    snprintf(what, sizeof(what), "div component Np=%d M=%d", NP, M);
+    // (the grid of 8 waves per CU, but no more blocks than are resident)
+    const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU == 1 ? 1 : 8 / G::WAVES};
+    return mfma_launch<fe::div3d_mfma_kernel<NP, M, 0, 1, 3, ALDS>>(
+        s, walk_static(nTiles), geo, what, [&](const Launch&) { return call(opT, 0, J, D, nullptr, P, 1, E, nTiles, opT, jes); });
 }
 
 // 'e,ij,ej->ei' (MODE 2) / 'ij,ej->ei' (MODE 3): the one-component instances of the div template
@@ -935,16 +851,11 @@ int launch_matapply_mode(const double* J, const double* D, const fe::FieldPtrs& 
     const int64_t nTiles = E / G::TEL;
     *e_done = nTiles > 0 ? E : 0;   // the launch covers the elements behind the last tile too (remainder_items)
     if (nTiles == 0) return FE_OK;
-    static PerDeviceOnce once;
-    const int attr_rc = once.run([] {
-        char what[64];
-        snprintf(what, sizeof(what), "matapply Np=%d M=%d mode %d", NP, M, MODE);
-        return configure_kernel(fe::div3d_mfma_kernel<NP, M, 0, MODE>, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU);
-    });
-    if (attr_rc != FE_OK) return attr_rc;
-    hipLaunchKernelGGL((fe::div3d_mfma_kernel<NP, M, 0, MODE>), dim3(persistent_grid(nTiles, G::WAVES)), dim3(256),
-                       G::LDS_BYTES, s, J, D, nullptr, P, nb, E, nTiles, opT, 0);
-    return FE_OK;
+    char what[64];
+    snprintf(what, sizeof(what), "matapply Np=%d M=%d mode %d", NP, M, MODE);
+    return mfma_launch<fe::div3d_mfma_kernel<NP, M, 0, MODE>>(
+        s, walk_static(nTiles), {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, 8 / G::WAVES}, what,
+        [&](const Launch&) { return call(opT, 0, J, D, nullptr, P, nb, E, nTiles, opT, 0); });
 }
 
 template <int NP, int M>
@@ -958,68 +869,34 @@ template <int NP, int NFP, int M, int NB, int NF = fe::kFmNf, bool ALDS = false>
 int launch_fm_nb(const double* J, const double* R, const void* prep, const fe::FieldPtrs& P, int64_t E, int64_t nTiles,
                  int jfe, int rifj, hipStream_t s) {
     constexpr bool W8 = ALDS;   // fragments in LDS: eight waves per block share them, one block per CU
-    constexpr bool kCanPrep = !ALDS && NF == fe::kFmNf;   // prepared operators: tetrahedra p = 1..4
     using G = fe::FmGeom<NP, NFP, M, NF, ALDS, W8>;
     jfe = (jfe ? 1 : 0) | temporal_flag((NF + (int64_t)NB * NF * NFP) * E * 8, kTemporalFloorFaceMass, kTemporalCapFaceMassMib);
-    static PerDeviceOnce once_plain, once_prepared;
-    char what[96];
-    int attr_rc = FE_OK;
-    bool use_prep = false;
-    if constexpr (kCanPrep) use_prep = prep != nullptr;
-    if (use_prep) {
-        if constexpr (kCanPrep) {
-            snprintf(what, sizeof(what), "face-mass Np=%d Nfp=%d M=%d b=%d, prepared operator", NP, NFP, M, NB);
-            attr_rc = configured(once_prepared, fe::facemass_mfma_kernel<NP, NFP, M, NB, NF, false, false, true>, what, G::LDS_BYTES,
-                                 G::THREADS, G::BLOCKS_PER_CU);
-        }
-    } else {
-        snprintf(what, sizeof(what), "face-mass Np=%d Nfp=%d nf=%d M=%d b=%d", NP, NFP, NF, M, NB);
-        attr_rc = configured(once_plain, fe::facemass_mfma_kernel<NP, NFP, M, NB, NF, ALDS, W8>, what, G::LDS_BYTES, G::THREADS,
-                             G::BLOCKS_PER_CU);
-    }
-    if (attr_rc != FE_OK) return attr_rc;
-    int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES;
-    const int64_t cap = (int64_t)G::BLOCKS_PER_CU * device_cu_count();
-    if (blocks > cap) blocks = cap;
-    if constexpr (kCanPrep) {
+    const Geometry geo = {G::WAVES, G::THREADS, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
+    char what[96], tail_what[96];
+    if constexpr (!ALDS && NF == fe::kFmNf) {   // prepared operators: tetrahedra p = 1..4
         if (prep) {
-            hipLaunchKernelGGL((fe::facemass_mfma_kernel<NP, NFP, M, NB, NF, false, false, true>), dim3((unsigned)blocks),
-                               dim3(G::THREADS), G::LDS_BYTES, s, J, R, prep, P, E, nTiles, jfe, rifj);
-            return FE_OK;
+            snprintf(what, sizeof(what), "face-mass Np=%d Nfp=%d M=%d b=%d, prepared operator", NP, NFP, M, NB);
+            return mfma_launch<fe::facemass_mfma_kernel<NP, NFP, M, NB, NF, false, false, true>>(
+                s, walk_static(nTiles), geo, what,
+                [&](const Launch&) { return call(jfe & ~fe::kOpStoresWriteThrough, 0, J, R, prep, P, E, nTiles, jfe, rifj); });
         }
     }
+    snprintf(what, sizeof(what), "face-mass Np=%d Nfp=%d nf=%d M=%d b=%d", NP, NFP, NF, M, NB);
+    auto args = [&](const Launch&) { return call(jfe & ~fe::kOpStoresWriteThrough, 0, J, R, nullptr, P, E, nTiles, jfe, rifj); };
+    auto tail_args = [&](const Launch& L) { return call(jfe, 0, J, R, P, E, nTiles, jfe, rifj, L.tail, L.t_static[0]); };
+    constexpr auto K = fe::facemass_mfma_kernel<NP, NFP, M, NB, NF, ALDS, W8>;
+    // behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk): p = 5 x 4, and tetrahedra p = 1 .. 4 and
+    // triangles with three or more fields
     if constexpr (NP == 56 && NFP == 21 && M == 1 && NF == fe::kFmNf && ALDS && NB == 4) {
-        const int64_t t_static = tail_static_tiles(nTiles, blocks, G::WAVES);
-        unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-        if (tail) {
-            static PerDeviceOnce once_tail;
-            snprintf(what, sizeof(what), "face-mass Np=56 b=%d (A in LDS), dynamic walk", NB);
-            if (int rc = configured(once_tail, fe::facemass_w8_tail_kernel<NP, NFP, NB>, what, G::LDS_BYTES, G::THREADS, G::BLOCKS_PER_CU))
-                return rc;
-            hipLaunchKernelGGL((fe::facemass_w8_tail_kernel<NP, NFP, NB>), dim3((unsigned)blocks), dim3(G::THREADS), G::LDS_BYTES, s, J, R, P,
-                               E, nTiles, jfe, rifj, tail, t_static);
-            return FE_OK;
-        }
+        snprintf(tail_what, sizeof(tail_what), "face-mass Np=56 b=%d (A in LDS), dynamic walk", NB);
+        return mfma_launch<K, fe::facemass_w8_tail_kernel<NP, NFP, NB>>(s, walk_tickets(nTiles), geo, what, args, tail_what, tail_args);
+    } else if constexpr (!ALDS && NB >= 3) {
+        snprintf(tail_what, sizeof(tail_what), "face-mass Np=%d nf=%d M=%d b=%d, dynamic walk", NP, NF, M, NB);
+        return mfma_launch<K, fe::facemass_mfma_tail_kernel<NP, NFP, M, NB, NF>>(
+            s, walk_tickets(nTiles, true, NP == 35 && NF == fe::kFmNf && NB == 4), geo, what, args, tail_what, tail_args);
+    } else {
+        return mfma_launch<K>(s, walk_static(nTiles), geo, what, args);
     }
-    if constexpr (!ALDS && NB >= 3) {   // tetrahedra p = 1 .. 4 and triangles, three or more fields
-        // behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk)
-        const int64_t t_static = tail_static_tiles(nTiles, blocks, G::WAVES, false, NP == 35 && NF == fe::kFmNf && NB == 4);
-        unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-        if (tail) {
-            static PerDeviceOnce once_tail;
-            snprintf(what, sizeof(what), "face-mass Np=%d nf=%d M=%d b=%d, dynamic walk", NP, NF, M, NB);
-            if (int rc = configured(once_tail, fe::facemass_mfma_tail_kernel<NP, NFP, M, NB, NF>, what, G::LDS_BYTES, G::THREADS, G::BLOCKS_PER_CU))
-                return rc;
-            hipLaunchKernelGGL((fe::facemass_mfma_tail_kernel<NP, NFP, M, NB, NF>), dim3((unsigned)blocks), dim3(G::THREADS), G::LDS_BYTES, s,
-                               J, R, P, E, nTiles, jfe, rifj, tail, t_static);
-            note_launch(true, jfe, (unsigned)blocks, G::WAVES, nTiles, t_static);
-            return FE_OK;
-        }
-    }
-    hipLaunchKernelGGL((fe::facemass_mfma_kernel<NP, NFP, M, NB, NF, ALDS, W8>), dim3((unsigned)blocks), dim3(G::THREADS),
-                       G::LDS_BYTES, s, J, R, nullptr, P, E, nTiles, jfe, rifj);
-    note_launch(false, jfe & ~fe::kOpStoresWriteThrough, (unsigned)blocks, G::WAVES, nTiles, nTiles);
-    return FE_OK;
 }
 
 // One MFMA launch for a group of nb fields (2 <= nb <= kMaxGroup of the geometry).
@@ -1129,40 +1006,27 @@ int launch_graddiv(const double* J, const double* D, const void* prep, const fe:
     const int64_t nTilesG = E / GG::TEL, nTilesD = E / GD::TEL;
     *e_done_g = *e_done_d = (nTilesG > 0 || nTilesD > 0) ? E : 0;   // remainders included
     if (nTilesG == 0 && nTilesD == 0) return FE_OK;
-    static PerDeviceOnce once_plain, once_prepared;
-    char what[64];
-    int attr_rc;
     constexpr bool kDyn = NP == 35 && MG == 1 && MD == 1;   // bodies with a dynamic walk (fe_common.h)
-    if (prep) {
-        snprintf(what, sizeof(what), "div + grad Np=%d, prepared operator", NP);
-        attr_rc = configured(once_prepared, fe::graddiv3d_mfma_kernel<NP, MG, MD, true>, what, G::LDS_BYTES, 256, 2);
-    } else {
-        snprintf(what, sizeof(what), "div + grad Np=%d", NP);
-        attr_rc = configured(once_plain, fe::graddiv3d_mfma_kernel<NP, MG, MD, false, kDyn>, what, G::LDS_BYTES, 256, 2);
-    }
-    if (attr_rc != FE_OK) return attr_rc;
-    const int64_t nTiles = nTilesG > nTilesD ? nTilesG : nTilesD;
-    const unsigned grid = persistent_grid(nTiles, 4);
-    fe::FusedTail ft = {nullptr, nTilesD, nTilesG, 0};
-    if (kDyn && !prep) {
-        ft.static_d = tail_static_tiles(nTilesD, grid, 4, true);
-        ft.static_g = tail_static_tiles(nTilesG, grid, 4, true);
-        if (ft.static_d < nTilesD || ft.static_g < nTilesG) ft.tail = tail_slot(s, 2);
-    }
+    const Geometry geo = {4, 256, G::LDS_BYTES, 2, 2};
+    const int loads = temporal_flag((9 + 4 * (int64_t)NP) * E * 8, 0, kTemporalCapGradDivMib);
     // body order (fe_fused.h): with the static walk the younger half of the grid runs grad first; with tickets every block
     // runs div, then grad (profiles/r03/dynamic_walk_fused.txt: 77.9 - 78.1 against 76.9 - 77.6 %)
-    int op_arg = ((ft.tail ? 0 : kFusedOrderGradDiv) << 8) | temporal_flag((9 + 4 * (int64_t)NP) * E * 8, 0, kTemporalCapGradDivMib);
+    auto args = [&](const Launch& L) {
+        int op_arg = ((L.tail ? 0 : kFusedOrderGradDiv) << 8) | loads;
 #ifdef FE_EXPERIMENTS
-    if (const char* o = getenv("FE_FUSED_ORDER")) op_arg = atoi(o) << 8;
+        if (const char* o = getenv("FE_FUSED_ORDER")) op_arg = atoi(o) << 8;
 #endif
-    if (prep)
-        hipLaunchKernelGGL((fe::graddiv3d_mfma_kernel<NP, MG, MD, true>), dim3(grid), dim3(256), G::LDS_BYTES, s, J, D, prep,
-                           Pg, Pd, E, nTilesG, nTilesD, op_arg, ft);
-    else
-        hipLaunchKernelGGL((fe::graddiv3d_mfma_kernel<NP, MG, MD, false, kDyn>), dim3(grid), dim3(256), G::LDS_BYTES, s, J, D, nullptr,
-                           Pg, Pd, E, nTilesG, nTilesD, op_arg, ft);
-    note_launch(ft.tail != nullptr, op_arg & fe::kOpLoadsTemporal, grid, 4, nTilesG + nTilesD, ft.static_d + ft.static_g, 0, 2);
-    return FE_OK;
+        return call(op_arg & fe::kOpLoadsTemporal, 0, J, D, prep, Pg, Pd, E, nTilesG, nTilesD, op_arg,
+                    fe::FusedTail{L.tail, L.t_static[0], L.t_static[1], 0});
+    };
+    char what[64];
+    if (prep) {
+        snprintf(what, sizeof(what), "div + grad Np=%d, prepared operator", NP);
+        return mfma_launch<fe::graddiv3d_mfma_kernel<NP, MG, MD, true>>(s, {{nTilesD, nTilesG, 0}, 2, 0u, false}, geo, what, args);
+    }
+    snprintf(what, sizeof(what), "div + grad Np=%d", NP);
+    constexpr auto K = fe::graddiv3d_mfma_kernel<NP, MG, MD, false, kDyn>;   // (takes the counters itself)
+    return mfma_launch<K, (kDyn ? K : nullptr)>(s, {{nTilesD, nTilesG, 0}, 2, 3u, false}, geo, what, args, what, args);
 }
 
 // div, grad and face-mass x nb (2..4) in one persistent launch (full tiles only)
@@ -1171,42 +1035,26 @@ int launch_waveop_nb(const fe::WaveOpArgs& a, const fe::GradFields& Pg, const fe
                      const fe::FieldPtrs& Pf, hipStream_t s) {
     using G = fe::WaveOpGeom<NP, NFP, MG, MD, MF>;
     constexpr bool kDyn = NP == 35 && NFP == 15 && MG == 1 && MD == 1 && MF == 1;   // bodies with a dynamic walk (fe_common.h)
-    static PerDeviceOnce once_plain, once_prepared;
+    const Geometry geo = {4, 256, G::LDS_BYTES, 2, 2};
+    const int loads = temporal_flag((9 + 4 * (int64_t)NP + 4 + (int64_t)NB * 4 * NFP) * a.E * 8, 0, kTemporalCapFaceMassMib);
+    auto args = [&](const Launch& L) {
+        fe::WaveOpArgs args = a;
+        args.load_flags = loads;
+        if (L.tail) args.order = 0;   // with tickets every block runs div, grad, lift (see launch_graddiv)
+#ifdef FE_EXPERIMENTS
+        if (const char* o = getenv("FE_FUSED_ORDER")) args.order = atoi(o);
+#endif
+        return call(loads & fe::kOpLoadsTemporal, 0, args, Pg, Pd, Pf, fe::FusedTail{L.tail, L.t_static[0], L.t_static[1], L.t_static[2]});
+    };
+    const Walk walk = {{a.nTilesD, a.nTilesG, a.nTilesF}, 3, NB >= 3 ? 7u : 3u, false};   // (the lift of two fields walks statically)
     char what[80];
-    int attr_rc;
     if (a.prepD && a.prepR) {
         snprintf(what, sizeof(what), "div + grad + face-mass Np=%d b=%d, prepared operators", NP, NB);
-        attr_rc = configured(once_prepared, fe::waveop3d_mfma_kernel<NP, NFP, MG, MD, MF, NB, true>, what, G::LDS_BYTES, 256, 2);
-    } else {
-        snprintf(what, sizeof(what), "div + grad + face-mass Np=%d b=%d", NP, NB);
-        attr_rc = configured(once_plain, fe::waveop3d_mfma_kernel<NP, NFP, MG, MD, MF, NB, false, kDyn>, what, G::LDS_BYTES, 256, 2);
+        return mfma_launch<fe::waveop3d_mfma_kernel<NP, NFP, MG, MD, MF, NB, true>>(s, walk, geo, what, args);
     }
-    if (attr_rc != FE_OK) return attr_rc;
-    int64_t nTiles = a.nTilesG > a.nTilesD ? a.nTilesG : a.nTilesD;
-    if (a.nTilesF > nTiles) nTiles = a.nTilesF;
-    const unsigned grid = persistent_grid(nTiles, 4);
-    fe::FusedTail ft = {nullptr, a.nTilesD, a.nTilesG, a.nTilesF};
-    if (kDyn && !(a.prepD && a.prepR)) {
-        ft.static_d = tail_static_tiles(a.nTilesD, grid, 4, true);
-        ft.static_g = tail_static_tiles(a.nTilesG, grid, 4, true);
-        ft.static_f = NB >= 3 ? tail_static_tiles(a.nTilesF, grid, 4, true) : a.nTilesF;
-        if (ft.static_d < a.nTilesD || ft.static_g < a.nTilesG || ft.static_f < a.nTilesF) ft.tail = tail_slot(s, 3);
-    }
-    fe::WaveOpArgs args = a;
-    args.load_flags = temporal_flag((9 + 4 * (int64_t)NP + 4 + (int64_t)NB * 4 * NFP) * a.E * 8, 0, kTemporalCapFaceMassMib);
-    if (ft.tail) args.order = 0;   // with tickets every block runs div, grad, lift (see launch_graddiv)
-#ifdef FE_EXPERIMENTS
-    if (const char* o = getenv("FE_FUSED_ORDER")) args.order = atoi(o);
-#endif
-    if (a.prepD && a.prepR)
-        hipLaunchKernelGGL((fe::waveop3d_mfma_kernel<NP, NFP, MG, MD, MF, NB, true>), dim3(grid), dim3(256), G::LDS_BYTES, s, args, Pg,
-                           Pd, Pf, ft);
-    else
-        hipLaunchKernelGGL((fe::waveop3d_mfma_kernel<NP, NFP, MG, MD, MF, NB, false, kDyn>), dim3(grid), dim3(256), G::LDS_BYTES, s,
-                           args, Pg, Pd, Pf, ft);
-    note_launch(ft.tail != nullptr, args.load_flags & fe::kOpLoadsTemporal, grid, 4, a.nTilesG + a.nTilesD + a.nTilesF,
-                ft.static_d + ft.static_g + ft.static_f, 0, 3);
-    return FE_OK;
+    snprintf(what, sizeof(what), "div + grad + face-mass Np=%d b=%d", NP, NB);
+    constexpr auto K = fe::waveop3d_mfma_kernel<NP, NFP, MG, MD, MF, NB, false, kDyn>;   // (takes the counters itself)
+    return mfma_launch<K, (kDyn ? K : nullptr)>(s, walk, geo, what, args, what, args);
 }
 
 template <int NP, int NFP, int MG, int MD, int MF>
@@ -1237,30 +1085,20 @@ int launch_nd2(const double* J, const double* D, const fe::FieldPtrs& P, int nb,
     const int64_t nTiles = E / G::TEL;
     *launched = nTiles > 0;   // the launch covers the elements behind the last tile too
     if (nTiles == 0) return FE_OK;
-    static PerDeviceOnce once;
-    const int attr_rc = once.run([] {
-        char what[64];
-        snprintf(what, sizeof(what), "triangles %s Np=%d M=%d", MODE == 4 ? "grad" : MODE == 1 ? "div component" : "div", NP, M);
-        return configure_kernel(fe::div3d_mfma_kernel<NP, M, 0, MODE, 2>, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU);
-    });
-    if (attr_rc != FE_OK) return attr_rc;
-    const unsigned grid = persistent_grid(nTiles, G::WAVES);
+    const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, 8 / G::WAVES};
+    const char* kind = MODE == 4 ? "grad" : MODE == 1 ? "div component" : "div";
+    char what[64], tail_what[64];
+    snprintf(what, sizeof(what), "triangles %s Np=%d M=%d", kind, NP, M);
+    auto args = [&](const Launch&) { return call(opT, 0, J, D, nullptr, P, nb, E, nTiles, opT, jes); };
+    constexpr auto K = fe::div3d_mfma_kernel<NP, M, 0, MODE, 2>;
     if constexpr (MODE == 0 || MODE == 4) {   // behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk)
-        const int64_t t_static = tail_static_tiles(nTiles, grid, G::WAVES);
-        unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-        if (tail) {
-            static PerDeviceOnce once_tail;
-            char what[64];
-            snprintf(what, sizeof(what), "triangles %s Np=%d M=%d, dynamic walk", MODE == 4 ? "grad" : "div", NP, M);
-            if (int rc = configured(once_tail, fe::nd2_mfma_tail_kernel<NP, M, MODE>, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
-            hipLaunchKernelGGL((fe::nd2_mfma_tail_kernel<NP, M, MODE>), dim3(grid), dim3(256), G::LDS_BYTES, s, J, D, P, nb, E, nTiles, opT,
-                               tail, t_static);
-            return FE_OK;
-        }
+        snprintf(tail_what, sizeof(tail_what), "triangles %s Np=%d M=%d, dynamic walk", kind, NP, M);
+        return mfma_launch<K, fe::nd2_mfma_tail_kernel<NP, M, MODE>>(
+            s, walk_tickets(nTiles), geo, what, args, tail_what,
+            [&](const Launch& L) { return call(opT, 0, J, D, P, nb, E, nTiles, opT, L.tail, L.t_static[0]); });
+    } else {
+        return mfma_launch<K>(s, walk_static(nTiles), geo, what, args);
     }
-    hipLaunchKernelGGL((fe::div3d_mfma_kernel<NP, M, 0, MODE, 2>), dim3(grid), dim3(256),
-                       G::LDS_BYTES, s, J, D, nullptr, P, nb, E, nTiles, opT, jes);
-    return FE_OK;
 }
 
 template <int MODE>
@@ -1273,6 +1111,58 @@ int launch_nd2_np(const double* J, const double* D, const fe::FieldPtrs& P, int 
         case 6: return launch_nd2<6, 8, MODE>(J, D, P, nb, E, opT, s, launched, jes);
         default: return launch_nd2<3, 8, MODE>(J, D, P, nb, E, opT, s, launched, jes);
     }
+}
+
+// Fields `v[0 .. nb-1]` / `out[...]` of one launch, the unused slots padded with the first field
+fe::FieldPtrs field_group(const double* const* v, double* const* out, int nb) {
+    fe::FieldPtrs P;
+    for (int k = 0; k < fe::kMaxFields; ++k) {
+        P.v[k] = v[k < nb ? k : 0];
+        P.out[k] = out[k < nb ? k : 0];
+    }
+    return P;
+}
+
+// float32 grad and div on the matrix cores (fe_grad_f32.h, fe_div_f32.h): one launch per field, every one on `s` (a dynamic walk
+// uses the stream's counters in turn).  1: too few elements for a wave tile (the caller runs the tiled kernel).
+template <typename G, auto K, auto KT = nullptr>
+int launch_f32_fields(const fe_argpack* a, const double* const* vin, double* const* vout, int b, int flags, const char* what,
+                      hipStream_t s) {
+    const int64_t nTiles = a->E / G::TEL;
+    if (nTiles == 0) return 1;
+    const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
+    const float* J = reinterpret_cast<const float*>(a->J);
+    const float* D = reinterpret_cast<const float*>(a->D);
+    for (int k = 0; k < b; ++k) {
+        const float* u = reinterpret_cast<const float*>(vin[k]);
+        float* out = reinterpret_cast<float*>(vout[k]);
+        if (int rc = mfma_launch<K, KT>(
+                s, walk_tickets(nTiles), geo, what, [&](const Launch&) { return call(flags, 0, J, D, u, out, a->E, nTiles, flags); },
+                what, [&](const Launch& L) { return call(flags, 0, J, D, u, out, a->E, nTiles, flags, L.tail, L.t_static[0]); }))
+            return rc;
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+// float32 face-mass x 4 (fe_facemass_f32.h): groups of up to kMaxFields fields share J and the fragments
+template <typename G, auto K>
+int launch_f32_facemass(const fe_argpack* a, const double* const* vin, double* const* vout, int b, int jl, int rl, const char* what,
+                        hipStream_t s) {
+    const int64_t nTiles = a->E / G::TEL;
+    if (nTiles == 0) return 1;
+    const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
+    const float* J = reinterpret_cast<const float*>(a->J);
+    const float* R = reinterpret_cast<const float*>(a->D);
+    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {
+        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
+        const fe::FieldPtrs P = field_group(vin + k0, vout + k0, nb);
+        if (int rc = mfma_launch<K>(s, walk_static(nTiles), geo, what,
+                                    [&](const Launch&) { return call(0, 0, J, R, P, nb, a->E, nTiles, jl, rl); }))
+            return rc;
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
 }
 
 // ---- prepared operators: what fe_prepare_operator wrote where (host-side record, so that a launcher
@@ -1696,6 +1586,7 @@ int fe_grad3d_batched_f64(const double* J, const double* D, const double* const*
 int fe_grad3d_prepared_f64(const double* J, const double* D, const void* D_prepared, const double* const* u,
                            double* const* out, int64_t E, int32_t Np, int32_t b, int32_t op_flags,
                            int32_t variant, void* stream) {
+    forget_last_launch();
     if (!u || !out) return fail(FE_EINVAL, "grad: null pointer table");
     if (b < 1) return fail(FE_EINVAL, "grad: b=%d, need at least one field", b);
     if (b > FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch
@@ -1725,6 +1616,7 @@ int fe_grad3d_prepared_f64(const double* J, const double* D, const void* D_prepa
 int fe_gradplanes3d_f64(const double* const* J3, const double* D, const double* const* u,
                         double* const* out, int64_t E, int32_t Np, int32_t b, int32_t op_flags,
                         int32_t variant, void* stream) {
+    forget_last_launch();
     if (!J3 || !u || !out) return fail(FE_EINVAL, "grad planes: null pointer table");
     if (b < 1) return fail(FE_EINVAL, "grad planes: b=%d, need at least one field", b);
     if (b > FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch
@@ -1807,6 +1699,7 @@ int fe_div3d_batched_f64(const double* J, const double* D, const double* const* 
 int fe_div3d_prepared_f64(const double* J, const double* D, const void* D_prepared, const double* const* u,
                           double* const* out, int64_t E, int32_t Np, int32_t b, int32_t op_flags,
                           int32_t variant, void* stream) {
+    forget_last_launch();
     if (!u || !out) return fail(FE_EINVAL, "div: null pointer table");
     if (b < 1) return fail(FE_EINVAL, "div: b=%d, need at least one field", b);
     if (b > FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch
@@ -1917,18 +1810,21 @@ static int nd_launch(int family, const char* what, const double* J, const double
 
 int fe_grad_f64(const double* J, const double* D, const double* const* u, double* const* out, int64_t E,
                 int32_t ndim, int32_t Np, int32_t b, int32_t op_flags, int32_t variant, void* stream) {
+    forget_last_launch();
     if (ndim == 3) return fe_grad3d_batched_f64(J, D, u, out, E, Np, b, op_flags, variant, stream);
     return nd_launch(FE_FAMILY_GRAD, "grad", J, D, u, out, E, ndim, Np, b, op_flags, variant, stream);
 }
 
 int fe_div_f64(const double* J, const double* D, const double* const* u, double* const* out, int64_t E,
                int32_t ndim, int32_t Np, int32_t b, int32_t op_flags, int32_t variant, void* stream) {
+    forget_last_launch();
     if (ndim == 3) return fe_div3d_batched_f64(J, D, u, out, E, Np, b, op_flags, variant, stream);
     return nd_launch(FE_FAMILY_DIV, "div", J, D, u, out, E, ndim, Np, b, op_flags, variant, stream);
 }
 
 int fe_divcomp_f64(const double* J, const double* D, const double* u, double* out, int64_t E, int32_t ndim,
                    int32_t Np, int32_t op_flags, int32_t variant, void* stream) {
+    forget_last_launch();
     if (ndim == 3) return fe_divcomp3d_f64(J, D, u, out, E, Np, op_flags, variant, stream);
     if (ndim != 2) return fail(FE_EUNSUPPORTED, "div component: ndim must be 2 or 3 (got %d)", ndim);
     if (int rc = check_common(J, D, u, out, E, Np)) return rc;
@@ -1959,6 +1855,7 @@ int fe_divcomp_f64(const double* J, const double* D, const double* u, double* ou
 
 int fe_divcomp3d_f64(const double* J, const double* D, const double* u, double* out, int64_t E,
                      int32_t Np, int32_t op_flags, int32_t variant, void* stream) {
+    forget_last_launch();
     if (int rc = check_common(J, D, u, out, E, Np)) return rc;
     if (op_flags & ~(FE_OP_TRANSPOSED | FE_OP_J_ES))
         return fail(FE_EINVAL, "div component: bad operator flags %d", op_flags);
@@ -1996,6 +1893,7 @@ int fe_divcomp3d_f64(const double* J, const double* D, const double* u, double* 
 
 int fe_matapply_f64(const double* J, const double* D, const double* const* u, double* const* out, int64_t E,
                     int32_t Np, int32_t b, int32_t op_flags, int32_t variant, void* stream) {
+    forget_last_launch();
     if (!u || !out) return fail(FE_EINVAL, "matapply: null pointer table");
     if (b < 1) return fail(FE_EINVAL, "matapply: b=%d, need at least one field", b);
     if (b > FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch
@@ -2052,6 +1950,7 @@ int fe_graddiv3d_f64(const double* J, const double* D, const double* u_grad, con
 int fe_graddiv3d_prepared_f64(const double* J, const double* D, const void* D_prepared, const double* u_grad,
                               const double* v_div, double* grad_out, double* div_out, int64_t E, int32_t Np,
                               int32_t variant, void* stream) {
+    forget_last_launch();
     int perr;
     const void* prep = usable_prepared(D_prepared, D, kPreparedD, Np, 0, 0, 0, "graddiv", &perr);
     if (perr != FE_OK) return perr;
@@ -2098,6 +1997,7 @@ int fe_facemass_f64(const double* J, const double* R, const double* const* v, do
 int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_prepared, const double* const* v,
                              double* const* out, int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
                              int32_t layout_flags, int32_t variant, void* stream) {
+    forget_last_launch();
     int perr;   // (the J layout flag is not part of the operator)
     const void* prep = usable_prepared(R_prepared, R, kPreparedR, Np, nf, Nfp, layout_flags & ~FE_FM_J_FE, "face-mass", &perr);
     if (perr != FE_OK) return perr;
@@ -2159,11 +2059,7 @@ int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_pre
     for (int k0 = 0; k0 < b;) {
         int nb = (b - k0 < max_group) ? b - k0 : max_group;
         if (use_mfma && b - k0 - nb == 1) nb -= 1;
-        fe::FieldPtrs P;
-        for (int k = 0; k < fe::kMaxFields; ++k) {
-            P.v[k] = v[k0 + (k < nb ? k : 0)];
-            P.out[k] = out[k0 + (k < nb ? k : 0)];
-        }
+        const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
         if (nTiles > 0) {
             int rc = FE_OK;
             if (nf == 3) {
@@ -2217,6 +2113,7 @@ int fe_waveop3d_prepared_f64(const double* J, const double* D, const void* D_pre
                              const double* R, const void* R_prepared, const double* const* f, double* const* lift,
                              int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t fm_layout_flags,
                              int32_t variant, void* stream) {
+    forget_last_launch();
     int perr;
     const void* prepD = usable_prepared(D_prepared, D, kPreparedD, Np, 0, 0, 0, "waveop", &perr);
     if (perr != FE_OK) return perr;
@@ -2244,12 +2141,9 @@ int fe_waveop3d_prepared_f64(const double* J, const double* D, const void* D_pre
     if (bits & 7u) return fail(FE_EINVAL, "waveop: device pointers must be 8-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const fe::GradFields Pg = grad_fields(J, &u_grad, &grad_out, 1, E, Np);
-    fe::FieldPtrs Pd = {}, Pf = {};
+    fe::FieldPtrs Pd = {};
     Pd.v[0] = v_div;  Pd.out[0] = div_out;
-    for (int k = 0; k < fe::kMaxFields; ++k) {
-        Pf.v[k] = f[k < b ? k : 0];
-        Pf.out[k] = lift[k < b ? k : 0];
-    }
+    const fe::FieldPtrs Pf = field_group(f, lift, b);
     fe::WaveOpArgs a = {};
     a.J = J; a.D = D; a.Jf = Jface; a.R = R; a.E = E;
     a.prepD = prepD; a.prepR = prepR;
@@ -2843,6 +2737,7 @@ int fe_tail_check(int32_t repair, int64_t* dirty_words, int32_t* groups, int32_t
 }
 
 int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
+    forget_last_launch();
     if (!a) return fail(FE_EINVAL, "fe_launch_f32: null argument pack");
     if (a->E < 0 || a->Np <= 0) return fail(FE_EINVAL, "fe_launch_f32: bad sizes (E=%lld Np=%d)", (long long)a->E, a->Np);
     if (a->E == 0) return FE_OK;
@@ -2896,171 +2791,66 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
         bool aligned = ((reinterpret_cast<uintptr_t>(a->J) | reinterpret_cast<uintptr_t>(a->D)) & 15u) == 0;
         for (int k = 0; k < b; ++k)
             aligned = aligned && vin[k] && vout[k] && ((reinterpret_cast<uintptr_t>(vin[k]) | reinterpret_cast<uintptr_t>(vout[k])) & 15u) == 0;
-        if (aligned && div_lower) {   // fe_div_f32.h: the kernel over the geometry (Np, M)
-            auto go_np = [&](auto geom, auto kernel, const char* what, PerDeviceOnce& once) -> int {
-                using G = decltype(geom);
-                const int64_t nTiles = a->E / G::TEL;
-                if (nTiles == 0) return 1;   // too few elements for a wave tile: the tiled kernel
-                if (int rc = configured(once, kernel, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
-                int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES;
-                const int64_t cap = (int64_t)G::BLOCKS_PER_CU * device_cu_count();
-                if (blocks > cap) blocks = cap;
-                for (int k = 0; k < b; ++k)
-                    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), G::LDS_BYTES, s, reinterpret_cast<const float*>(a->J),
-                                       reinterpret_cast<const float*>(a->D), reinterpret_cast<const float*>(vin[k]),
-                                       reinterpret_cast<float*>(vout[k]), a->E, nTiles, opT);
-                FE_HIP_CHECK(hipGetLastError());
-                return FE_OK;
-            };
-            static PerDeviceOnce once20, once10, once4;
-            const int rc = a->Np == 20 ? go_np(fe::DivF32GeomT<20, 1>{}, fe::div3d_mfma_f32_np_kernel<20, 1>, "div float32 Np=20 M=1", once20)
-                           : a->Np == 10 ? go_np(fe::DivF32GeomT<10, 3>{}, fe::div3d_mfma_f32_np_kernel<10, 3>, "div float32 Np=10 M=3", once10)
-                                         : go_np(fe::DivF32GeomT<4, 5>{}, fe::div3d_mfma_f32_np_kernel<4, 5>, "div float32 Np=4 M=5", once4);
-            if (rc <= 0) return rc;
-        } else if (aligned && family == FE_FAMILY_DIV) {
+        int rc = 1;   // 1: no MFMA launch (unaligned, or too few elements for a wave tile): the tiled kernel below
+        if (!aligned) {
+        } else if (div_lower) {   // fe_div_f32.h: the kernel over the geometry (Np, M)
+            rc = a->Np == 20 ? launch_f32_fields<fe::DivF32GeomT<20, 1>, fe::div3d_mfma_f32_np_kernel<20, 1>>(a, vin, vout, b, opT, "div float32 Np=20 M=1", s)
+                 : a->Np == 10 ? launch_f32_fields<fe::DivF32GeomT<10, 3>, fe::div3d_mfma_f32_np_kernel<10, 3>>(a, vin, vout, b, opT, "div float32 Np=10 M=3", s)
+                               : launch_f32_fields<fe::DivF32GeomT<4, 5>, fe::div3d_mfma_f32_np_kernel<4, 5>>(a, vin, vout, b, opT, "div float32 Np=4 M=5", s);
+        } else if (family == FE_FAMILY_DIV) {
             // the measured alternatives (profiles/r03/float32_div_facemass.txt) stay selectable in the experiment build
 #ifdef FE_EXPERIMENTS
             static const int ring = [] { const char* e = getenv("FEINSUM_F32_DIV_RING"); return e && atoi(e) == 1 ? 1 : 2; }();
             static const int small = [] { const char* e = getenv("FEINSUM_F32_SMALL"); return e ? atoi(e) : 1; }();
-#else
-            constexpr int ring = 2, small = 1;
-#endif
-            const int64_t nTiles = a->E / 16;
-            auto go = [&](auto geom, auto kernel, const char* what, PerDeviceOnce& once) -> int {
-                using G = decltype(geom);
-                if (int rc = configured(once, kernel, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
-                int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES;
-                const int64_t cap = (int64_t)G::BLOCKS_PER_CU * device_cu_count();
-                if (blocks > cap) blocks = cap;
-                for (int k = 0; k < b; ++k)
-                    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), G::LDS_BYTES, s, reinterpret_cast<const float*>(a->J),
-                                       reinterpret_cast<const float*>(a->D), reinterpret_cast<const float*>(vin[k]),
-                                       reinterpret_cast<float*>(vout[k]), a->E, nTiles, opT);
-                FE_HIP_CHECK(hipGetLastError());
-                return FE_OK;
-            };
-            static PerDeviceOnce once2;
-#ifdef FE_EXPERIMENTS
-            static PerDeviceOnce once1, once3;
             static const int f32dbg = [] { const char* e = getenv("FEINSUM_F32_DBG"); return e ? atoi(e) : 0; }();   // parts of the tile work removed
-            static PerDeviceOnce onced[16];
-#define FE_F32DBG_CASE(D) case D: return go(fe::DivF32Geom<2>{}, fe::div3d_mfma_f32_kernel<2, true, D>, "div float32 experiment", onced[D]);
+#define FE_F32DBG_CASE(D) \
+    case D: rc = launch_f32_fields<fe::DivF32Geom<2>, fe::div3d_mfma_f32_kernel<2, true, D>>(a, vin, vout, b, opT, "div float32 experiment", s); break;
             switch (f32dbg) {
                 FE_F32DBG_CASE(1) FE_F32DBG_CASE(2) FE_F32DBG_CASE(3) FE_F32DBG_CASE(4) FE_F32DBG_CASE(5) FE_F32DBG_CASE(6) FE_F32DBG_CASE(7)
                 FE_F32DBG_CASE(8) FE_F32DBG_CASE(9) FE_F32DBG_CASE(12) FE_F32DBG_CASE(15)
-                default: break;
+                default:
+                    if (ring == 1)
+                        rc = launch_f32_fields<fe::DivF32Geom<1>, fe::div3d_mfma_f32_kernel<1, false>>(a, vin, vout, b, opT, "div float32 Np=35 one buffer", s);
+                    else if (!small)
+                        rc = launch_f32_fields<fe::DivF32Geom<2>, fe::div3d_mfma_f32_kernel<2, false>>(a, vin, vout, b, opT, "div float32 Np=35 three row tiles", s);
+                    else
+                        rc = launch_f32_fields<fe::DivF32Geom<2>, fe::div3d_mfma_f32_kernel<2, true>>(a, vin, vout, b, opT, "div float32 Np=35", s);
             }
 #undef FE_F32DBG_CASE
-            if (ring == 1) return go(fe::DivF32Geom<1>{}, fe::div3d_mfma_f32_kernel<1, false>, "div float32 Np=35 one buffer", once1);
-            if (!small) return go(fe::DivF32Geom<2>{}, fe::div3d_mfma_f32_kernel<2, false>, "div float32 Np=35 three row tiles", once3);
+#else
+            rc = launch_f32_fields<fe::DivF32Geom<2>, fe::div3d_mfma_f32_kernel<2, true>>(a, vin, vout, b, opT, "div float32 Np=35", s);
 #endif
-            return go(fe::DivF32Geom<2>{}, fe::div3d_mfma_f32_kernel<2, true>, "div float32 Np=35", once2);
-        }
-        if (aligned && fm_lower) {   // fe_facemass_f32.h: the kernel over the geometry (Np, Nfp, M)
-            auto go_np = [&](auto geom, auto kernel, const char* what, PerDeviceOnce& once) -> int {
-                using G = decltype(geom);
-                const int64_t nTiles = a->E / G::TEL;
-                if (nTiles == 0) return 1;   // too few elements for a wave tile: the tiled kernel
-                if (int rc = configured(once, kernel, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
-                int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES;
-                const int64_t cap = (int64_t)G::BLOCKS_PER_CU * device_cu_count();
-                if (blocks > cap) blocks = cap;
-                for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // groups of up to kMaxFields fields share J and the fragments
-                    const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
-                    fe::FieldPtrs P;
-                    for (int k = 0; k < fe::kMaxFields; ++k) {
-                        P.v[k] = vin[k0 + (k < nb ? k : 0)];
-                        P.out[k] = vout[k0 + (k < nb ? k : 0)];
-                    }
-                    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), G::LDS_BYTES, s, reinterpret_cast<const float*>(a->J),
-                                       reinterpret_cast<const float*>(a->D), P, nb, a->E, nTiles, jl, rl);
-                }
-                FE_HIP_CHECK(hipGetLastError());
-                return FE_OK;
-            };
-            static PerDeviceOnce once20, once10, once4;
-            const int rc = a->Np == 20 ? go_np(fe::FmF32GeomT<20, 10, 1>{}, fe::facemass_mfma_f32_np_kernel<20, 10, 1>, "face-mass float32 Np=20 M=1", once20)
-                           : a->Np == 10 ? go_np(fe::FmF32GeomT<10, 6, 2>{}, fe::facemass_mfma_f32_np_kernel<10, 6, 2>, "face-mass float32 Np=10 M=2", once10)
-                                         : go_np(fe::FmF32GeomT<4, 3, 4>{}, fe::facemass_mfma_f32_np_kernel<4, 3, 4>, "face-mass float32 Np=4 M=4", once4);
-            if (rc <= 0) return rc;
-        } else if (aligned && family == FE_FAMILY_FACEMASS) {
-            using G = fe::FmF32Geom;
-            static PerDeviceOnce once;
-            auto kernel = fe::facemass_mfma_f32_kernel<true>;
-            const char* what = "face-mass float32 Np=35";
-            PerDeviceOnce* flag = &once;
+        } else if (fm_lower) {   // fe_facemass_f32.h: the kernel over the geometry (Np, Nfp, M)
+            rc = a->Np == 20 ? launch_f32_facemass<fe::FmF32GeomT<20, 10, 1>, fe::facemass_mfma_f32_np_kernel<20, 10, 1>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=20 M=1", s)
+                 : a->Np == 10 ? launch_f32_facemass<fe::FmF32GeomT<10, 6, 2>, fe::facemass_mfma_f32_np_kernel<10, 6, 2>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=10 M=2", s)
+                               : launch_f32_facemass<fe::FmF32GeomT<4, 3, 4>, fe::facemass_mfma_f32_np_kernel<4, 3, 4>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=4 M=4", s);
+        } else if (family == FE_FAMILY_FACEMASS) {
 #ifdef FE_EXPERIMENTS
             static const int small = [] { const char* e = getenv("FEINSUM_F32_SMALL"); return e ? atoi(e) : 1; }();
-            static PerDeviceOnce once3;
-            if (!small) { kernel = fe::facemass_mfma_f32_kernel<false>; what = "face-mass float32 Np=35 three row tiles"; flag = &once3; }
+            if (!small)
+                rc = launch_f32_facemass<fe::FmF32Geom, fe::facemass_mfma_f32_kernel<false>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=35 three row tiles", s);
+            else
 #endif
-            if (int rc = configured(*flag, kernel, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
-            const int64_t nTiles = a->E / G::TEL;
-            int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES;
-            const int64_t cap = (int64_t)G::BLOCKS_PER_CU * device_cu_count();
-            if (blocks > cap) blocks = cap;
-            for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // groups of up to kMaxFields fields share J and the fragments
-                const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
-                fe::FieldPtrs P;
-                for (int k = 0; k < fe::kMaxFields; ++k) {
-                    P.v[k] = vin[k0 + (k < nb ? k : 0)];
-                    P.out[k] = vout[k0 + (k < nb ? k : 0)];
-                }
-                hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), G::LDS_BYTES, s, reinterpret_cast<const float*>(a->J),
-                                   reinterpret_cast<const float*>(a->D), P, nb, a->E, nTiles, jl, rl);
-            }
-            FE_HIP_CHECK(hipGetLastError());
-            return FE_OK;
-        }
-        if (aligned) {
+                rc = launch_f32_facemass<fe::FmF32Geom, fe::facemass_mfma_f32_kernel<true>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=35", s);
+        } else {
             // two 16-element sub-tiles per wave iteration from E = 2e5 on (round 4: 4.5 KB store bursts, two blocks per CU: 68.1 ->
             // 70.5 % of the float32 roofline at 1e6, 70.2 -> 75.5 % at 4e6; below 2e5 the three-blocks-per-CU kernel of one sub-tile
             // is faster: 15.3 against 17.7 us at 1e5; FEINSUM_F32_M=1 / 2 forces either; profiles/r04/float32_grad_two_subtiles.txt)
             static const int m_env = [] { const char* e = getenv("FEINSUM_F32_M"); return e ? atoi(e) : 0; }();
             const bool m1 = m_env == 1 || (m_env != 2 && a->E < 200000);
-            // `tail_kernel`: the same kernel with a dynamic tail (behind two static rounds the tiles come by tickets; from five rounds
-            // on, as for float64) or nullptr; every launch of the loop runs on `s`, so they use the stream's counters in turn
-            auto launch = [&](auto geom, auto kernel, auto tail_kernel, const char* what) -> int {
-                using G = decltype(geom);
-                static PerDeviceOnce once, once_tail;
-                if (int rc = configured(once, kernel, what, G::LDS_BYTES, 256, G::BLOCKS_PER_CU)) return rc;
-                const int64_t nTiles = a->E / G::TEL;
-                if (nTiles == 0) return 1;   // too few elements for a wave tile: the tiled kernel
-                int64_t blocks = (nTiles + G::WAVES - 1) / G::WAVES;
-                const int64_t cap = (int64_t)G::BLOCKS_PER_CU * device_cu_count();
-                if (blocks > cap) blocks = cap;
-                const int flags = opT | temporal_flag((9 + (int64_t)a->Np) * a->E * 4);
-                int64_t t_static = nTiles;
-                if constexpr (!std::is_same_v<decltype(tail_kernel), std::nullptr_t>) {
-                    t_static = tail_static_tiles(nTiles, blocks, G::WAVES);
-                    if (t_static < nTiles)
-                        if (int rc = configured(once_tail, tail_kernel, what, G::LDS_BYTES, 256, 2)) return rc;
-                }
-                for (int k = 0; k < b; ++k) {
-                    if constexpr (!std::is_same_v<decltype(tail_kernel), std::nullptr_t>) {
-                        unsigned* tail = t_static < nTiles ? tail_slot(s) : nullptr;
-                        if (tail) {
-                            hipLaunchKernelGGL(tail_kernel, dim3((unsigned)blocks), dim3(256), G::LDS_BYTES, s,
-                                               reinterpret_cast<const float*>(a->J), reinterpret_cast<const float*>(a->D),
-                                               reinterpret_cast<const float*>(vin[k]), reinterpret_cast<float*>(vout[k]), a->E, nTiles, flags,
-                                               tail, t_static);
-                            continue;
-                        }
-                    }
-                    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), G::LDS_BYTES, s,
-                                       reinterpret_cast<const float*>(a->J), reinterpret_cast<const float*>(a->D),
-                                       reinterpret_cast<const float*>(vin[k]), reinterpret_cast<float*>(vout[k]), a->E, nTiles, flags);
-                }
-                FE_HIP_CHECK(hipGetLastError());
-                return FE_OK;
-            };
-            const int rc = a->Np == 20 ? launch(fe::GradF32GeomT<3, 20>{}, fe::grad3d_mfma_f32_kernel<3, 20>, fe::grad3d_mfma_f32_tail_kernel<3, 20>, "grad float32 Np=20 M=3")
-                           : a->Np == 10 ? launch(fe::GradF32GeomT<5, 10>{}, fe::grad3d_mfma_f32_kernel<5, 10>, fe::grad3d_mfma_f32_tail_kernel<5, 10>, "grad float32 Np=10 M=5")
-                           : a->Np == 4 ? launch(fe::GradF32GeomT<8, 4>{}, fe::grad3d_mfma_f32_kernel<8, 4>, fe::grad3d_mfma_f32_tail_kernel<8, 4>, "grad float32 Np=4 M=8")
-                           : m1 ? launch(fe::GradF32GeomT<1>{}, fe::grad3d_mfma_f32_kernel<1>, nullptr, "grad float32 Np=35 M=1")
-                                : launch(fe::GradF32GeomT<2>{}, fe::grad3d_mfma_f32_kernel<2>, fe::grad3d_mfma_f32_tail_kernel<2>, "grad float32 Np=35 M=2");
-            if (rc <= 0) return rc;
+            const int flags = opT | temporal_flag((9 + (int64_t)a->Np) * a->E * 4);
+            // behind two static rounds the tiles come by tickets (from five rounds on, as for float64) -- not on the one-sub-tile kernel
+            rc = a->Np == 20 ? launch_f32_fields<fe::GradF32GeomT<3, 20>, fe::grad3d_mfma_f32_kernel<3, 20>, fe::grad3d_mfma_f32_tail_kernel<3, 20>>(
+                                   a, vin, vout, b, flags, "grad float32 Np=20 M=3", s)
+                 : a->Np == 10 ? launch_f32_fields<fe::GradF32GeomT<5, 10>, fe::grad3d_mfma_f32_kernel<5, 10>, fe::grad3d_mfma_f32_tail_kernel<5, 10>>(
+                                     a, vin, vout, b, flags, "grad float32 Np=10 M=5", s)
+                 : a->Np == 4 ? launch_f32_fields<fe::GradF32GeomT<8, 4>, fe::grad3d_mfma_f32_kernel<8, 4>, fe::grad3d_mfma_f32_tail_kernel<8, 4>>(
+                                    a, vin, vout, b, flags, "grad float32 Np=4 M=8", s)
+                 : m1 ? launch_f32_fields<fe::GradF32GeomT<1>, fe::grad3d_mfma_f32_kernel<1>>(a, vin, vout, b, flags, "grad float32 Np=35 M=1", s)
+                      : launch_f32_fields<fe::GradF32GeomT<2>, fe::grad3d_mfma_f32_kernel<2>, fe::grad3d_mfma_f32_tail_kernel<2>>(
+                            a, vin, vout, b, flags, "grad float32 Np=35 M=2", s);
         }
+        if (rc <= 0) return rc;
     }
     for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // groups of up to kMaxFields fields share the staged operator
         const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;

@@ -1060,3 +1060,48 @@ def test_the_reference_regime_sizes_against_the_oracle(torch_cuda, E):
     for a, b in zip(pair, plain[:2]):
         for k in a:
             assert torch.equal(a[k], b[k])
+
+
+def _record_of(torch, expr, E, transform=None, prepare=False, dtype=None):
+    """fe_last_launch_info after one launch of *expr* at *E* elements (random device inputs), behind a launch that leaves a
+    different record (plain grad, E = 160 000: a dynamic walk of 10 000 tiles) -- a launcher that records nothing shows that one."""
+    from feinsum_amd import measure
+
+    f.evaluate(dg.grad(), 0, _device_inputs(torch, dg.grad(), 160000, 5), transform="mfma", wait=True)
+    assert _hip.last_launch_info()["tiles"] == 10000
+    dev = _device_inputs(torch, expr, E, 6)
+    if dtype is not None:
+        dev = {k: v.to(dtype) for k, v in dev.items()}
+    q, bound, _ = measure._bind(expr, 0, dev, None, transform, prepare=prepare)
+    bound.launch(q.stream_ptr)
+    q.finish()
+    return _hip.last_launch_info()
+
+
+def test_every_mfma_launch_is_recorded(torch_cuda):
+    """fe_last_launch_info describes the MFMA launch enqueued last on every path -- prepared operators, p = 5 (whose single-field
+    div walks by tickets), float32, triangles, div components -- not the launch before it."""
+    torch = torch_cuda
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+
+    def static(info, tiles, waves, per_cu):
+        blocks = min(-(-tiles // waves), per_cu * cus)
+        assert (info["blocks"], info["waves_per_block"], info["tiles"]) == (blocks, waves, tiles), info
+        assert not info["dynamic_walk"] and info["static_tiles"] == tiles, info
+
+    static(_record_of(torch, dg.grad(), 100000, prepare=True), 6250, 4, 2)                         # prepared grad
+    static(_record_of(torch, dg.face_mass(4), 100000, prepare=True), 6250, 4, 2)                   # prepared face-mass x 4
+    static(_record_of(torch, dg.batched_div_components(), 100000), 6250, 4, 2)                     # div components (the last)
+    grad_f32 = f.einsum("xre,rij,ej->xei", f.array("J", (3, 3, "E"), "float32"), f.array("R", (3, 35, 35), "float32"),
+                        f.array("u", ("E", 35), "float32"))
+    static(_record_of(torch, grad_f32, 100000, dtype=torch.float32), 6250, 4, 3)                   # float32 grad, M = 1
+    grad_tri = f.einsum("xre,rij,ej->xei", f.array("J", (2, 2, "E")), f.array("R", (2, 10, 10)), f.array("u", ("E", 10)))
+    static(_record_of(torch, grad_tri, 100000), 100000 // 96, 4, 2)                                # triangles p = 3
+    info = _record_of(torch, dg.div(56), 10 ** 6)                                                  # p = 5 div, one field
+    assert (info["blocks"], info["waves_per_block"], info["tiles"]) == (min(7813, cus), 8, 62500), info
+    assert info["dynamic_walk"] and info["static_tiles"] == 2 * 8 * info["blocks"], info
+
+
+def test_a_call_without_an_mfma_launch_records_none(torch_cuda):
+    """A call that runs only generic kernels reports no launch, not the one before it."""
+    assert _record_of(torch_cuda, dg.grad(), 1000, transform="generic") == {}
