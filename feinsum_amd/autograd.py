@@ -92,8 +92,8 @@ def expand_to_operand(value: Any, term_out: Sequence[str], wrt_subscripts: Seque
     """Broadcast a term's output (numpy or torch; axes *term_out*) to the operand's axes *wrt_subscripts* / *shape*."""
     view = tuple(int(shape[k]) if i in term_out else 1 for k, i in enumerate(wrt_subscripts))
     value = value.reshape(view)
-    if hasattr(value, "expand"):      # torch
-        return value.expand(*[int(d) for d in shape])
+    if hasattr(value, "expand"):      # torch (a size tuple: a 0-d operand expands to ())
+        return value.expand(tuple(int(d) for d in shape))
     return np.broadcast_to(value, tuple(int(d) for d in shape))
 
 
