@@ -263,20 +263,20 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Cooperative copy of an operator matrix (n doubles) from global memory into the start of the
+// Cooperative copy of an operator matrix (n doubles, or floats) from global memory into the start of the
 // block's LDS, all threads, coalesced.  Caller synchronises.  (2048 waves each gathering their
 // MFMA fragments of the same ~30 KB straight from L2 cost up to 18 us of prologue; staged once
 // per block it is ~5 us and the whole kernel ran 9 % faster in A/B.)
-template <int N, int THREADS = 256>
-__device__ __forceinline__ void stage_operator(const double* __restrict__ g, double* lds) {
+template <int N, int THREADS = 256, typename T>
+__device__ __forceinline__ void stage_operator(const T* __restrict__ g, T* lds) {
     // all loads are issued before the first LDS write so that their latencies overlap (a plain
     // copy loop waits for each load in turn: ~15 dependent L2 round trips).
     constexpr int kPer = (N + THREADS - 1) / THREADS;
-    double tmp[kPer];
+    T tmp[kPer];
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
         const int i = threadIdx.x + k * THREADS;
-        tmp[k] = (i < N) ? g[i] : 0.0;
+        tmp[k] = (i < N) ? g[i] : T(0);
     }
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {

@@ -1,4 +1,5 @@
-// fe_grad_f32.h -- grad einsum 'xre,rij,ej->xei' in float32 on the matrix cores (tetrahedra p = 4, Np = 35).
+// fe_grad_f32.h -- grad einsum 'xre,rij,ej->xei' in float32 on the matrix cores (tetrahedra p = 1 ... 4; the description is of p = 4,
+// Np = 35).
 //
 // The float32 counterpart of fe_grad.h's kernel, one wave = one tile of 16 elements, same data movement (LDS-DMA loads one
 // tile ahead with counted vmcnt, outputs transposed through wave-private LDS into 1-KiB contiguous non-temporal stores):
@@ -134,21 +135,7 @@ __device__ __forceinline__ void grad3d_mfma_f32_body(const float* __restrict__ J
             pre = true;
         }
     }
-    {
-        float* dl = reinterpret_cast<float*>(smem + G::IN_BYTES);
-        constexpr int kPer = (G::OP_F + 255) / 256;
-        float tmp[kPer];
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const int idx = threadIdx.x + k * 256;
-            tmp[k] = idx < G::OP_F ? D[idx] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const int idx = threadIdx.x + k * 256;
-            if (idx < G::OP_F) dl[idx] = tmp[k];
-        }
-    }
+    stage_operator<G::OP_F>(D, reinterpret_cast<float*>(smem + G::IN_BYTES));
     __syncthreads();
 
     // ---- A fragments: lane (g, n) supplies A[row n of tile t][k = 4 ks + g]; row n = 4 gp + v  ->  slot s = 4 t + v of

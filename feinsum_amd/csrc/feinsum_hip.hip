@@ -2778,60 +2778,28 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
             return fail(FE_EUNSUPPORTED, "fe_launch_f32: family %d has no float32 kernel", family);
     }
     if (!a->D || (family != FE_FAMILY_MATAPPLY && !a->J)) return fail(FE_EINVAL, "fe_launch_f32: null device pointer");
-    // grad of tetrahedra p = 4 on the matrix cores (fe_grad_f32.h): 16-byte aligned operands, E a multiple of 4 (so that
-    // every row of J and every output plane starts on a 16-byte boundary) and at least one full tile; else the tiled kernel
-    // div and face-mass likewise (fe_div_f32.h, fe_facemass_f32.h)
-    const bool grad_lower = family == FE_FAMILY_GRAD && ndim == 3 && (a->Np == 20 || a->Np == 10 || a->Np == 4);   // p = 1 ... 3 (round 4)
-    const bool div_lower = family == FE_FAMILY_DIV && ndim == 3 && (a->Np == 20 || a->Np == 10 || a->Np == 4);        // p = 1 ... 3 (round 5)
-    const bool fm_lower = family == FE_FAMILY_FACEMASS && nf == 4 &&
-                          ((a->Np == 20 && Nfp == 10) || (a->Np == 10 && Nfp == 6) || (a->Np == 4 && Nfp == 3));          // p = 1 ... 3 (round 5)
-    const bool mfma_shape = grad_lower || div_lower || (family == FE_FAMILY_GRAD && ndim == 3 && a->Np == 35) || (family == FE_FAMILY_DIV && ndim == 3 && a->Np == 35) ||
-                            (family == FE_FAMILY_FACEMASS && a->Np == 35 && nf == 4 && Nfp == 15) || fm_lower;
-    if (mfma_shape && a->variant != FE_VARIANT_TILED && a->E % 4 == 0 && a->E >= 16) {
+    // tetrahedra p = 1 ... 4 on the matrix cores (fe_grad_f32.h, fe_div_f32.h, fe_facemass_f32.h): 16-byte aligned operands, E a
+    // multiple of 4 (so that every row of J and every plane starts on a 16-byte boundary) and at least one full wave tile; else
+    // the tiled kernel.  The dispatches on Np below are the one list of shapes that have such a kernel: any other leaves rc = 1.
+    const bool tets = family == FE_FAMILY_FACEMASS ? nf == 4 : (family == FE_FAMILY_GRAD || family == FE_FAMILY_DIV) && ndim == 3;
+    if (tets && a->variant != FE_VARIANT_TILED && a->E % 4 == 0 && a->E >= 16) {
         bool aligned = ((reinterpret_cast<uintptr_t>(a->J) | reinterpret_cast<uintptr_t>(a->D)) & 15u) == 0;
         for (int k = 0; k < b; ++k)
             aligned = aligned && vin[k] && vout[k] && ((reinterpret_cast<uintptr_t>(vin[k]) | reinterpret_cast<uintptr_t>(vout[k])) & 15u) == 0;
-        int rc = 1;   // 1: no MFMA launch (unaligned, or too few elements for a wave tile): the tiled kernel below
+        int rc = 1;   // 1: no MFMA launch (no kernel for the shape, unaligned, or too few elements for a wave tile): the tiled kernel below
         if (!aligned) {
-        } else if (div_lower) {   // fe_div_f32.h: the kernel over the geometry (Np, M)
-            rc = a->Np == 20 ? launch_f32_fields<fe::DivF32GeomT<20, 1>, fe::div3d_mfma_f32_np_kernel<20, 1>>(a, vin, vout, b, opT, "div float32 Np=20 M=1", s)
-                 : a->Np == 10 ? launch_f32_fields<fe::DivF32GeomT<10, 3>, fe::div3d_mfma_f32_np_kernel<10, 3>>(a, vin, vout, b, opT, "div float32 Np=10 M=3", s)
-                               : launch_f32_fields<fe::DivF32GeomT<4, 5>, fe::div3d_mfma_f32_np_kernel<4, 5>>(a, vin, vout, b, opT, "div float32 Np=4 M=5", s);
-        } else if (family == FE_FAMILY_DIV) {
-            // the measured alternatives (profiles/r03/float32_div_facemass.txt) stay selectable in the experiment build
-#ifdef FE_EXPERIMENTS
-            static const int ring = [] { const char* e = getenv("FEINSUM_F32_DIV_RING"); return e && atoi(e) == 1 ? 1 : 2; }();
-            static const int small = [] { const char* e = getenv("FEINSUM_F32_SMALL"); return e ? atoi(e) : 1; }();
-            static const int f32dbg = [] { const char* e = getenv("FEINSUM_F32_DBG"); return e ? atoi(e) : 0; }();   // parts of the tile work removed
-#define FE_F32DBG_CASE(D) \
-    case D: rc = launch_f32_fields<fe::DivF32Geom<2>, fe::div3d_mfma_f32_kernel<2, true, D>>(a, vin, vout, b, opT, "div float32 experiment", s); break;
-            switch (f32dbg) {
-                FE_F32DBG_CASE(1) FE_F32DBG_CASE(2) FE_F32DBG_CASE(3) FE_F32DBG_CASE(4) FE_F32DBG_CASE(5) FE_F32DBG_CASE(6) FE_F32DBG_CASE(7)
-                FE_F32DBG_CASE(8) FE_F32DBG_CASE(9) FE_F32DBG_CASE(12) FE_F32DBG_CASE(15)
-                default:
-                    if (ring == 1)
-                        rc = launch_f32_fields<fe::DivF32Geom<1>, fe::div3d_mfma_f32_kernel<1, false>>(a, vin, vout, b, opT, "div float32 Np=35 one buffer", s);
-                    else if (!small)
-                        rc = launch_f32_fields<fe::DivF32Geom<2>, fe::div3d_mfma_f32_kernel<2, false>>(a, vin, vout, b, opT, "div float32 Np=35 three row tiles", s);
-                    else
-                        rc = launch_f32_fields<fe::DivF32Geom<2>, fe::div3d_mfma_f32_kernel<2, true>>(a, vin, vout, b, opT, "div float32 Np=35", s);
-            }
-#undef FE_F32DBG_CASE
-#else
-            rc = launch_f32_fields<fe::DivF32Geom<2>, fe::div3d_mfma_f32_kernel<2, true>>(a, vin, vout, b, opT, "div float32 Np=35", s);
-#endif
-        } else if (fm_lower) {   // fe_facemass_f32.h: the kernel over the geometry (Np, Nfp, M)
-            rc = a->Np == 20 ? launch_f32_facemass<fe::FmF32GeomT<20, 10, 1>, fe::facemass_mfma_f32_np_kernel<20, 10, 1>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=20 M=1", s)
-                 : a->Np == 10 ? launch_f32_facemass<fe::FmF32GeomT<10, 6, 2>, fe::facemass_mfma_f32_np_kernel<10, 6, 2>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=10 M=2", s)
-                               : launch_f32_facemass<fe::FmF32GeomT<4, 3, 4>, fe::facemass_mfma_f32_np_kernel<4, 3, 4>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=4 M=4", s);
-        } else if (family == FE_FAMILY_FACEMASS) {
-#ifdef FE_EXPERIMENTS
-            static const int small = [] { const char* e = getenv("FEINSUM_F32_SMALL"); return e ? atoi(e) : 1; }();
-            if (!small)
-                rc = launch_f32_facemass<fe::FmF32Geom, fe::facemass_mfma_f32_kernel<false>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=35 three row tiles", s);
-            else
-#endif
-                rc = launch_f32_facemass<fe::FmF32Geom, fe::facemass_mfma_f32_kernel<true>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=35", s);
+        } else if (family == FE_FAMILY_DIV) {   // the kernel over the geometry (Np, M)
+            rc = a->Np == 35 ? launch_f32_fields<fe::DivF32GeomT<35, 1>, fe::div3d_mfma_f32_kernel<35, 1>>(a, vin, vout, b, opT, "div float32 Np=35", s)
+                 : a->Np == 20 ? launch_f32_fields<fe::DivF32GeomT<20, 1>, fe::div3d_mfma_f32_kernel<20, 1>>(a, vin, vout, b, opT, "div float32 Np=20 M=1", s)
+                 : a->Np == 10 ? launch_f32_fields<fe::DivF32GeomT<10, 3>, fe::div3d_mfma_f32_kernel<10, 3>>(a, vin, vout, b, opT, "div float32 Np=10 M=3", s)
+                 : a->Np == 4 ? launch_f32_fields<fe::DivF32GeomT<4, 5>, fe::div3d_mfma_f32_kernel<4, 5>>(a, vin, vout, b, opT, "div float32 Np=4 M=5", s)
+                              : 1;
+        } else if (family == FE_FAMILY_FACEMASS) {   // the kernel over the geometry (Np, Nfp, M)
+            rc = a->Np == 35 && Nfp == 15 ? launch_f32_facemass<fe::FmF32GeomT<35, 15, 1>, fe::facemass_mfma_f32_kernel<35, 15, 1>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=35", s)
+                 : a->Np == 20 && Nfp == 10 ? launch_f32_facemass<fe::FmF32GeomT<20, 10, 1>, fe::facemass_mfma_f32_kernel<20, 10, 1>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=20 M=1", s)
+                 : a->Np == 10 && Nfp == 6 ? launch_f32_facemass<fe::FmF32GeomT<10, 6, 2>, fe::facemass_mfma_f32_kernel<10, 6, 2>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=10 M=2", s)
+                 : a->Np == 4 && Nfp == 3 ? launch_f32_facemass<fe::FmF32GeomT<4, 3, 4>, fe::facemass_mfma_f32_kernel<4, 3, 4>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=4 M=4", s)
+                                          : 1;
         } else {
             // two 16-element sub-tiles per wave iteration from E = 2e5 on (round 4: 4.5 KB store bursts, two blocks per CU: 68.1 ->
             // 70.5 % of the float32 roofline at 1e6, 70.2 -> 75.5 % at 4e6; below 2e5 the three-blocks-per-CU kernel of one sub-tile
@@ -2840,15 +2808,16 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
             const bool m1 = m_env == 1 || (m_env != 2 && a->E < 200000);
             const int flags = opT | temporal_flag((9 + (int64_t)a->Np) * a->E * 4);
             // behind two static rounds the tiles come by tickets (from five rounds on, as for float64) -- not on the one-sub-tile kernel
-            rc = a->Np == 20 ? launch_f32_fields<fe::GradF32GeomT<3, 20>, fe::grad3d_mfma_f32_kernel<3, 20>, fe::grad3d_mfma_f32_tail_kernel<3, 20>>(
-                                   a, vin, vout, b, flags, "grad float32 Np=20 M=3", s)
+            rc = a->Np == 35 ? (m1 ? launch_f32_fields<fe::GradF32GeomT<1>, fe::grad3d_mfma_f32_kernel<1>>(a, vin, vout, b, flags, "grad float32 Np=35 M=1", s)
+                                   : launch_f32_fields<fe::GradF32GeomT<2>, fe::grad3d_mfma_f32_kernel<2>, fe::grad3d_mfma_f32_tail_kernel<2>>(
+                                         a, vin, vout, b, flags, "grad float32 Np=35 M=2", s))
+                 : a->Np == 20 ? launch_f32_fields<fe::GradF32GeomT<3, 20>, fe::grad3d_mfma_f32_kernel<3, 20>, fe::grad3d_mfma_f32_tail_kernel<3, 20>>(
+                                     a, vin, vout, b, flags, "grad float32 Np=20 M=3", s)
                  : a->Np == 10 ? launch_f32_fields<fe::GradF32GeomT<5, 10>, fe::grad3d_mfma_f32_kernel<5, 10>, fe::grad3d_mfma_f32_tail_kernel<5, 10>>(
                                      a, vin, vout, b, flags, "grad float32 Np=10 M=5", s)
                  : a->Np == 4 ? launch_f32_fields<fe::GradF32GeomT<8, 4>, fe::grad3d_mfma_f32_kernel<8, 4>, fe::grad3d_mfma_f32_tail_kernel<8, 4>>(
                                     a, vin, vout, b, flags, "grad float32 Np=4 M=8", s)
-                 : m1 ? launch_f32_fields<fe::GradF32GeomT<1>, fe::grad3d_mfma_f32_kernel<1>>(a, vin, vout, b, flags, "grad float32 Np=35 M=1", s)
-                      : launch_f32_fields<fe::GradF32GeomT<2>, fe::grad3d_mfma_f32_kernel<2>, fe::grad3d_mfma_f32_tail_kernel<2>>(
-                            a, vin, vout, b, flags, "grad float32 Np=35 M=2", s);
+                              : 1;
         }
         if (rc <= 0) return rc;
     }

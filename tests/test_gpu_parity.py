@@ -740,7 +740,7 @@ F32_CASES = {
 @pytest.mark.parametrize("E", [1, 37, 132, 1000, 10007, 70004])
 def test_float32_families(torch_cuda, name, E):
     """All-float32 DG einsums (the reference validates float32 at 1e-6: src/feinsum/measure.py:178-192) run on the
-    matrix cores (grad / div / face-mass at p = 4 with E a multiple of 4: fe_grad_f32.h, fe_div_f32.h, fe_facemass_f32.h;
+    matrix cores (grad / div / face-mass at p = 1 ... 4 with E a multiple of 4: fe_grad_f32.h, fe_div_f32.h, fe_facemass_f32.h;
     E = 1000 has 62 tiles and 8 elements behind them, at E = 70 004 every wave walks several tiles and, with b fields,
     several (tile, field) units) or on the tiled kernel in float (fe_launch_f32), not on the one-thread-per-entry
     generic einsum kernel.  Compared with the
