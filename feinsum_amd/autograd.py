@@ -191,8 +191,12 @@ def _function():
                 q.stream.wait_stream(cur)
             outs = measure.evaluate(spec.einsum, q, dict(zip(spec.names, tensors)), transform=spec.transform,
                                     schedule=spec.schedule)
-            if own:
+            if own:      # the outputs belong to the queue's stream (measure.DeviceQueue); torch goes on with them on its own
+                from feinsum_amd import placement
+
                 cur.wait_stream(q.stream)
+                for t in outs.values():
+                    placement.record_stream(t, cur)
             ctx.spec = spec
             ctx.save_for_backward(*tensors)
             return tuple(outs[name] for name in spec.einsum.output_names)

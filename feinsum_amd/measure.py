@@ -84,7 +84,14 @@ class DeviceInfo:
 
 class DeviceQueue:
     """A HIP device + stream; duck-types the bits of ``cl.CommandQueue`` the
-    reference uses (``cq.device.name``, ``cq.finish()``)."""
+    reference uses (``cq.device.name``, ``cq.finish()``).
+
+    *stream* need not be the calling thread's current stream.  Every array the library allocates for a launch on this
+    queue -- outputs the caller does not hand in, prepared-operator buffers, intermediates, workspaces, the zero-filled
+    arrays of :func:`generate_out_arrays` -- is allocated and filled under this queue's stream and belongs to it, as a
+    tensor allocated inside ``torch.cuda.stream(stream)`` does: dropped, its memory goes to the next owner in this
+    stream's order.  Arrays the caller allocates itself (inputs, ``out_dict``) stay the caller's to order against
+    this stream."""
 
     def __init__(self, device: Any = 0, stream: Any = None) -> None:
         import torch
@@ -118,6 +125,18 @@ class DeviceQueue:
 
     def finish(self) -> None:
         self.stream.synchronize()
+
+
+def _on_stream_of(q: DeviceQueue):
+    """Context in which allocations and fills belong to *q*'s stream: nothing at all where that stream is the current
+    one (or a capture is in progress: its allocations are the capturing stream's), else ``torch.cuda.stream``."""
+    import contextlib
+
+    import torch
+
+    if q._stream is None or q._stream == torch.cuda.current_stream(q.torch_device) or torch.cuda.is_current_stream_capturing():
+        return contextlib.nullcontext()
+    return torch.cuda.stream(q._stream)
 
 
 def _as_queue(cq: Any) -> DeviceQueue:
@@ -193,26 +212,28 @@ def result_dtype(einsum: BatchedEinsum, row: int = 0) -> np.dtype:
 def generate_out_arrays(cq: Any, einsum: BatchedEinsum, long_dim_length: int, *, split: bool = False) -> Mapping[str, Any]:
     """Zero-filled device outputs ``_fe_out, _fe_out_0, ...`` (reference: measure.py:44-60).  *split*: one array each
     from the split allocator (``feinsum_amd.placement.zeros``: 4 MiB pieces alternating between two classes of physical
-    memory) instead of the torch allocator; arrays below 8 MiB come from torch either way."""
+    memory) instead of the torch allocator; arrays below 8 MiB come from torch either way.  Allocated and zero-filled
+    on the queue's stream (see :class:`DeviceQueue`): a launch on that queue is ordered behind the fill."""
     import torch
 
     q = _as_queue(cq)
     shape = _concrete_shape(einsum.shape, long_dim_length)
     outs = {}
-    if split and len(einsum.output_names) > 1:   # several arrays, allocated one after the other: say what is coming
-        from feinsum_amd import placement
-
-        nbytes = sum(int(np.prod(shape)) * result_dtype(einsum, k).itemsize for k in range(len(einsum.output_names)))
-        if nbytes >= placement.SPLIT_MIN_BYTES:
-            placement.split_reserve(nbytes, q.torch_device)
-    for k, name in enumerate(einsum.output_names):
-        tdtype = getattr(torch, result_dtype(einsum, k).name)
-        if split:
+    with _on_stream_of(q):
+        if split and len(einsum.output_names) > 1:   # several arrays, allocated one after the other: say what is coming
             from feinsum_amd import placement
 
-            outs[name] = placement.zeros(shape, tdtype, q.torch_device)
-        else:
-            outs[name] = torch.zeros(shape, dtype=tdtype, device=q.torch_device)
+            nbytes = sum(int(np.prod(shape)) * result_dtype(einsum, k).itemsize for k in range(len(einsum.output_names)))
+            if nbytes >= placement.SPLIT_MIN_BYTES:
+                placement.split_reserve(nbytes, q.torch_device)
+        for k, name in enumerate(einsum.output_names):
+            tdtype = getattr(torch, result_dtype(einsum, k).name)
+            if split:
+                from feinsum_amd import placement
+
+                outs[name] = placement.zeros(shape, tdtype, q.torch_device)
+            else:
+                outs[name] = torch.zeros(shape, dtype=tdtype, device=q.torch_device)
     return MappingProxyType(outs)
 
 
@@ -307,7 +328,8 @@ class _FamilyLaunch:
         tetrahedra p = 1..4, ``fe_prepare_operator``) into a device buffer owned by this bound launch;
         the launches then fetch their MFMA fragments from it instead of rebuilding them from the
         plain array every time.  The buffers are SNAPSHOTS: call this again after changing an
-        operator array in place.  Returns the number of prepared groups."""
+        operator array in place.  Returns the number of prepared groups.  New buffers are taken on the
+        current stream: call it with the stream of *stream_ptr* current (``_bind`` does)."""
         import torch
 
         if self.f32 or self.variant not in (_hip.VARIANT_AUTO, _hip.VARIANT_MFMA, _hip.VARIANT_MFMA_SPLIT) or self.group_family == FAMILY_GRADPLANES \
@@ -320,7 +342,7 @@ class _FamilyLaunch:
             key = (pack.D, pack.layout_flags)
             buf = self._prepared.get(key)
             fresh = buf is None
-            if fresh:
+            if fresh:    # on the stream that writes and reads it (the caller's current one: _bind switches to the queue's)
                 device = self._keep[1][0].device
                 buf = torch.empty(_hip.PREPARED_OPERATOR_BYTES, dtype=torch.uint8, device=device)
             flags = pack.layout_flags & ~1 if self.plan.family == FAMILY_FACEMASS else pack.layout_flags   # (not FM_J_FE)
@@ -498,15 +520,18 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     out_shape = tuple(sizes[d.name] if isinstance(d, SizeParam) else int(d) for d in einsum.shape)
     outs = []
     allocated: dict = {}      # outputs this call allocated itself: name -> "split" | "torch" | "torch (<why>)"
-    for k, name in enumerate(einsum.output_names):
-        dt = result_dtype(einsum, k)
-        if out_dict is not None and name in out_dict:
-            _check_tensor(name, out_dict[name], out_shape, dt, q)
-            outs.append(out_dict[name])
-        else:
-            tensor, how = _allocate_output(out_shape, getattr(torch, dt.name), q.torch_device, transform)
-            outs.append(tensor)
-            allocated[name] = how
+    owned = []                # ... and the arrays: they belong to the queue's stream (DeviceQueue)
+    with _on_stream_of(q):
+        for k, name in enumerate(einsum.output_names):
+            dt = result_dtype(einsum, k)
+            if out_dict is not None and name in out_dict:
+                _check_tensor(name, out_dict[name], out_shape, dt, q)
+                outs.append(out_dict[name])
+            else:
+                tensor, how = _allocate_output(out_shape, getattr(torch, dt.name), q.torch_device, transform)
+                outs.append(tensor)
+                owned.append(tensor)
+                allocated[name] = how
     kind = launch_kind(einsum, transform, sizes)
     if kind == "contraction":
         bound = ContractionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
@@ -517,7 +542,7 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     elif kind == "family":
         bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform))
         if _prepared_from_transform(transform, prepare):
-            with torch.cuda.device(q.torch_device):
+            with torch.cuda.device(q.torch_device), _on_stream_of(q):
                 bound.prepare_operators(q.stream_ptr)
     else:
         bound = _GenericLaunch(einsum, arg_dict, outs)
@@ -526,6 +551,7 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     bound.reads = tuple(span(arg_dict[name]) for name in sorted(einsum.all_args))
     bound.writes = tuple(span(t) for t in outs)
     bound.output_allocations = MappingProxyType(allocated)
+    bound.owned_arrays, bound.owned_stream_ptr = tuple(owned), q.stream_ptr   # (operator.py: launches on another stream mark them)
     return q, bound, outs
 
 
@@ -568,6 +594,13 @@ def evaluate(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *,
     (the replacement for ``t_unit.executor(cq, ...)(cq, **arg_dict)``,
     reference measure.py:163-165).  Asynchronous unless *wait*; outputs are
     fully overwritten.  *schedule*: see the module docstring.
+
+    Stream order: the outputs this call allocates (those not in *out_dict*) and everything else it allocates belong to
+    the queue's stream (:class:`DeviceQueue`), which need not be the current stream: they may be dropped at once, and
+    whoever gets their memory next -- on any stream -- is ordered behind this launch without a host synchronisation.
+    To READ them on another stream, order that stream behind the queue's and, as with any torch tensor,
+    ``placement.record_stream(out, that_stream)`` before dropping them.  The arrays the caller allocates (*arg_dict*,
+    *out_dict*) are the caller's to order against the queue's stream.
     """
     import torch
 

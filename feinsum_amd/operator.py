@@ -140,6 +140,8 @@ class BoundOperator:
         self.queue, self.launches, self.outputs = queue, launches, outputs
         self._graph = None
         self._capture_id = 0
+        self._stages: List[Any] = []
+        self._streams_known: set = set()      # streams (pointers) the arrays bound here are known to be used on
 
     @property
     def entry_points(self) -> Tuple[str, ...]:
@@ -156,13 +158,33 @@ class BoundOperator:
 
     def launch(self, stream_ptr: Optional[int] = None) -> None:
         s = self.queue.stream_ptr if stream_ptr is None else stream_ptr
+        if s not in self._streams_known:
+            self._used_on(s)
         for b in self.launches:
             b.launch(s)
+
+    def _used_on(self, s: int) -> None:
+        """The arrays this operator allocated at bind time (outputs not handed in, prepared operators) belong to the stream
+        it was bound on; a launch on another stream marks them, as ``ContractionLaunch`` marks its intermediates, so that
+        they outlive that stream's work too."""
+        import torch
+
+        from feinsum_amd import placement
+
+        if torch.cuda.is_current_stream_capturing():     # (the replays mark them: replay())
+            return
+        stream = torch.cuda.ExternalStream(s) if s else torch.cuda.default_stream(self.queue.torch_device)
+        for b in self._stages:
+            for t in getattr(b, "owned_arrays", ()):
+                placement.record_stream(t, stream)
+            for buf in getattr(b, "_prepared", {}).values():
+                buf.record_stream(stream)
+        self._streams_known.add(s)
 
     def refresh_operators(self) -> None:
         """Re-prepare the operator matrices after their arrays were changed in place (the prepared copies
         are snapshots taken at bind time; the fused launches hold the same buffers)."""
-        for b in getattr(self, "_stages", []):
+        for b in self._stages:
             if isinstance(b, _FamilyLaunch) and b._prepared:
                 b.prepare_operators(self.queue.stream_ptr)
 
@@ -218,6 +240,11 @@ class BoundOperator:
         """Enqueue the captured evaluation on the current stream."""
         if self._graph is None:
             raise RuntimeError("capture() the operator before replay()")
+        import torch
+
+        s = int(torch.cuda.current_stream(self.queue.torch_device).cuda_stream)
+        if s not in self._streams_known:
+            self._used_on(s)
         self._graph.replay()
 
     def time_batch(self, n: int, stream_ptr: Optional[int] = None, *, graph: bool = False) -> float:
@@ -250,7 +277,10 @@ def bind_operator(stages: Sequence[StageT], cq: Any, *,
     launches): write the operator matrices once in the kernels' fragment layout
     (``fe_prepare_operator``), so that the launches of this bound operator skip rebuilding them -- for
     operators that stay constant across launches, as in a time integrator.  The prepared copies are
-    snapshots: after changing an operator array in place call :meth:`BoundOperator.refresh_operators`."""
+    snapshots: after changing an operator array in place call :meth:`BoundOperator.refresh_operators`.
+
+    Stream order as in ``evaluate``: the outputs not handed in and the prepared operators are allocated under the
+    queue's stream and belong to it; ``launch`` / ``replay`` on another stream mark them as used there."""
     if out_dicts is not None and len(out_dicts) != len(stages):
         raise ValueError("out_dicts: need one entry (or None) per stage")
     queue, bound, outputs = None, [], []
@@ -261,6 +291,7 @@ def bind_operator(stages: Sequence[StageT], cq: Any, *,
         outputs.append(MappingProxyType(dict(zip(expr.output_names, outs))))
     op = BoundOperator(queue, _merge(bound) if fuse else bound, outputs)
     op._stages = bound
+    op._streams_known = {b.owned_stream_ptr for b in bound}
     return op
 
 

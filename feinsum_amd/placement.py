@@ -36,11 +36,13 @@ MIB = 1 << 20
 import logging as _logging
 import os as _os
 import threading as _threading
+import weakref as _weakref
 from collections import deque as _deque
 
 _log = _logging.getLogger(__name__)
 _recycle_lock = _threading.RLock()      # (re-entrant: a garbage collection inside a locked region may run another __del__)
-_recycled: Dict[Any, Any] = {}          # (device index, nbytes) -> deque of (ptr, event)
+_recycled: Dict[Any, Any] = {}          # (device index, nbytes) -> deque of (ptr, events: one per stream the array was used on)
+_live: Dict[Any, Any] = {}              # (device index, ptr) -> weakref of the _SplitBuffer that owns the array now
 _recycled_bytes: Dict[int, int] = {}    # device index -> bytes waiting
 _recycle_stats = {"reused": 0, "freed": 0, "kept": 0, "free_failures": 0}
 
@@ -100,19 +102,22 @@ class _SplitBuffer:
         self.nbytes, self.device_index = int(nbytes), int(device_index)
         self._free = _hip.split_free     # (bound now: module globals may be gone at interpreter exit)
         self.ptr = 0
+        stream = torch.cuda.current_stream(self.device_index)
+        self.streams = {int(stream.cuda_stream): stream}      # the owning stream, then every record_stream()
         with _recycle_lock:
             waiting = _recycled.get((self.device_index, self.nbytes))
             if waiting:
-                self.ptr, event = waiting.popleft()
+                self.ptr, events = waiting.popleft()
                 _recycled_bytes[self.device_index] -= self.nbytes
                 _recycle_stats["reused"] += 1
             else:
-                event = None
+                events = ()
         if self.ptr:
-            if event is not None:
-                torch.cuda.current_stream(self.device_index).wait_event(event)   # stream-ordered: no host synchronisation
+            for event in events:
+                stream.wait_event(event)                      # stream-ordered: no host synchronisation
         else:
             self.ptr = _hip.split_alloc(nbytes)
+        _live[(self.device_index, self.ptr)] = _weakref.ref(self)
         self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (self.ptr, False),
                                          "version": 3, "strides": None}
 
@@ -122,14 +127,21 @@ class _SplitBuffer:
             return
         victims = []
         try:
+            _live.pop((self.device_index, ptr), None)
             import torch
 
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("stream capture in progress")      # no event may be recorded now: free below (after the capture it syncs)
-            event = torch.cuda.Event()
-            event.record(torch.cuda.current_stream(self.device_index))
+            current = torch.cuda.current_stream(self.device_index)
+            streams = dict(self.streams)
+            streams.setdefault(int(current.cuda_stream), current)
+            events = []
+            for stream in streams.values():
+                event = torch.cuda.Event()
+                event.record(stream)
+                events.append(event)
             with _recycle_lock:
-                _recycled.setdefault((self.device_index, self.nbytes), _deque()).append((ptr, event))
+                _recycled.setdefault((self.device_index, self.nbytes), _deque()).append((ptr, tuple(events)))
                 _recycled_bytes[self.device_index] = _recycled_bytes.get(self.device_index, 0) + self.nbytes
                 _recycle_stats["kept"] += 1
                 cap = _recycle_cap()
@@ -147,6 +159,18 @@ class _SplitBuffer:
             _really_free(self._free, self.device_index, v)
 
 
+def record_stream(tensor: Any, stream: Any) -> None:
+    """``tensor.record_stream(stream)`` for any device tensor: *tensor* is used on *stream*, which is not the stream it
+    was allocated on, so whoever gets its memory next must wait for *stream* too.  For an array of the split allocator
+    (where ``torch.Tensor.record_stream`` does nothing) the release event is recorded on *stream* as well."""
+    ref = _live.get((tensor.device.index, tensor.untyped_storage().data_ptr())) if tensor.is_cuda else None
+    buf = ref() if ref is not None else None
+    if buf is not None:
+        buf.streams.setdefault(int(stream.cuda_stream), stream)
+    elif tensor.is_cuda:
+        tensor.record_stream(stream)
+
+
 def empty(shape: Sequence[int], dtype: Any = None, device: Any = None, *, written: bool = True) -> Any:
     """
     A new uninitialised device tensor, as ``torch.empty`` -- for arrays a launch WRITES taken from the split allocator:
@@ -156,7 +180,8 @@ def empty(shape: Sequence[int], dtype: Any = None, device: Any = None, *, writte
     alike, with the default kernels.  No arena and no timing scan: the memory mapped is the array's size rounded up to
     2 MiB; arrays below 8 MiB, ``written=False`` and CPU devices get a plain ``torch.empty`` (where a read-only array
     lies does not matter).  The tensor is an ordinary torch tensor (views, copies, kernels); its memory returns to the
-    allocator's pool when the last view is gone.
+    allocator's pool when the last view is gone.  The array belongs to the stream that is current in this call (see
+    the recycling comment above): work on another stream is announced with :func:`record_stream`.
     """
     import torch
 
@@ -199,7 +224,8 @@ def is_split(tensor: Any) -> bool:
 
 
 def zeros(shape: Sequence[int], dtype: Any = None, device: Any = None, *, written: bool = True) -> Any:
-    """:func:`empty`, zero-filled (what the reference's ``cla.zeros`` outputs are: ``src/feinsum/measure.py:44-60``)."""
+    """:func:`empty`, zero-filled on the current stream (what the reference's ``cla.zeros`` outputs are:
+    ``src/feinsum/measure.py:44-60``)."""
     return empty(shape, dtype, device, written=written).zero_()
 
 
