@@ -359,7 +359,12 @@ class _FamilyLaunch:
     def _bind_planes(self, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any]) -> bool:
         """Rows of 're,rij,ej->ei' that share u and D (e.g. the curl-type batch of
         ``tuning/impls/re_rji_ej_to_ei_3d_cross_product_v0.py:220-231``) go through the grad-type
-        planes launch, which forms D u once per field.  False: keep one launch per row."""
+        planes launch, which forms D u once per field.  False: keep one launch per row.
+
+        The rule: J stored ``re`` (not ``er``), tetrahedra, ONE operator name, at most three geometry-factor names,
+        every field with the same number of planes, that number at least two, and no (field, factor) pair twice.
+        Plane x of every field is the x-th factor name in sorted order, whatever the order of the rows; a field
+        without that plane gets no output there."""
         role, rows = self.plan.roles, einsum.args
         if self.plan.layout_flags & OP_J_ES or self.plan.params.get("ndim", 3) != 3:
             return False
@@ -469,6 +474,39 @@ class _GenericLaunch:
         return _hip.time_with_events(self.launch, n, stream_ptr)
 
 
+def _generic_kernel_is_the_einsum_one(plan: KernelPlan) -> bool:
+    """float64 grad / div / div components of triangles have the matrix-core and the tiled kernels but no plain
+    one-thread-per-entry kernel of their own: ``"generic"`` runs them on the generic einsum kernel."""
+    return (plan.family in (FAMILY_GRAD, FAMILY_DIV, FAMILY_DIVCOMP) and plan.params.get("ndim") == 2
+            and not plan.params.get("f32"))
+
+
+def _overlap(a: Sequence[Tuple[int, int]], b: Sequence[Tuple[int, int]]) -> bool:
+    """Do two lists of (address, nbytes) ranges share a byte?  (A range of no bytes shares none.)"""
+    return any(pa < pb + nb and pb < pa + na for pa, na in a for pb, nb in b if na and nb)
+
+
+def _span(t: Any) -> Tuple[int, int]:
+    """(address, nbytes) of a contiguous tensor."""
+    return int(t.data_ptr()), int(t.numel()) * int(t.element_size())
+
+
+def _refuse_aliased_outputs(einsum: BatchedEinsum, arg_dict: Mapping[str, Any], given: Mapping[str, Any]) -> None:
+    """The aliasing rule of :func:`evaluate`: no output handed in may share a byte with an input or with another
+    output (the kernels read their operands while other threads already store results)."""
+    names = list(given)
+    for k, name in enumerate(names):
+        for other in sorted(einsum.all_args):
+            if _overlap([_span(given[name])], [_span(arg_dict[other])]):
+                raise InvalidParameterError(
+                    f"output '{name}' shares memory with input '{other}': an evaluation may not write what it reads"
+                    " (hand in an output of its own)")
+        for other in names[:k]:
+            if _overlap([_span(given[name])], [_span(given[other])]):
+                raise InvalidParameterError(
+                    f"output '{name}' shares memory with output '{other}': every output needs memory of its own")
+
+
 def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int]) -> str:
     """
     Which kernels run *einsum* under *transform* (size parameters *sizes*): ``"reduction"`` (the transform of that
@@ -476,7 +514,8 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     families where ``reduction.auto_picks_reduction`` finds a long summation space summed into a small output),
     ``"contraction"`` (the transform of that name, or ``"auto"`` on a two-operand einsum outside the DG families where
     ``contraction.auto_picks_contraction`` says the contraction kernel wins), ``"family"`` (a DG family kernel) or
-    ``"generic"``.  The reduction rule is checked before the contraction rule.  ``"adjoint"`` (that transform only: an
+    ``"generic"`` (also the ``"generic"`` transform on float64 grad / div / div components of triangles, which have no
+    plain kernel of their own).  The reduction rule is checked before the contraction rule.  ``"adjoint"`` (that transform only: an
     einsum that ``family.match_adjoint_family`` recognises, else ``NotImplementedError``) runs the adjoint kernels.
     """
     variant = _variant_from_transform(transform)
@@ -491,7 +530,8 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     if variant == "reduction":
         check_reduction(einsum, sizes)
         return "reduction"
-    if match_family(einsum) is not None:
+    plan = match_family(einsum)
+    if plan is not None and not (variant in ("generic", 1) and _generic_kernel_is_the_einsum_one(plan)):
         return "family"
     if variant not in (None, "auto", "generic", 0, 1):
         raise NotImplementedError(
@@ -518,15 +558,19 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
         concrete = tuple(sizes[d.name] if isinstance(d, SizeParam) else int(d) for d in shape)
         _check_tensor(name, arg_dict[name], concrete, einsum.arg_to_dtype[name], q)
     out_shape = tuple(sizes[d.name] if isinstance(d, SizeParam) else int(d) for d in einsum.shape)
+    given = {name: out_dict[name] for name in einsum.output_names if out_dict is not None and name in out_dict}
+    for k, name in enumerate(einsum.output_names):
+        if name in given:
+            _check_tensor(name, given[name], out_shape, result_dtype(einsum, k), q)
+    _refuse_aliased_outputs(einsum, arg_dict, given)     # before anything is allocated, prepared or launched
     outs = []
     allocated: dict = {}      # outputs this call allocated itself: name -> "split" | "torch" | "torch (<why>)"
     owned = []                # ... and the arrays: they belong to the queue's stream (DeviceQueue)
     with _on_stream_of(q):
         for k, name in enumerate(einsum.output_names):
             dt = result_dtype(einsum, k)
-            if out_dict is not None and name in out_dict:
-                _check_tensor(name, out_dict[name], out_shape, dt, q)
-                outs.append(out_dict[name])
+            if name in given:
+                outs.append(given[name])
             else:
                 tensor, how = _allocate_output(out_shape, getattr(torch, dt.name), q.torch_device, transform)
                 outs.append(tensor)
@@ -547,9 +591,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     else:
         bound = _GenericLaunch(einsum, arg_dict, outs)
     # byte ranges the launch reads and writes (operator.py checks them before reordering launches)
-    span = lambda t: (int(t.data_ptr()), int(t.numel()) * int(t.element_size()))   # noqa: E731
-    bound.reads = tuple(span(arg_dict[name]) for name in sorted(einsum.all_args))
-    bound.writes = tuple(span(t) for t in outs)
+    bound.reads = tuple(_span(arg_dict[name]) for name in sorted(einsum.all_args))
+    bound.writes = tuple(_span(t) for t in outs)
     bound.output_allocations = MappingProxyType(allocated)
     bound.owned_arrays, bound.owned_stream_ptr = tuple(owned), q.stream_ptr   # (operator.py: launches on another stream mark them)
     return q, bound, outs
@@ -594,6 +637,11 @@ def evaluate(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *,
     (the replacement for ``t_unit.executor(cq, ...)(cq, **arg_dict)``,
     reference measure.py:163-165).  Asynchronous unless *wait*; outputs are
     fully overwritten.  *schedule*: see the module docstring.
+
+    Aliasing: an output handed in through *out_dict* may not share a byte with any input, nor with another output
+    (``InvalidParameterError``, raised before anything is allocated, prepared or launched, under every transform): the
+    kernels read their operands while other threads already store results, so an in-place step needs a second
+    array.  Arrays of no bytes overlap nothing, views that merely touch are fine, and inputs may overlap inputs.
 
     Stream order: the outputs this call allocates (those not in *out_dict*) and everything else it allocates belong to
     the queue's stream (:class:`DeviceQueue`), which need not be the current stream: they may be dropped at once, and

@@ -32,7 +32,7 @@ from typing import Any, List, Mapping, Optional, Sequence, Tuple
 from feinsum_amd import _hip
 from feinsum_amd.einsum import BatchedEinsum
 from feinsum_amd.family import FAMILY_DIV, FAMILY_FACEMASS, FAMILY_GRAD
-from feinsum_amd.measure import _bind, _FamilyLaunch
+from feinsum_amd.measure import _bind, _FamilyLaunch, _overlap
 
 StageT = Tuple[BatchedEinsum, Mapping[str, Any]]
 
@@ -70,11 +70,6 @@ def _single_plain_group(b: Any, family: int) -> bool:
     return (isinstance(b, _FamilyLaunch) and b.plan.family == family and len(b.groups) == 1
             and (family == FAMILY_FACEMASS
                  or (b.groups[0].b == 1 and b.plan.layout_flags == 0 and b.groups[0].ndim == 3)))
-
-
-def _overlap(a: Sequence[Tuple[int, int]], b: Sequence[Tuple[int, int]]) -> bool:
-    """Do two lists of (address, nbytes) ranges share a byte?"""
-    return any(pa < pb + nb and pb < pa + na for pa, na in a for pb, nb in b if na and nb)
 
 
 def _conflict(x: Any, y: Any) -> bool:
@@ -279,6 +274,11 @@ def bind_operator(stages: Sequence[StageT], cq: Any, *,
     operators that stay constant across launches, as in a time integrator.  The prepared copies are
     snapshots: after changing an operator array in place call :meth:`BoundOperator.refresh_operators`.
 
+    Aliasing as in ``evaluate``, stage by stage: a stage whose outputs share a byte with its own inputs or with each
+    other is refused (``InvalidParameterError``, before anything is allocated or launched).  ACROSS stages the arrays
+    may overlap -- stage k may write what stage k + 1 reads; such stages keep their order and are never merged into
+    one launch.
+
     Stream order as in ``evaluate``: the outputs not handed in and the prepared operators are allocated under the
     queue's stream and belong to it; ``launch`` / ``replay`` on another stream mark them as used there."""
     if out_dicts is not None and len(out_dicts) != len(stages):
@@ -298,7 +298,9 @@ def bind_operator(stages: Sequence[StageT], cq: Any, *,
 def evaluate_operator(stages: Sequence[StageT], cq: Any, *,
                       out_dicts: Optional[Sequence[Optional[Mapping[str, Any]]]] = None,
                       transform: Any = None, fuse: bool = True, wait: bool = False) -> List[Mapping[str, Any]]:
-    """Enqueue all stages; returns one ``{"_fe_out": tensor, ...}`` mapping per stage."""
+    """Enqueue all stages; returns one ``{"_fe_out": tensor, ...}`` mapping per stage.  The aliasing rule of
+    :func:`bind_operator` holds: no stage may write what it reads itself, a later stage may read what an earlier one
+    wrote."""
     import torch
 
     op = bind_operator(stages, cq, out_dicts=out_dicts, transform=transform, fuse=fuse)

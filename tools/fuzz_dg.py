@@ -289,22 +289,24 @@ def _e_axis(expr, name: Optional[str]) -> Optional[int]:
     return None
 
 
-def references(torch, case: DGCase, arrays, mants, scales, sig, dev, st: Optional[Stats] = None):
-    """``[{output name: reference (device tensor)}]`` per stage.  E <= HOST_REF_MAX_E: the int64 reference of the whole
+def references(torch, case: DGCase, arrays, mants, scales, sig, dev, st: Optional[Stats] = None, e_axis=None):
+    """``[{output name: reference (device tensor)}]`` per stage (*e_axis*: ``(expr, array name or None) -> element axis``
+    where the element axis is not a size parameter; default :func:`_e_axis`).  E <= HOST_REF_MAX_E: the int64 reference of the whole
     array, and torch's float64 einsum must agree with it everywhere; else torch's float64 einsum of the whole array,
     checked against the int64 reference on first / middle / last / random slices."""
     refs = []
     rng = np.random.default_rng(case.seed + 1)
     E = case.E
+    e_axis = e_axis or _e_axis
     for expr, keys in case.stages():
         subs = expr.get_subscripts()
         out_dt = np.dtype("float32") if case.dtype == "float32" else np.dtype("float64")
-        oax = _e_axis(expr, None)
+        oax = e_axis(expr, None)
         per = {}
         for out_name, row in zip(expr.output_names, expr.args):
             ks = [keys[a.name] for a in row]
             total = sum(scales[k] for k in ks)
-            eaxes = [_e_axis(expr, a.name) for a in row]
+            eaxes = [e_axis(expr, a.name) for a in row]
             if E <= HOST_REF_MAX_E:
                 host = ref_.int_reference(subs, [mants[k] for k in ks], total, out_dt, sig)
                 r = torch.from_numpy(host).cuda()
