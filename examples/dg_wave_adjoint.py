@@ -7,7 +7,10 @@ differentiated with respect to the field u, the volume geometric factors J and t
 ``evaluate_differentiable`` and ``torch.autograd`` (the J- and face-adjoints run on the adjoint kernels),
 then checked against a central finite difference along a random direction.
 
-    python examples/dg_wave_adjoint.py [E]
+    python examples/dg_wave_adjoint.py [E] [--operators]
+
+``--operators`` also differentiates with respect to the operator matrices D and L, on the operator-gradient kernels
+(``operator_gradients="kernel"``).
 """
 import sys
 from pathlib import Path
@@ -22,7 +25,7 @@ import feinsum_amd as f  # noqa: E402
 NP, NF, NFP = 35, 4, 15
 
 
-def main(E: int = 100_000) -> None:
+def main(E: int = 100_000, operators: bool = False) -> None:
     grad = f.einsum("xre,rij,ej->xei", f.array("J", (3, 3, "E")), f.array("D", (3, NP, NP)), f.array("u", ("E", NP)))
     lift = f.batched_einsum("ef,fij,fej->ei", [[f.array("Jf", ("E", NF)), f.array("L", (NF, NP, NFP)),
                                                 f.array(f"v{k}", (NF, "E", NFP))] for k in range(3)])
@@ -34,13 +37,14 @@ def main(E: int = 100_000) -> None:
     data_grad = torch.from_numpy(rng.standard_normal((3, E, NP))).cuda()
     data_lift = [torch.from_numpy(rng.standard_normal((E, NP))).cuda() for _ in range(3)]
     dev = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
-    wrt = ("u", "J", "Jf")
+    wrt = ("u", "J", "Jf") + (("D", "L") if operators else ())
+    og = "kernel" if operators else "auto"
     for k in wrt:
         dev[k].requires_grad_(True)
 
     def loss(arrays):
-        g = f.evaluate_differentiable(grad, 0, {k: arrays[k] for k in ("J", "D", "u")})["_fe_out"]
-        outs = f.evaluate_differentiable(lift, 0, {k: arrays[k] for k in lift.all_args})
+        g = f.evaluate_differentiable(grad, 0, {k: arrays[k] for k in ("J", "D", "u")}, operator_gradients=og)["_fe_out"]
+        outs = f.evaluate_differentiable(lift, 0, {k: arrays[k] for k in lift.all_args}, operator_gradients=og)
         val = 0.5 * ((g - data_grad) ** 2).sum()
         for name, d in zip(lift.output_names, data_lift):
             val = val + 0.5 * ((outs[name] - d) ** 2).sum()
@@ -61,4 +65,5 @@ def main(E: int = 100_000) -> None:
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 100_000)
+    argv = [a for a in sys.argv[1:] if a != "--operators"]
+    main(int(argv[0]) if argv else 100_000, operators="--operators" in sys.argv[1:])

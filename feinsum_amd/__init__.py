@@ -16,7 +16,7 @@ from feinsum_amd.diagnostics import (EinsumTunitMatchError, HipLibraryError, Inv
                                      TransformValidationError)
 from feinsum_amd.einsum import (Array, BatchedEinsum, EinsumAxisAccess, FreeAxis, SizeParam,
                                 SummationAxis)
-from feinsum_amd.family import AdjointPlan, KernelPlan, match_adjoint_family, match_family
+from feinsum_amd.family import AdjointPlan, KernelPlan, match_adjoint_family, match_family, match_operator_adjoint
 from feinsum_amd.make_einsum import array, batched_einsum, einsum
 from feinsum_amd.canonicalization import canonicalize_einsum
 from feinsum_amd.sql_utils import (QueryInfo, get_timed_einsums_in_db, query, query_reference_archive, record_facts,
@@ -29,7 +29,7 @@ from feinsum_amd.measure import (DeviceQueue, evaluate, generate_input_arrays, g
 from feinsum_amd.autograd import adjoint_einsums, evaluate_differentiable
 
 __all__ = (
-    "AdjointPlan", "adjoint_einsums", "evaluate_differentiable", "match_adjoint_family",
+    "AdjointPlan", "adjoint_einsums", "evaluate_differentiable", "match_adjoint_family", "match_operator_adjoint",
     "Array", "BatchedEinsum", "BoundOperator", "ContractionSchedule", "DeviceQueue", "EinsumAxisAccess",
     "EinsumTunitMatchError", "FakeCLDevice", "FreeAxis", "HipLibraryError", "InvalidParameterError", "KernelPlan",
     "NoDevicePeaksInfoError", "NoFactInDatabaseError", "QueryInfo", "SizeParam", "SummationAxis",

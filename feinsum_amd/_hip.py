@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = (
     "fe_graddiv3d_prepared_f64", "fe_waveop3d_prepared_f64", "fe_divcomp_f64", "fe_release_prepared",
     "fe_split_alloc", "fe_split_free", "fe_split_info", "fe_split_stats", "fe_split_reserve", "fe_split_trim", "fe_launch_f32", "fe_set_tail_rounds", "fe_set_tail_min_rounds",
     "fe_set_cu_limit", "fe_set_phase_priority_p5", "fe_set_div_interleave", "fe_set_div_quarter_tail", "fe_set_grad_quarter_tail", "fe_set_grad_staggered_start", "fe_last_launch_info", "fe_stream_retired", "fe_capture_id", "fe_graph_retired", "fe_tail_stats", "fe_tail_check", "fe_tail_plant", "fe_set_temporal_loads_mib", "fe_set_write_through_mib",
-    "fe_geomadj_f64", "fe_facemass_adj_f64",
+    "fe_geomadj_f64", "fe_facemass_adj_f64", "fe_opgrad_plan", "fe_opgrad_f64", "fe_facemass_opgrad_f64",
 )
 FAMILY_F32 = 0x100    # FE_FAMILY_F32
 
@@ -262,6 +262,14 @@ def load_library() -> C.CDLL:
     lib.fe_facemass_adj_f64.restype = C.c_int
     lib.fe_facemass_adj_f64.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p), C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p]
+    lib.fe_opgrad_plan.restype = C.c_int
+    lib.fe_opgrad_plan.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
+    lib.fe_opgrad_f64.restype = C.c_int
+    lib.fe_opgrad_f64.argtypes = ([C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64]
+                                  + [C.c_int32] * 4 + [C.c_int64] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p])
+    lib.fe_facemass_opgrad_f64.restype = C.c_int
+    lib.fe_facemass_opgrad_f64.argtypes = ([C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64]
+                                           + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p])
     _lib = lib
     return lib
 
@@ -403,6 +411,29 @@ def facemass_adj(J: Optional[int], R: int, g: Sequence[int], v: Optional[Sequenc
 
 
 PREPARED_OPERATOR_BYTES = 96 * 1024   # FE_PREPARED_OPERATOR_BYTES
+
+
+def opgrad_plan(E: int, n_out_entries: int) -> Tuple[int, int]:
+    """``(slices, workspace bytes)`` of an operator-gradient launch (``fe_opgrad_plan``, host only)."""
+    slices, nbytes = C.c_int64(0), C.c_size_t(0)
+    check(load_library().fe_opgrad_plan(E, n_out_entries, C.byref(slices), C.byref(nbytes)))
+    return int(slices.value), int(nbytes.value)
+
+
+def opgrad(J: Optional[int], a: Sequence[int], b: Sequence[int], out: int, E: int, X: int, R: int, Np: int,
+           jstrides: Sequence[int], strides: Sequence[int], workspace: Optional[int], workspace_bytes: int,
+           stream: int = 0) -> None:
+    """``out[r sr + p sp + q sq] = sum_k sum_e (sum_x J[x jx + r jr + e je] b_k[x][e][p]) a_k[e][q]`` (fe_opgrad_f64;
+    *jstrides* = (jx, jr, je), *strides* = (sr, sp, sq))."""
+    check(load_library().fe_opgrad_f64(J, _ptr_array(a), _ptr_array(b), out, E, len(a), X, R, Np, *jstrides, *strides,
+                                       workspace, workspace_bytes, stream))
+
+
+def facemass_opgrad(J: Optional[int], g: Sequence[int], v: Sequence[int], dR: int, E: int, Np: int, nf: int, Nfp: int,
+                    workspace: Optional[int], workspace_bytes: int, layout_flags: int = 0, stream: int = 0) -> None:
+    """``dR[f, i, j] = sum_k sum_e g_k[e][i] J[e, f] v_k[f][e][j]`` in R's layout (fe_facemass_opgrad_f64)."""
+    check(load_library().fe_facemass_opgrad_f64(J, _ptr_array(g), _ptr_array(v), dR, E, Np, nf, Nfp, len(g), layout_flags,
+                                                workspace, workspace_bytes, stream))
 
 
 def prepare_operator(family: int, op: int, Np: int, nf: int, Nfp: int, flags: int, prepared: int,

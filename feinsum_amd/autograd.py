@@ -21,13 +21,14 @@ import numpy as np
 
 from feinsum_amd.contraction_schedule import ContractionSchedule
 from feinsum_amd.einsum import BatchedEinsum, SizeParam
-from feinsum_amd.family import ADJ_FACEMASS_J, match_adjoint_family, match_family
+from feinsum_amd.family import ADJ_FACEMASS_J, match_adjoint_family, match_family, match_operator_adjoint
 from feinsum_amd.make_einsum import array
 
 #: prefix of the output-gradient operands of the adjoint einsums; no user array may start with it
 GRAD_PREFIX = "_fe_grad"
 
-#: launches of the backward passes of this process, by route: "family", "geomadj", "facemass_v", "facemass_j", "auto"
+#: launches of the backward passes of this process, by route: "family", "geomadj", "facemass_v", "facemass_j", "auto",
+#: and with ``operator_gradients="kernel"`` also "opgrad_d", "opgrad_r"
 launch_counts: Counter = Counter()
 
 
@@ -108,13 +109,14 @@ class _Spec:
     queue: Any
     transform: Any
     schedule: Optional[ContractionSchedule]
+    operator_gradients: str = "auto"
 
 
 def _concrete(shape, sizes) -> Tuple[int, ...]:
     return tuple(sizes[d.name] if isinstance(d, SizeParam) else int(d) for d in shape)
 
 
-def _run_term(term: BatchedEinsum, args: Mapping[str, Any], q: Any) -> Any:
+def _run_term(term: BatchedEinsum, args: Mapping[str, Any], q: Any, operator_gradients: str = "auto") -> Any:
     """Sum of the rows of an adjoint einsum, on q's stream, in ordinary torch allocations."""
     import torch
 
@@ -124,6 +126,14 @@ def _run_term(term: BatchedEinsum, args: Mapping[str, Any], q: Any) -> Any:
     sizes = measure._long_length(term, args)
     shape = _concrete(term.shape, sizes)
     dtypes = [getattr(torch, measure.result_dtype(term, k).name) for k in range(term.b)]
+    op_plan = match_operator_adjoint(term) if operator_gradients == "kernel" else None
+    if op_plan is not None:
+        # the operator gradient on the matrix cores: one launch, the rows (they share J) summed in the kernel in row order
+        out = torch.empty(shape, dtype=dtypes[0], device=q.torch_device)
+        with torch.cuda.device(q.torch_device):
+            AdjointLaunch(op_plan, term, args, [out], sum_rows=True, stream=q.stream).launch(q.stream_ptr)
+        launch_counts[op_plan.kind] += 1
+        return out
     plan = match_adjoint_family(term)
     if plan is not None and plan.kind == ADJ_FACEMASS_J and len({row[plan.roles["R"]].name for row in term.args}) == 1:
         # every field into one dJ, summed inside the kernel in row order
@@ -166,7 +176,7 @@ def _backward(ctx, spec: _Spec, grads) -> List[Any]:
             if not rows:
                 continue
             sub = term.einsum.copy(args=rows)
-            value = expand_to_operand(_run_term(sub, args, q), sub.out_idx_set, term.wrt_subscripts, target.shape)
+            value = expand_to_operand(_run_term(sub, args, q, spec.operator_gradients), sub.out_idx_set, term.wrt_subscripts, target.shape)
             total = value.contiguous() if total is None else total.add_(value)
         if total is not None and total.dtype != target.dtype:
             total = total.to(target.dtype)       # float32 operand of a float64 einsum: computed in float64, rounded once
@@ -227,16 +237,24 @@ _FN = None
 
 
 def evaluate_differentiable(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *, transform: Any = None,
-                            schedule: Optional[ContractionSchedule] = None) -> Mapping[str, Any]:
+                            schedule: Optional[ContractionSchedule] = None,
+                            operator_gradients: str = "auto") -> Mapping[str, Any]:
     """:func:`~feinsum_amd.measure.evaluate` as a ``torch.autograd.Function``: returns ``{name: tensor}``, bitwise the
     outputs of ``evaluate`` with the same *transform*, carrying a ``grad_fn`` when an input requires grad.  The backward
     pass computes the gradients ``ctx.needs_input_grad`` asks for, on the stream it runs on (with a ``DeviceQueue`` of
     its own stream: ordered against torch's current stream by events both ways), into ordinary torch allocations.
-    Double backward is not supported (``once_differentiable``)."""
+    Double backward is not supported (``once_differentiable``).
+
+    *operator_gradients*: ``"auto"`` runs the gradients with respect to the operator matrices (D, R) as ``"auto"`` runs
+    their adjoint einsums; ``"kernel"`` sends every such term that :func:`~feinsum_amd.family.match_operator_adjoint`
+    accepts to the operator-gradient kernels (``launch_counts["opgrad_d"]`` / ``["opgrad_r"]``; one launch for all rows
+    of a batched term) and leaves every other term on its route.  Anything else: ``InvalidParameterError``."""
     global _FN
     from feinsum_amd.diagnostics import InvalidParameterError
     from feinsum_amd.measure import _as_queue
 
+    if operator_gradients not in ("auto", "kernel"):
+        raise InvalidParameterError(f"operator_gradients must be 'auto' or 'kernel' (got {operator_gradients!r})")
     if _FN is None:
         _FN = _function()
     q = _as_queue(cq)
@@ -244,5 +262,5 @@ def evaluate_differentiable(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[st
     missing = [n for n in names if n not in arg_dict]
     if missing:
         raise InvalidParameterError(f"missing input arrays: {missing}")
-    outs = _FN.apply(_Spec(einsum, names, q, transform, schedule), *[arg_dict[n] for n in names])
+    outs = _FN.apply(_Spec(einsum, names, q, transform, schedule, operator_gradients), *[arg_dict[n] for n in names])
     return MappingProxyType(dict(zip(einsum.output_names, outs)))

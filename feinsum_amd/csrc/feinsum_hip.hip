@@ -21,6 +21,7 @@
 #include "../../include/feinsum_hip.h"
 #include "fe_common.h"
 #include "fe_adjoint.h"
+#include "fe_opgrad.h"
 #include "fe_contract.h"
 #include "fe_div.h"
 #include "fe_einsum.h"
@@ -2490,6 +2491,23 @@ int fe_einsum_reduce_plan(const fe_einsum_desc* d, int32_t* path, int64_t* slice
     return FE_OK;
 }
 
+}  // extern "C"
+namespace {
+// out[o] = the sum of the `slices` partials of entry o in the workspace (fe_reduce.h), in slice order: the second launch of
+// the split reduction and of the operator gradients.  One registration per element type, whoever launches it.
+template <typename T>
+int launch_reduce_combine(const char* name, const void* workspace, void* out, int64_t n_out, int64_t slices, hipStream_t s) {
+    static PerDeviceOnce once;
+    if (int rc = configured(once, fe::reduce_combine_kernel<T>, name, 0, fe::kRdThreads, 1)) return rc;
+    const dim3 cgrid((unsigned)((n_out + fe::kRdThreads / 64 - 1) / (fe::kRdThreads / 64))), cblock(fe::kRdThreads);
+    hipLaunchKernelGGL((fe::reduce_combine_kernel<T>), cgrid, cblock, 0, s, static_cast<const T*>(workspace),
+                       static_cast<T*>(out), n_out, slices);
+    return FE_OK;
+}
+
+}  // namespace
+extern "C" {
+
 int fe_einsum_reduce(const fe_einsum_desc* d, const void* const* operands, void* out, void* workspace,
                      size_t workspace_bytes, void* stream) {
     if (!operands) return fail(FE_EINVAL, "reduce: null operand array");
@@ -2546,17 +2564,9 @@ int fe_einsum_reduce(const fe_einsum_desc* d, const void* const* operands, void*
 #undef FE_REDUCE_CASE
         FE_HIP_CHECK(hipGetLastError());
     }
-    const dim3 cgrid((unsigned)ceil_div(r.n_out, fe::kRdThreads / 64)), cblock(fe::kRdThreads);
-#define FE_COMBINE_CASE(T, NAME)                                                                                        \
-    do {                                                                                                                \
-        static PerDeviceOnce once;                                                                                      \
-        if (int rc = configured(once, fe::reduce_combine_kernel<T>, NAME, 0, fe::kRdThreads, 1)) return rc;            \
-        hipLaunchKernelGGL((fe::reduce_combine_kernel<T>), cgrid, cblock, 0, s, static_cast<const T*>(workspace),       \
-                           static_cast<T*>(out), r.n_out, r.slices);                                                    \
-    } while (0)
-    if (f64) FE_COMBINE_CASE(double, "reduce combine f64");
-    else FE_COMBINE_CASE(float, "reduce combine f32");
-#undef FE_COMBINE_CASE
+    if (int rc = f64 ? launch_reduce_combine<double>("reduce combine f64", workspace, out, r.n_out, r.slices, s)
+                     : launch_reduce_combine<float>("reduce combine f32", workspace, out, r.n_out, r.slices, s))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
@@ -3037,6 +3047,197 @@ int fe_facemass_adj_f64(const double* J, const double* R, const double* const* g
         if (rc != FE_OK) return rc;
     }
     return FE_OK;
+}
+
+}  // extern "C"
+
+// ---- operator gradients (fe_opgrad.h) ----
+namespace {
+
+constexpr int64_t kOgMinSlice = 64;      // elements: a slice is at least this long (before rounding to 16)
+constexpr int64_t kOgMaxSlices = 1024;   // four resident blocks on each of 256 CUs
+
+// S and the slice length (a multiple of 16 elements) of E elements: E alone decides them.
+void opgrad_slices(int64_t E, int64_t* slices, int64_t* slice_len) {
+    const int64_t S = E <= 0 ? 0 : std::min(kOgMaxSlices, ceil_div(E, kOgMinSlice));
+    *slices = S;
+    *slice_len = S ? ceil_div(ceil_div(E, S), (int64_t)fe::kOgChunk) * fe::kOgChunk : 0;
+}
+
+size_t opgrad_ws_bytes(int64_t slices, int64_t n_out) {
+    return ((size_t)slices * (size_t)n_out * sizeof(double) + kReduceWsAlign - 1) / kReduceWsAlign * kReduceWsAlign;
+}
+
+// the three output strides must lay [n0][n1][n2] out as a dense array in some axis order (axes of extent 1: any stride)
+bool opgrad_dense_layout(const int64_t (&st)[3], const int (&ext)[3]) {
+    int order[3] = {0, 1, 2};
+    std::sort(order, order + 3, [&](int x, int y) { return st[x] < st[y]; });
+    int64_t expect = 1;
+    for (int k : order) {
+        if (ext[k] == 1) continue;
+        if (st[k] != expect) return false;
+        expect *= ext[k];
+    }
+    return true;
+}
+
+int opgrad_check_workspace(const char* what, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (need == 0) return FE_OK;
+    if (!workspace) return fail(FE_EINVAL, "%s: null workspace (fe_opgrad_plan: %zu bytes)", what, need);
+    if (workspace_bytes < need) return fail(FE_EINVAL, "%s: workspace of %zu bytes, the plan needs %zu", what, workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(workspace) % kReduceWsAlign)
+        return fail(FE_EINVAL, "%s: workspace not %zu-byte aligned", what, kReduceWsAlign);
+    return FE_OK;
+}
+
+template <int NM, int NN, bool FACE>
+int launch_opgrad_partial(const fe::OpGradArgs& g, int64_t slices, hipStream_t s) {
+    using G = fe::OpGradGeom<NM, NN, FACE>;
+    const int lds = G::LDS_DOUBLES * (int)sizeof(double);
+    static PerDeviceOnce once;
+    if (int rc = configured(once, fe::opgrad_partial_kernel<NM, NN, FACE>, FACE ? "opgrad partials (face-mass)" : "opgrad partials",
+                            lds, fe::kOgThreads, 4))
+        return rc;
+    hipLaunchKernelGGL((fe::opgrad_partial_kernel<NM, NN, FACE>), dim3((unsigned)slices), dim3(fe::kOgThreads), lds, s, g);
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+// the partial launches of all fields (kOgMaxFields per launch, the later ones adding to their slices), then the combine
+template <typename Launch>
+int opgrad_run(fe::OpGradArgs& g, const double* const* a, const double* const* b, int nb_all, double* out, int64_t slices,
+               hipStream_t s, Launch&& launch) {
+    for (int k0 = 0; k0 < nb_all && slices > 0; k0 += fe::kOgMaxFields) {
+        g.nb = std::min(nb_all - k0, fe::kOgMaxFields);
+        for (int k = 0; k < fe::kOgMaxFields; ++k) {
+            g.a[k] = k < g.nb ? a[k0 + k] : nullptr;
+            g.b[k] = k < g.nb ? b[k0 + k] : nullptr;
+        }
+        g.accumulate = k0 > 0 ? 1 : 0;
+        if (int rc = launch(g)) return rc;
+    }
+    if (int rc = launch_reduce_combine<double>("reduce combine f64", g.ws, out, g.n_out, slices, s)) return rc;
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fe_opgrad_plan(int64_t E, int32_t n_out_entries, int64_t* slices, size_t* workspace_bytes) {
+    if (E < 0) return fail(FE_EINVAL, "opgrad plan: E must be >= 0 (got %lld)", (long long)E);
+    if (n_out_entries < 1) return fail(FE_EINVAL, "opgrad plan: %d output entries", n_out_entries);
+    if (!slices || !workspace_bytes) return fail(FE_EINVAL, "opgrad plan: null pointer");
+    int64_t len;
+    opgrad_slices(E, slices, &len);
+    *workspace_bytes = opgrad_ws_bytes(*slices, n_out_entries);
+    return FE_OK;
+}
+
+int fe_opgrad_f64(const double* J, const double* const* a, const double* const* b, double* out, int64_t E, int32_t nb,
+                  int32_t X, int32_t R, int32_t Np, int64_t jx, int64_t jr, int64_t je, int64_t sr, int64_t sp,
+                  int64_t sq, void* workspace, size_t workspace_bytes, void* stream) {
+    if (E < 0) return fail(FE_EINVAL, "opgrad: E must be >= 0 (got %lld)", (long long)E);
+    if (nb < 1) return fail(FE_EINVAL, "opgrad: nb=%d, need at least one field", nb);
+    if (X < 1 || X > 3 || R < 1 || R > 3) return fail(FE_EUNSUPPORTED, "opgrad: X = %d, R = %d not compiled (1..3)", X, R);
+    switch (Np) {
+        case 3: case 4: case 6: case 10: case 15: case 20: case 21: case 35: break;
+        default: return fail(FE_EUNSUPPORTED, "opgrad: Np = %d not compiled (3, 4, 6, 10, 15, 20, 21, 35)", Np);
+    }
+    if (!a || !b || !out || (E > 0 && !J)) return fail(FE_EINVAL, "opgrad: null pointer");
+    if (!aligned8(J) || !aligned8(out)) return fail(FE_EINVAL, "opgrad: device pointers must be 8-byte aligned (float64 arrays)");
+    for (int k = 0; k < nb; ++k) {
+        if (E > 0 && (!a[k] || !b[k])) return fail(FE_EINVAL, "opgrad: null device pointer (field %d)", k);
+        if (!aligned8(a[k]) || !aligned8(b[k])) return fail(FE_EINVAL, "opgrad: device pointers must be 8-byte aligned (float64 arrays)");
+    }
+    if (jx < 0 || jr < 0 || je < 0) return fail(FE_EINVAL, "opgrad: negative J stride");
+    const int64_t st[3] = {sr, sp, sq};
+    const int ext[3] = {R, Np, Np};
+    if (!opgrad_dense_layout(st, ext))
+        return fail(FE_EINVAL, "opgrad: output strides (%lld, %lld, %lld) are no dense layout of [%d][%d][%d]", (long long)sr,
+                    (long long)sp, (long long)sq, R, Np, Np);
+    if (E * (int64_t)Np * X >= (int64_t)1 << 39) return fail(FE_EINVAL, "opgrad: E too large");
+    int64_t slices, slice_len;
+    opgrad_slices(E, &slices, &slice_len);
+    const int64_t n_out = (int64_t)R * Np * Np;
+    if (int rc = opgrad_check_workspace("opgrad", workspace, workspace_bytes, opgrad_ws_bytes(slices, n_out))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    fe::OpGradArgs g = {};
+    g.J = J, g.ws = static_cast<double*>(workspace);
+    g.E = E, g.slice_len = slice_len, g.n_out = n_out;
+    g.jx = jx, g.jr = jr, g.je = je, g.sr = sr, g.sp = sp, g.sq = sq;
+    g.X = X, g.R = R;
+    return opgrad_run(g, a, b, nb, out, slices, s, [&](const fe::OpGradArgs& ga) {
+        switch (Np) {
+            case 3: return launch_opgrad_partial<3, 3, false>(ga, slices, s);
+            case 4: return launch_opgrad_partial<4, 4, false>(ga, slices, s);
+            case 6: return launch_opgrad_partial<6, 6, false>(ga, slices, s);
+            case 10: return launch_opgrad_partial<10, 10, false>(ga, slices, s);
+            case 15: return launch_opgrad_partial<15, 15, false>(ga, slices, s);
+            case 20: return launch_opgrad_partial<20, 20, false>(ga, slices, s);
+            case 21: return launch_opgrad_partial<21, 21, false>(ga, slices, s);
+            default: return launch_opgrad_partial<35, 35, false>(ga, slices, s);
+        }
+    });
+}
+
+int fe_facemass_opgrad_f64(const double* J, const double* const* g, const double* const* v, double* dR, int64_t E,
+                           int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (E < 0) return fail(FE_EINVAL, "facemass opgrad: E must be >= 0 (got %lld)", (long long)E);
+    if (b < 1) return fail(FE_EINVAL, "facemass opgrad: b=%d, need at least one field", b);
+    if (layout_flags & ~(FE_FM_J_FE | FE_FM_R_IFJ | FE_FM_R_T))
+        return fail(FE_EINVAL, "facemass opgrad: bad layout flags %d", layout_flags);
+    int kind = -1;   // compiled shapes
+    if (nf == 4 && Np == 4 && Nfp == 3) kind = 0;
+    else if (nf == 4 && Np == 10 && Nfp == 6) kind = 1;
+    else if (nf == 4 && Np == 20 && Nfp == 10) kind = 2;
+    else if (nf == 4 && Np == 35 && Nfp == 15) kind = 3;
+    else if (nf == 3 && Np == 3 && Nfp == 2) kind = 4;
+    else if (nf == 3 && Np == 6 && Nfp == 3) kind = 5;
+    else if (nf == 3 && Np == 10 && Nfp == 4) kind = 6;
+    else if (nf == 3 && Np == 15 && Nfp == 5) kind = 7;
+    else if (nf == 3 && Np == 21 && Nfp == 6) kind = 8;
+    if (kind < 0)
+        return fail(FE_EUNSUPPORTED, "facemass opgrad: (nf, Np, Nfp) = (%d, %d, %d) not compiled", nf, Np, Nfp);
+    if (!g || !v || !dR || (E > 0 && !J)) return fail(FE_EINVAL, "facemass opgrad: null pointer");
+    if (!aligned8(J) || !aligned8(dR)) return fail(FE_EINVAL, "facemass opgrad: device pointers must be 8-byte aligned");
+    for (int k = 0; k < b; ++k) {
+        if (E > 0 && (!g[k] || !v[k])) return fail(FE_EINVAL, "facemass opgrad: null device pointer (field %d)", k);
+        if (!aligned8(g[k]) || !aligned8(v[k])) return fail(FE_EINVAL, "facemass opgrad: device pointers must be 8-byte aligned");
+    }
+    if (E * (int64_t)Np * b >= (int64_t)1 << 39) return fail(FE_EINVAL, "facemass opgrad: E too large");
+    int64_t slices, slice_len;
+    opgrad_slices(E, &slices, &slice_len);
+    const int64_t n_out = (int64_t)nf * Np * Nfp;
+    if (int rc = opgrad_check_workspace("facemass opgrad", workspace, workspace_bytes, opgrad_ws_bytes(slices, n_out))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // dR's strides of (f, i, j): 'fij', 'ifj', 'fji', 'jfi' (as the face-mass kernels read R)
+    const int rl = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) | ((layout_flags & FE_FM_R_T) ? 2 : 0);
+    const int sF = rl == 0 ? Np * Nfp : rl == 1 ? Nfp : rl == 2 ? Nfp * Np : Np;
+    const int sI = rl == 0 ? Nfp : rl == 1 ? nf * Nfp : 1;
+    const int sJ = rl == 0 || rl == 1 ? 1 : rl == 2 ? Np : nf * Np;
+    const bool jfe = (layout_flags & FE_FM_J_FE) != 0;
+    fe::OpGradArgs a = {};
+    a.J = J, a.ws = static_cast<double*>(workspace);
+    a.E = E, a.slice_len = slice_len, a.n_out = n_out;
+    a.jx = 0, a.jr = jfe ? E : 1, a.je = jfe ? 1 : nf;
+    a.sr = sF, a.sp = sJ, a.sq = sI;   // rows of the tiles are j (the planes of v), columns i (g)
+    a.X = 1, a.R = nf;
+    return opgrad_run(a, g, v, b, dR, slices, s, [&](const fe::OpGradArgs& ga) {
+        switch (kind) {
+            case 0: return launch_opgrad_partial<3, 4, true>(ga, slices, s);
+            case 1: return launch_opgrad_partial<6, 10, true>(ga, slices, s);
+            case 2: return launch_opgrad_partial<10, 20, true>(ga, slices, s);
+            case 3: return launch_opgrad_partial<15, 35, true>(ga, slices, s);
+            case 4: return launch_opgrad_partial<2, 3, true>(ga, slices, s);
+            case 5: return launch_opgrad_partial<3, 6, true>(ga, slices, s);
+            case 6: return launch_opgrad_partial<4, 10, true>(ga, slices, s);
+            case 7: return launch_opgrad_partial<5, 15, true>(ga, slices, s);
+            default: return launch_opgrad_partial<6, 21, true>(ga, slices, s);
+        }
+    });
 }
 
 }  // extern "C"

@@ -26,7 +26,8 @@ Argument conventions kept from the reference:
                contractions on the matrix cores, ``feinsum_amd.contraction``; ``"reduction"``: a long summation
                space summed into a small output as a split reduction over the whole chip,
                ``feinsum_amd.reduction``; ``"adjoint"``: the adjoint kernels of the DG families, for the einsums
-               ``family.match_adjoint_family`` recognises only); in a dict, ``"prepared": True`` lets a
+               ``family.match_adjoint_family`` recognises only; ``"operator_adjoint"``: the
+               operator-gradient kernels, for the einsums ``family.match_operator_adjoint`` recognises only); in a dict, ``"prepared": True`` lets a
                bound launch (``timeit``) use a prepared copy of its operator
                matrices; ``"placement"`` (or ``$FEINSUM_PLACEMENT``): ``timeit``
                allocates one array per operand as the reference does; with the
@@ -63,7 +64,7 @@ from feinsum_amd.einsum import INT_CLASSES, BatchedEinsum, SizeParam
 from feinsum_amd.adjoint import AdjointLaunch
 from feinsum_amd.family import (FAMILY_DIV, FAMILY_DIVCOMP, FAMILY_FACEMASS, FAMILY_GRAD,
                                 FAMILY_GRADPLANES, FAMILY_MATAPPLY, OP_J_ES, KernelPlan,
-                                match_adjoint_family, match_family)
+                                match_adjoint_family, match_family, match_operator_adjoint)
 
 logger = logging.getLogger(__name__)
 
@@ -516,7 +517,9 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     ``contraction.auto_picks_contraction`` says the contraction kernel wins), ``"family"`` (a DG family kernel) or
     ``"generic"`` (also the ``"generic"`` transform on float64 grad / div / div components of triangles, which have no
     plain kernel of their own).  The reduction rule is checked before the contraction rule.  ``"adjoint"`` (that transform only: an
-    einsum that ``family.match_adjoint_family`` recognises, else ``NotImplementedError``) runs the adjoint kernels.
+    einsum that ``family.match_adjoint_family`` recognises, else ``NotImplementedError``) runs the adjoint kernels, and
+    ``"operator_adjoint"`` (that transform only: ``family.match_operator_adjoint``, else ``NotImplementedError``) the
+    operator-gradient kernels.
     """
     variant = _variant_from_transform(transform)
     if variant == "adjoint":
@@ -525,6 +528,12 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
                 f"einsum '{einsum.get_subscripts()}' is not one of the adjoint kernels' shapes"
                 " (feinsum_amd.family.match_adjoint_family)")
         return "adjoint"
+    if variant == "operator_adjoint":
+        if match_operator_adjoint(einsum) is None:
+            raise NotImplementedError(
+                f"transform 'operator_adjoint': einsum '{einsum.get_subscripts()}' is not an operator gradient of a DG"
+                " family at a compiled size (feinsum_amd.family.match_operator_adjoint)")
+        return "operator_adjoint"
     if variant == "contraction":
         return "contraction"
     if variant == "reduction":
@@ -583,6 +592,9 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
         bound = ReductionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
     elif kind == "adjoint":
         bound = AdjointLaunch(match_adjoint_family(einsum), einsum, arg_dict, outs)
+    elif kind == "operator_adjoint":
+        with torch.cuda.device(q.torch_device):
+            bound = AdjointLaunch(match_operator_adjoint(einsum), einsum, arg_dict, outs, stream=q.stream)
     elif kind == "family":
         bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform))
         if _prepared_from_transform(transform, prepare):

@@ -596,6 +596,34 @@ int fe_facemass_adj_f64(const double* J, const double* R, const double* const* g
                         double* const* dv, double* dJ, int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
                         int32_t layout_flags, void* stream);
 
+/* ---- operator gradients of the DG families (feinsum_amd/csrc/fe_opgrad.h) ----
+ *
+ * The element axis is summed on the matrix cores into the operator's shape:
+ *   out[r * sr + p * sp + q * sq] = sum_k sum_e (sum_x J[x * jx + r * jr + e * je] * b_k[x][e][p]) * a_k[e][q]
+ * for 0 <= r < R, 0 <= p, q < Np, over nb >= 1 field pairs (a_k [E][Np], b_k [X][E][Np]) that share J, summed in their
+ * order.  b carries the X planes (grad: the output gradient, div: the field; X = 1 for the div component and the
+ * element-local operator).  (sr, sp, sq) must lay [R][Np][Np] out densely in some axis order (FE_EINVAL otherwise);
+ * the J strides cover 'xre', 're', 'er' and 'e'.  Shapes as fe_geomadj_f64, else FE_EUNSUPPORTED.
+ *
+ * E is cut into S slices (fe_opgrad_plan: S = min(1024, ceil(E / 64)), E alone decides it); every slice writes its
+ * partial output into its own part of `workspace`, and a second launch sums the slices of every entry in a fixed
+ * order: no atomics, bitwise reproducible across runs, streams and graph replays.  The workspace holds
+ * S * entries * 8 bytes rounded up to a multiple of 256 and must be 256-byte aligned: null, short or misaligned is
+ * FE_EINVAL before any device work (a plan of 0 bytes takes any pointer).  It is overwritten; nothing is allocated.
+ * Every output entry is written; E == 0 writes zeros and reads nothing.  Asynchronous on `stream`. */
+int fe_opgrad_plan(int64_t E, int32_t n_out_entries, int64_t* slices, size_t* workspace_bytes);   /* host only */
+int fe_opgrad_f64(const double* J, const double* const* a, const double* const* b, double* out, int64_t E, int32_t nb,
+                  int32_t X, int32_t R, int32_t Np, int64_t jx, int64_t jr, int64_t je, int64_t sr, int64_t sp,
+                  int64_t sq, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The gradient of face-mass with respect to R, for b fields that share J (layout_flags: FE_FM_* as fe_facemass_f64):
+ *   dR[f, i, j] = sum_k sum_e g_k[e][i] * (J[e, f] * v_k[f][e][j])
+ * dR has R's layout ('fij', 'ifj', 'fji', 'jfi'), J is 'ef' or 'fe'; the fields are summed in their order.  Shapes as
+ * fe_facemass_adj_f64; workspace (entries = nf * Np * Nfp), errors and reproducibility as fe_opgrad_f64. */
+int fe_facemass_opgrad_f64(const double* J, const double* const* g, const double* const* v, double* dR, int64_t E,
+                           int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

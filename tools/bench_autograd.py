@@ -1,6 +1,7 @@
 """The adjoint kernels against the routes these einsums had before -- "auto" (the generic kernel) and
-"contraction" (the optimal schedule as strided contractions) -- in the same process, and the forward + backward time of
-evaluate_differentiable.  One JSON line per (case, E, route).
+"contraction" (the optimal schedule as strided contractions) -- in the same process, the operator-gradient kernels
+(transform "operator_adjoint") against "auto", and the forward + backward time of evaluate_differentiable under both
+settings of operator_gradients.  One JSON line per (case, E, route).
     python tools/bench_autograd.py [--E 100000 1000000] [--reps N]
 
 Seconds per launch by HIP events over --reps back-to-back launches after a warm-up launch, float64, tetrahedra p = 4.
@@ -104,8 +105,21 @@ def main():
              roofline=1304 * E / BW / (best + bestj))
         emit(case="facemass_adj_dJ", E=E, speedup_vs_best_existing=(best + bestj) / fused)
         del args, argsj, dv, dJ
+        # operator gradients: dD 'xre,ej,xei->rij' and dR 'ef,fej,ei->fij' (b = 4, a launch per row under both transforms)
+        for case, fwd_e, wrt, nbytes in (("opgrad_d", C.grad(3, NP), "D", 1192),
+                                         ("opgrad_r_b4", C.face_mass(NP, NF, NFP, 4), "R", 8 * (4 * (NP + NF * NFP) + NF))):
+            (term,) = adjoint_einsums(fwd_e, wrt)
+            args = device_inputs(term, E, 4)
+            per = {}
+            for route in ("operator_adjoint", "auto"):
+                per[route] = bound_seconds(term, args, route, a.reps if route == "operator_adjoint" else a.old_reps)
+                emit(case=case, einsum=term.get_subscripts(), E=E, route=route, seconds=per[route],
+                     roofline=nbytes * E / BW / per[route])
+            emit(case=case, E=E, speedup_vs_auto=per["auto"] / per["operator_adjoint"])
+            del args
         # forward + backward of evaluate_differentiable
-        for name, ein in (("grad", C.grad(3, NP)), ("facemass_b4", C.face_mass(NP, NF, NFP, 4))):
+        for name, ein, og in [(n, e, og) for n, e in (("grad", C.grad(3, NP)), ("facemass_b4", C.face_mass(NP, NF, NFP, 4)))
+                              for og in ("auto", "kernel")]:
             dev = device_inputs(ein, E, 3)
             for t in dev.values():
                 t.requires_grad_(True)
@@ -114,12 +128,13 @@ def main():
             def step():
                 for t in dev.values():
                     t.grad = None
-                outs = evaluate_differentiable(ein, 0, dev)
+                outs = evaluate_differentiable(ein, 0, dev, operator_gradients=og)
                 torch.autograd.backward([outs[n] for n in ein.output_names], gbar)
 
             fwd = seconds(lambda: evaluate_differentiable(ein, 0, {n: t.detach() for n, t in dev.items()}), a.reps)
             both = seconds(step, max(3, a.reps // 4))
-            emit(case=f"{name} forward + backward (all inputs)", E=E, forward_seconds=fwd, forward_backward_seconds=both)
+            emit(case=f"{name} forward + backward (all inputs)", operator_gradients=og, E=E, forward_seconds=fwd,
+                 forward_backward_seconds=both)
             del dev
         torch.cuda.empty_cache()
     emit(device=f.DeviceQueue(0).device.name)
