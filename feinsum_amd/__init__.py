@@ -22,14 +22,14 @@ from feinsum_amd.canonicalization import canonicalize_einsum
 from feinsum_amd.sql_utils import (QueryInfo, get_timed_einsums_in_db, query, query_reference_archive, record_facts,
                                    retrieve)
 from feinsum_amd.operator import BoundOperator, bind_operator, evaluate_operator
-from feinsum_amd.measure import (DeviceQueue, evaluate, generate_input_arrays, generate_out_arrays,
+from feinsum_amd.measure import (DeviceQueue, accumulate_route, evaluate, generate_input_arrays, generate_out_arrays,
                                  get_roofline_flop_rate, measure_giga_op_rate,
                                  stringify_comparison_vs_roofline, timeit, timeit_details,
                                  validate_batched_einsum_transform)
 from feinsum_amd.autograd import adjoint_einsums, evaluate_differentiable
 
 __all__ = (
-    "AdjointPlan", "adjoint_einsums", "evaluate_differentiable", "match_adjoint_family", "match_operator_adjoint",
+    "AdjointPlan", "accumulate_route", "adjoint_einsums", "evaluate_differentiable", "match_adjoint_family", "match_operator_adjoint",
     "Array", "BatchedEinsum", "BoundOperator", "ContractionSchedule", "DeviceQueue", "EinsumAxisAccess",
     "EinsumTunitMatchError", "FakeCLDevice", "FreeAxis", "HipLibraryError", "InvalidParameterError", "KernelPlan",
     "NoDevicePeaksInfoError", "NoFactInDatabaseError", "QueryInfo", "SizeParam", "SummationAxis",

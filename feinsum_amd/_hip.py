@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "fe_split_alloc", "fe_split_free", "fe_split_info", "fe_split_stats", "fe_split_reserve", "fe_split_trim", "fe_launch_f32", "fe_set_tail_rounds", "fe_set_tail_min_rounds",
     "fe_set_cu_limit", "fe_set_phase_priority_p5", "fe_set_div_interleave", "fe_set_div_quarter_tail", "fe_set_grad_quarter_tail", "fe_set_grad_staggered_start", "fe_last_launch_info", "fe_stream_retired", "fe_capture_id", "fe_graph_retired", "fe_tail_stats", "fe_tail_check", "fe_tail_plant", "fe_set_temporal_loads_mib", "fe_set_write_through_mib",
     "fe_geomadj_f64", "fe_facemass_adj_f64", "fe_opgrad_plan", "fe_opgrad_f64", "fe_facemass_opgrad_f64",
+    "fe_facemass_acc_f64", "fe_axpby",
 )
 FAMILY_F32 = 0x100    # FE_FAMILY_F32
 
@@ -270,6 +271,12 @@ def load_library() -> C.CDLL:
     lib.fe_facemass_opgrad_f64.restype = C.c_int
     lib.fe_facemass_opgrad_f64.argtypes = ([C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64]
                                            + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p])
+    lib.fe_facemass_acc_f64.restype = C.c_int
+    lib.fe_facemass_acc_f64.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                        C.c_void_p]
+    lib.fe_axpby.restype = C.c_int
+    lib.fe_axpby.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_void_p]
     _lib = lib
     return lib
 
@@ -390,6 +397,22 @@ def facemass(J: int, R: int, v: Sequence[int], out: Sequence[int], E: int, Np: i
         raise InvalidParameterError("face-mass: need as many outputs as fields")
     check(load_library().fe_facemass_f64(J, R, _ptr_array(v), _ptr_array(out), E, Np, nf, Nfp,
                                          len(v), layout_flags, variant_code(variant), stream))
+
+
+def facemass_acc(J: int, R: int, v: Sequence[int], out: Sequence[int], E: int, Np: int, nf: int, Nfp: int,
+                 alpha: float, beta: float, layout_flags: int = 0, stream: int = 0) -> None:
+    """``out_k <- alpha * facemass_k + beta * out_k`` (fe_facemass_acc_f64).  NotImplementedError: the shape has no fused
+    kernel (tetrahedra p = 1..4, two or more fields)."""
+    if len(v) != len(out):
+        raise InvalidParameterError("face-mass: need as many outputs as fields")
+    check(load_library().fe_facemass_acc_f64(J, R, _ptr_array(v), _ptr_array(out), E, Np, nf, Nfp, len(v), layout_flags,
+                                             float(alpha), float(beta), stream))
+
+
+def axpby(out: int, x: int, n: int, alpha: float, beta: float, float64: bool = True, stream: int = 0) -> None:
+    """``out[i] <- alpha * x[i] + beta * out[i]`` over *n* contiguous entries (fe_axpby); ``beta == 0`` does not read *out*."""
+    check(load_library().fe_axpby(out, x, int(n), float(alpha), float(beta), FE_DTYPE_F64 if float64 else FE_DTYPE_F32,
+                                  stream))
 
 
 def geomadj(D: int, a: int, b: int, out: int, E: int, X: int, R: int, Np: int, strides: Sequence[int],

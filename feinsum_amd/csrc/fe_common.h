@@ -164,6 +164,14 @@ __device__ __forceinline__ void store_tile_held(double* op, int lane, const v2d 
     }
 }
 
+// The combine of an accumulating launch, out <- alpha x + beta old, spelled ONCE so that every route (the face-mass kernel's
+// store path, its remainder code, fe_axpby) rounds alike: the product beta old, then one fused multiply-add -- two roundings,
+// none when alpha and beta are signed powers of two.  Callers skip it (and the load of `old`) when beta == 0.
+template <typename T>
+__device__ __forceinline__ T axpby_combine(T alpha, T x, T beta, T old) {
+    return __builtin_elementwise_fma(alpha, x, beta * old);
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");

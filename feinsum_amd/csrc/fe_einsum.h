@@ -99,6 +99,35 @@ __global__ __launch_bounds__(256) void einsum_pointwise_kernel(fe_einsum_ptrs op
     }
 }
 
+// out <- alpha x + beta out over n contiguous entries (fe_axpby: the second pass of an accumulating evaluation whose kernel
+// has no accumulating form).  A stream like the one above: 16 bytes per lane and iteration where out and x sit alike within
+// 16 bytes -- a scalar head up to the first 16-byte boundary, a scalar tail behind the last whole vector -- and entry by entry
+// where they do not.  beta == 0 does not read out.  The combine is axpby_combine (fe_common.h), as in the face-mass kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void axpby_kernel(T* __restrict__ out, const T* __restrict__ x, int64_t n, T alpha, T beta) {
+    constexpr int W = 16 / (int)sizeof(T);
+    typedef T vw __attribute__((ext_vector_type(W)));
+    const uintptr_t ao = reinterpret_cast<uintptr_t>(out) & 15, ax = reinterpret_cast<uintptr_t>(x) & 15;
+    const bool alike = ao == ax;
+    int64_t head = alike ? (int64_t)(((16 - ao) & 15) / sizeof(T)) : n;
+    head = head < n ? head : n;
+    const int64_t vecs = (n - head) / W;
+    const int64_t stride = (int64_t)gridDim.x * 256, t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool reads = beta != T(0);
+    vw av, bv;
+    for (int w = 0; w < W; ++w) { av[w] = alpha; bv[w] = beta; }
+    for (int64_t q = t0; q < vecs; q += stride) {
+        vw* o = reinterpret_cast<vw*>(out + head) + q;
+        const vw xv = __builtin_nontemporal_load(reinterpret_cast<const vw*>(x + head) + q);
+        const vw r = reads ? axpby_combine(av, xv, bv, __builtin_nontemporal_load(o)) : av * xv;
+        __builtin_nontemporal_store(r, o);
+    }
+    for (int64_t i = t0; i < n - vecs * W; i += stride) {   // the head, then the tail
+        const int64_t e = i < head ? i : i + vecs * W;
+        out[e] = reads ? axpby_combine(alpha, x[e], beta, out[e]) : alpha * x[e];
+    }
+}
+
 // The pointwise stream of a float64 einsum with float32 operands (bit p of f32_mask: operand p is float32): pairs of
 // 16 bytes (float64) or 8 bytes (float32) per operand, each operand aligned to its own pair size.
 __global__ __launch_bounds__(256) void einsum_pointwise_mixed_kernel(fe_einsum_ptrs ops, int n_operands,

@@ -44,6 +44,7 @@ struct FmGeom {
     static constexpr int SUB_CHUNKS = SUB_D / 2, SUB_INSTR = (SUB_CHUNKS + 63) / 64;
     static constexpr int UNIT_LOADS = NF * SLAB_INSTR;   // + J_INSTR at a tile start
     static constexpr int UNIT_STORES = M * SUB_INSTR;
+    static constexpr int ACC_LOADS = UNIT_STORES;        // kAcc: a unit reads every 16-byte chunk it is about to write
     static_assert(!W8 || (ALDS && M == 1 && UNIT_D >= SUB_D), "eight-wave blocks: A in LDS, o inside the slab buffer");
     struct WaveLds {
         double v[W8 ? 1 : 2][UNIT_D];   // ring of field slabs: v[slot][f][e][j]
@@ -59,7 +60,7 @@ struct FmGeom {
     static constexpr int LDS_BYTES = (WAVE_BYTES > OP_D * 8 ? WAVE_BYTES : OP_D * 8) + AFR_D * 8;
     static constexpr int BLOCKS_PER_CU = ALDS ? 1 : 2;
     static_assert((TEL * NFP) % 2 == 0, "slabs are moved in 16-byte chunks");
-    static_assert(2 * UNIT_STORES + UNIT_LOADS + J_INSTR <= 60, "counted vmcnt must fit the 6-bit field");
+    static_assert(2 * UNIT_STORES + ACC_LOADS + UNIT_LOADS + J_INSTR <= 60, "counted vmcnt must fit the 6-bit field");
     static_assert(BLOCKS_PER_CU * LDS_BYTES <= 160 * 1024, "blocks per CU");
 };
 
@@ -112,14 +113,22 @@ __device__ __forceinline__ void fm_issue_unit_loads(const double* __restrict__ J
 // kDyn (register fragments, NB >= 3): behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk): the
 // ticket for the next tile is asked for with unit 0 of a tile and read with unit NB - 2, whose prefetch is the next tile's
 // first unit; `tail` = the launch's counters (null: static walk), `t_static` = statically walked tiles.
+// kAcc (register fragments, static walk, plain operator): out_k <- alpha (the sum above) + beta out_k (axpby_combine).  With
+// beta != 0 a unit reads the 16-byte chunks it is about to write -- every chunk by the lane that stores it, so nothing has to be
+// ordered across waves -- into registers, by plain loads issued behind the unit's B fragments and IN FRONT OF the prefetch of
+// unit m + 2: what is younger than them at the store is that prefetch alone.  The loads are the compiler's own, so it places
+// its own wait in front of their first use (it does not see the LDS-DMA prefetch and waits for that too: DESIGN.md 3m); the
+// counted wait at the top of a unit counts them (ACC_LOADS) among the operations younger than the unit's own loads.  With
+// beta == 0 nothing is read: one scalar branch per unit.  The remainder code accumulates alike.
 template <int NP, int NFP, int M, int NB, int NF = kFmNf, bool ALDS = false, bool W8 = false, bool kPrep = false,
-          bool kDyn = false>
+          bool kDyn = false, bool kAcc = false>
 __device__ __forceinline__ void facemass_mfma_body(
     const double* __restrict__ J, const double* __restrict__ R, const void* __restrict__ prep, const FieldPtrs& P,
     int64_t E, int64_t nTiles, int jfe_flags, int rlayout, const unsigned bid, const unsigned nblk,
-    unsigned* __restrict__ tail = nullptr, int64_t t_static = 0) {
+    unsigned* __restrict__ tail = nullptr, int64_t t_static = 0, const double alpha = 1.0, const double beta = 0.0) {
     const int jfe = jfe_flags & 1;   // J stored [nf][E]; bit kOpLoadsTemporal: the field slabs by plain loads (fe_common.h)
     static_assert(!kPrep || !ALDS, "prepared operators: fragments in registers");
+    static_assert(!kAcc || (!ALDS && !W8 && !kPrep && !kDyn), "accumulating launches: register fragments, static walk");
     static_assert(!kDyn || (NB >= 3 && !ALDS && !W8 && !kPrep) || (NB >= 2 && ALDS && W8),
                   "dynamic walk: three or more fields with the fragments in registers, or the eight-wave blocks (p = 5)");
     using G = FmGeom<NP, NFP, M, NF, ALDS, W8>;
@@ -153,7 +162,7 @@ __device__ __forceinline__ void facemass_mfma_body(
         const int rI = rlayout == 0 ? NFP : rlayout == 1 ? NF * NFP : 1;
         const int rJ = rlayout == 0 || rlayout == 1 ? 1 : rlayout == 2 ? NP : NF * NP;
         remainder_items(nTiles * G::TEL, E, NP, bid, nblk, [&](int64_t e, int i) {
-            facemass_item<NB>(J, Rsrc, P, E, NP, NF, NFP, jEs, jFs, rF, rI, rJ, e, i);
+            facemass_item<NB, kAcc>(J, Rsrc, P, E, NP, NF, NFP, jEs, jFs, rF, rI, rJ, e, i, alpha, beta);
         });
     };
     bool first_requested = false;   // (units 0 and 1 of this wave's first tile: see the staged prologue)
@@ -357,6 +366,7 @@ __device__ __forceinline__ void facemass_mfma_body(
     unsigned* const counter = tail_pool_counters(tail, pool);
     unsigned* const done = tail_pool_reports(counter);
     bool reported = false;
+    const bool acc_reads = kAcc && beta != 0.0;   // wave-uniform (a kernel argument)
     int64_t tile = first;
     while (tile < tEnd) {
         balance_priority(younger_half, iteration++);
@@ -366,10 +376,14 @@ __device__ __forceinline__ void facemass_mfma_body(
         bool requested = false;
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
-            // ---- wait for this unit's loads; younger ops: S(m-2), [the ticket asked for in unit m-1,] L(m+1), S(m-1)
+            // ---- wait for this unit's loads; younger ops: S(m-2), [the ticket asked for in unit m-1,] [kAcc: the old values
+            //      O(m-1),] L(m+1), S(m-1)
             const bool next_is_tile_start = (k + 1 == NB);
             const bool has_next = !next_is_tile_start || (nt < tEnd);
-            if (warm && has_next) {
+            if (kAcc && acc_reads && warm && has_next) {
+                if (next_is_tile_start) wait_vmcnt<2 * G::UNIT_STORES + G::ACC_LOADS + G::UNIT_LOADS + G::J_INSTR>();
+                else wait_vmcnt<2 * G::UNIT_STORES + G::ACC_LOADS + G::UNIT_LOADS>();
+            } else if (warm && has_next) {
                 if (next_is_tile_start) wait_vmcnt<2 * G::UNIT_STORES + G::UNIT_LOADS + G::J_INSTR>();
                 else if (kDyn && k == 1 && requested) wait_vmcnt<2 * G::UNIT_STORES + G::UNIT_LOADS + 1>();
                 else wait_vmcnt<2 * G::UNIT_STORES + G::UNIT_LOADS>();
@@ -413,6 +427,22 @@ __device__ __forceinline__ void facemass_mfma_body(
                     if (x < 0) {   // this wave's pool is empty: stop asking, report
                         tail_request<1>(done);
                         reported = true;
+                    }
+                }
+            }
+            // ---- kAcc: the chunks this unit will overwrite, ahead of the prefetch (see the head of this function)
+            v2d old[kAcc ? M : 1][kAcc ? G::SUB_INSTR : 1];
+            if constexpr (kAcc) {
+                if (acc_reads) {
+#pragma unroll
+                    for (int m = 0; m < M; ++m) {
+                        const double* op = P.out[k] + (tile * G::TEL + 16 * m) * NP;
+#pragma unroll
+                        for (int c = 0; c < G::SUB_INSTR; ++c) {
+                            const int qc = c * 64 + lane;
+                            if ((c + 1) * 64 <= G::SUB_CHUNKS || qc < G::SUB_CHUNKS)
+                                old[m][c] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(op + 2 * qc));
+                        }
                     }
                 }
             }
@@ -467,7 +497,11 @@ __device__ __forceinline__ void facemass_mfma_body(
                 for (int c = 0; c < G::SUB_INSTR; ++c) {
                     const int qc = c * 64 + lane;
                     if ((c + 1) * 64 <= G::SUB_CHUNKS || qc < G::SUB_CHUNKS) {
-                        const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * tile_dst_chunk<NP>(qc));
+                        v2d val = *reinterpret_cast<const v2d*>(ob + 2 * tile_dst_chunk<NP>(qc));
+                        if constexpr (kAcc) {
+                            if (acc_reads) val = axpby_combine(v2d{alpha, alpha}, val, v2d{beta, beta}, old[m][c]);
+                            else val = v2d{alpha, alpha} * val;
+                        }
                         __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * qc));
                     }
                 }
@@ -507,6 +541,15 @@ __global__ __launch_bounds__(256, 2) FE_TAIL_KERNEL_ATTR void facemass_mfma_tail
     unsigned* __restrict__ tail, int64_t t_static) {
     facemass_mfma_body<NP, NFP, M, NB, NF, false, false, false, true>(J, R, nullptr, P, E, nTiles, jfe, rlayout, blockIdx.x,
                                                                       gridDim.x, tail, t_static);
+}
+
+// out_k <- alpha (the face-mass sum) + beta out_k: tetrahedra p = 1..4, 2..4 fields, static walk (facemass_mfma_body, kAcc)
+template <int NP, int NFP, int M, int NB>
+__global__ __launch_bounds__(256, 2) void facemass_mfma_acc_kernel(
+    const double* __restrict__ J, const double* __restrict__ R, FieldPtrs P, int64_t E, int64_t nTiles, int jfe, int rlayout,
+    double alpha, double beta) {
+    facemass_mfma_body<NP, NFP, M, NB, kFmNf, false, false, false, false, true>(J, R, nullptr, P, E, nTiles, jfe, rlayout,
+                                                                                blockIdx.x, gridDim.x, nullptr, 0, alpha, beta);
 }
 
 template <int NP, int NFP, int M, int NB, int NF = kFmNf, bool ALDS = false, bool W8 = false, bool kPrep = false>

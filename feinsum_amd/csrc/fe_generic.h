@@ -142,10 +142,12 @@ __global__ __launch_bounds__(256) void matapply_generic_kernel(
 
 // face-mass: out_k[e,i] = sum_{f,j} J[e,f] R[f,i,j] v_k[f,e,j]
 //   jEs / jFs : strides of J along e and f;  rF / rI / rJ : strides of R along f, i and j
-template <int NB>
+// kAcc: out_k[e,i] = alpha * (that sum) + beta * out_k[e,i]; beta == 0 does not read the output (axpby_combine, fe_common.h)
+template <int NB, bool kAcc = false>
 __device__ __forceinline__ void facemass_item(const double* __restrict__ J, const double* __restrict__ R,
                                               const FieldPtrs& P, int64_t E, int Np, int nf, int Nfp, int64_t jEs,
-                                              int64_t jFs, int rF, int rI, int rJ, int64_t e, int i) {
+                                              int64_t jFs, int rF, int rI, int rJ, int64_t e, int i, double alpha = 1.0,
+                                              double beta = 0.0) {
     double acc[NB];
 #pragma unroll
     for (int k = 0; k < NB; ++k) acc[k] = 0.0;
@@ -160,8 +162,16 @@ __device__ __forceinline__ void facemass_item(const double* __restrict__ J, cons
             for (int k = 0; k < NB; ++k) acc[k] += w * P.v[k][vo + j];
         }
     }
+    if constexpr (kAcc) {
 #pragma unroll
-    for (int k = 0; k < NB; ++k) P.out[k][e * Np + i] = acc[k];
+        for (int k = 0; k < NB; ++k) {
+            double* o = P.out[k] + (e * Np + i);
+            *o = beta != 0.0 ? axpby_combine(alpha, acc[k], beta, *o) : alpha * acc[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) P.out[k][e * Np + i] = acc[k];
+    }
 }
 
 template <int NB>
@@ -171,6 +181,16 @@ __global__ __launch_bounds__(256) void facemass_generic_kernel(
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (E - e_begin) * Np) return;
     facemass_item<NB>(J, R, P, E, Np, nf, Nfp, jEs, jFs, rF, rI, rJ, e_begin + idx / Np, (int)(idx % Np));
+}
+
+// the accumulating form (fe_facemass_acc_f64) for launches of fewer elements than a wave tile
+template <int NB>
+__global__ __launch_bounds__(256) void facemass_generic_acc_kernel(
+    const double* __restrict__ J, const double* __restrict__ R, FieldPtrs P, int64_t E, int Np,
+    int nf, int Nfp, int64_t jEs, int64_t jFs, int rF, int rI, int rJ, int64_t e_begin, double alpha, double beta) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (E - e_begin) * Np) return;
+    facemass_item<NB, true>(J, R, P, E, Np, nf, Nfp, jEs, jFs, rF, rI, rJ, e_begin + idx / Np, (int)(idx % Np), alpha, beta);
 }
 
 }  // namespace fe

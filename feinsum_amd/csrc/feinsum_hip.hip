@@ -4,6 +4,7 @@
 // sql_utils.py:247-294) and asynchronous launches on the caller's stream.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -920,6 +921,33 @@ int launch_fm(const double* J, const double* R, const void* prep, const fe::Fiel
         }
     }
     return fail(FE_EINVAL, "face-mass: internal field grouping error (nb=%d)", nb);
+}
+
+// The accumulating face-mass launch (fe_facemass_acc_f64; fe_facemass.h, kAcc): static walk, the plain operator
+template <int NP, int NFP, int M, int NB>
+int launch_fm_acc_nb(const double* J, const double* R, const fe::FieldPtrs& P, int64_t E, int64_t nTiles, int jfe, int rifj,
+                     double alpha, double beta, hipStream_t s) {
+    using G = fe::FmGeom<NP, NFP, M>;
+    // (with beta != 0 the launch reads its outputs too: they count as inputs for the cache rule)
+    const int64_t in_doubles = fe::kFmNf + (int64_t)NB * fe::kFmNf * NFP + (beta != 0.0 ? (int64_t)NB * NP : 0);
+    jfe = (jfe ? 1 : 0) | temporal_flag(in_doubles * E * 8, kTemporalFloorFaceMass, kTemporalCapFaceMassMib);
+    char what[96];
+    snprintf(what, sizeof(what), "face-mass Np=%d Nfp=%d M=%d b=%d, accumulating", NP, NFP, M, NB);
+    return mfma_launch<fe::facemass_mfma_acc_kernel<NP, NFP, M, NB>>(
+        s, walk_static(nTiles), {G::WAVES, G::THREADS, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU}, what,
+        [&](const Launch&) { return call(jfe & ~fe::kOpStoresWriteThrough, 0, J, R, P, E, nTiles, jfe, rifj, alpha, beta); });
+}
+
+template <int NP, int NFP, int M>
+int launch_fm_acc(const double* J, const double* R, const fe::FieldPtrs& P, int nb, int64_t E, int64_t nTiles, int jfe, int rifj,
+                  double alpha, double beta, hipStream_t s) {
+    switch (nb) {
+        case 2: return launch_fm_acc_nb<NP, NFP, M, 2>(J, R, P, E, nTiles, jfe, rifj, alpha, beta, s);
+        case 3: return launch_fm_acc_nb<NP, NFP, M, 3>(J, R, P, E, nTiles, jfe, rifj, alpha, beta, s);
+        case 4: return launch_fm_acc_nb<NP, NFP, M, 4>(J, R, P, E, nTiles, jfe, rifj, alpha, beta, s);
+        default: break;
+    }
+    return fail(FE_EINVAL, "accumulating face-mass: internal field grouping error (nb=%d)", nb);
 }
 
 // 'xre,rij,ej->xei' operands as grad-type planes: j[x] = J[x], out[k][x] = out_k[x]
@@ -2097,6 +2125,95 @@ int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_pre
         }
         k0 += nb;
     }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+int fe_facemass_acc_f64(const double* J, const double* R, const double* const* v, double* const* out, int64_t E, int32_t Np,
+                        int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, double alpha, double beta, void* stream) {
+    forget_last_launch();
+    if (E < 0) return fail(FE_EINVAL, "accumulating face-mass: E must be >= 0 (got %lld)", (long long)E);
+    if (Np <= 0 || nf <= 0 || Nfp <= 0 || b <= 0)
+        return fail(FE_EINVAL, "accumulating face-mass: Np, nf, Nfp, b must be positive (%d %d %d %d)", Np, nf, Nfp, b);
+    if (layout_flags & ~7) return fail(FE_EINVAL, "accumulating face-mass: bad layout flags %d", layout_flags);
+    if (!std::isfinite(alpha) || !std::isfinite(beta))
+        return fail(FE_EINVAL, "accumulating face-mass: alpha and beta must be finite (got %g, %g)", alpha, beta);
+    if (!v || !out) return fail(FE_EINVAL, "accumulating face-mass: null pointer table");
+    FmChoice geo{0, 16};
+    // the compiled scope: tetrahedra p = 1..4, two or more fields (in groups of 2..4); the caller evaluates anything else into
+    // an array of its own and combines with fe_axpby
+    if (nf != fe::kFmNf || Np == 56 || !fm_mfma_geometry(Np, nf, Nfp, &geo) || b < 2)
+        return fail(FE_EUNSUPPORTED, "accumulating face-mass: (nf, Np, Nfp, b) = (%d, %d, %d, %d) has no fused kernel"
+                    " (tetrahedra p = 1..4, b >= 2)", nf, Np, Nfp, b);
+    if (E == 0) return FE_OK;
+    if (!J || !R) return fail(FE_EINVAL, "accumulating face-mass: null device pointer");
+    for (int k = 0; k < b; ++k) {
+        if (!v[k] || !out[k]) return fail(FE_EINVAL, "accumulating face-mass: null field pointer %d", k);
+        if ((reinterpret_cast<uintptr_t>(v[k]) | reinterpret_cast<uintptr_t>(out[k])) & 7u)
+            return fail(FE_EINVAL, "accumulating face-mass: field pointers must be 8-byte aligned");
+    }
+    if ((reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(R)) & 7u)
+        return fail(FE_EINVAL, "accumulating face-mass: device pointers must be 8-byte aligned");
+    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "accumulating face-mass: E*Np too large");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int jfe = (layout_flags & FE_FM_J_FE) ? 1 : 0;
+    const int rifj = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((layout_flags & FE_FM_R_T) ? 2 : 0);
+    const int64_t jEs = jfe ? 1 : nf, jFs = jfe ? E : 1;
+    const int rF = rifj == 0 ? Np * Nfp : rifj == 1 ? Nfp : rifj == 2 ? Nfp * Np : Np;
+    const int rI = rifj == 0 ? Nfp : rifj == 1 ? nf * Nfp : 1;
+    const int rJ = rifj == 0 || rifj == 1 ? 1 : rifj == 2 ? Np : nf * Np;
+    const int64_t nTiles = E / geo.tel;   // full wave tiles; the launch covers the elements behind the last one too
+    // fields go in groups of up to four per launch; never leave a group of one
+    for (int k0 = 0; k0 < b;) {
+        int nb = b - k0 < 4 ? b - k0 : 4;
+        if (b - k0 - nb == 1) nb -= 1;
+        const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
+        if (nTiles > 0) {
+            int rc = FE_OK;
+            switch (Np) {   // the (Np, Nfp, M) geometries of fe_facemass_f64
+                case 35: rc = launch_fm_acc<35, 15, 1>(J, R, P, nb, E, nTiles, jfe, rifj, alpha, beta, s); break;
+                case 20: rc = launch_fm_acc<20, 10, 1>(J, R, P, nb, E, nTiles, jfe, rifj, alpha, beta, s); break;
+                case 10: rc = launch_fm_acc<10, 6, 2>(J, R, P, nb, E, nTiles, jfe, rifj, alpha, beta, s); break;
+                default: rc = launch_fm_acc<4, 3, 4>(J, R, P, nb, E, nTiles, jfe, rifj, alpha, beta, s); break;
+            }
+            if (rc != FE_OK) return rc;
+        } else {   // fewer elements than a wave tile: one thread per entry
+            const dim3 grid(generic_grid(E, Np)), block(256);
+#define FE_FM_ACC_CASE(NB)                                                                                 \
+    case NB:                                                                                               \
+        hipLaunchKernelGGL(fe::facemass_generic_acc_kernel<NB>, grid, block, 0, s, J, R, P, E, Np, nf, Nfp, \
+                           jEs, jFs, rF, rI, rJ, (int64_t)0, alpha, beta);                                 \
+        break;
+            switch (nb) { FE_FM_ACC_CASE(2) FE_FM_ACC_CASE(3) FE_FM_ACC_CASE(4) }
+#undef FE_FM_ACC_CASE
+        }
+        k0 += nb;
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+// out <- alpha x + beta out over n contiguous entries (fe_einsum.h, axpby_kernel)
+int fe_axpby(void* out, const void* x, int64_t n, double alpha, double beta, int32_t dtype, void* stream) {
+    if (n < 0) return fail(FE_EINVAL, "axpby: n must be >= 0 (got %lld)", (long long)n);
+    if (dtype != FE_DTYPE_F64 && dtype != FE_DTYPE_F32) return fail(FE_EINVAL, "axpby: dtype %d is neither float64 nor float32", dtype);
+    if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(FE_EINVAL, "axpby: alpha and beta must be finite (got %g, %g)", alpha, beta);
+    if (n == 0) return FE_OK;
+    if (!out || !x) return fail(FE_EINVAL, "axpby: null device pointer");
+    const uintptr_t size = dtype == FE_DTYPE_F64 ? 8 : 4;
+    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(x)) % size)
+        return fail(FE_EINVAL, "axpby: pointers must be aligned to the element size (%d bytes)", (int)size);
+    if (n >= ((int64_t)1 << 39)) return fail(FE_EINVAL, "axpby: n too large");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t per = 16 / (int64_t)size;
+    const int64_t want = (n / per + 255) / 256 + 1, cap = 32 * (int64_t)device_cu_count();
+    const dim3 grid((unsigned)(want < cap ? want : cap)), block(256);
+    if (dtype == FE_DTYPE_F64)
+        hipLaunchKernelGGL(fe::axpby_kernel<double>, grid, block, 0, s, static_cast<double*>(out), static_cast<const double*>(x), n,
+                           alpha, beta);
+    else
+        hipLaunchKernelGGL(fe::axpby_kernel<float>, grid, block, 0, s, static_cast<float*>(out), static_cast<const float*>(x), n,
+                           (float)alpha, (float)beta);
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }

@@ -34,7 +34,9 @@ Argument conventions kept from the reference:
                default ``"split"`` the outputs come from the split allocator
                (``feinsum_amd.placement.zeros``; ``evaluate`` allocates the outputs it
                is not handed the same way), ``"separate"`` takes every array
-               from torch; ``timeit_details(...).placement`` reports which was used.
+               from torch; ``timeit_details(...).placement`` reports which was used;
+               ``"accumulate"`` (``"kernel"`` / ``"axpby"``): which way an accumulating ``evaluate(..., alpha=, beta=)``
+               adds onto its outputs, instead of what :func:`accumulate_route` picks.
 ``schedule``   followed by the ``"contraction"`` transform (default: the optimal one) and by the
                ``"reduction"`` transform where the einsum does not stream in one launch; the
                other kernels implement the optimal schedule and ignore it.
@@ -273,8 +275,9 @@ class _FamilyLaunch:
     """A family plan bound to concrete device arrays: launch / time."""
 
     def __init__(self, plan: KernelPlan, einsum: BatchedEinsum, arg_dict: Mapping[str, Any],
-                 outs: Sequence[Any], variant: Any) -> None:
+                 outs: Sequence[Any], variant: Any, scale: Optional[Tuple[float, float]] = None) -> None:
         self.plan, self.variant = plan, _hip.variant_code(variant)
+        self.scale = scale    # (alpha, beta) of an accumulating face-mass launch (fe_facemass_acc_f64), else None
         role = plan.roles
         rows = einsum.args
         first = rows[0]
@@ -397,7 +400,10 @@ class _FamilyLaunch:
     def launch(self, stream_ptr: int) -> None:
         lib = _hip.load_library()
         for pack in self.groups:
-            if self.f32:
+            if self.scale is not None:
+                _hip.check(lib.fe_facemass_acc_f64(pack.J, pack.D, pack.v, pack.outs, pack.E, pack.Np, pack.nf, pack.Nfp,
+                                                   pack.b, pack.layout_flags, self.scale[0], self.scale[1], stream_ptr))
+            elif self.f32:
                 _hip.check(lib.fe_launch_f32(self.plan.family, C_byref(pack), stream_ptr))
             elif self.group_family == FAMILY_GRADPLANES:
                 _hip.check(lib.fe_gradplanes3d_f64(pack.j3, pack.D, pack.v, pack.outs, pack.E, pack.Np,
@@ -427,7 +433,7 @@ class _FamilyLaunch:
 
     def time_batch(self, n: int, stream_ptr: int) -> float:
         """Seconds for *n* launches of the whole batched einsum (HIP events)."""
-        if len(self.groups) == 1:
+        if len(self.groups) == 1 and self.scale is None:
             family = self.group_family | (_hip.FAMILY_F32 if self.f32 else 0)
             return _hip.time_launches(family, self.groups[0], n, stream_ptr) * 1e-3
         import torch
@@ -553,9 +559,84 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     return "generic"
 
 
+ACCUMULATE_ROUTES = ("kernel", "axpby")
+#: (Np, Nfp) of the tetrahedral orders p = 1..4: the shapes fe_facemass_acc_f64 is compiled for
+_ACC_FACEMASS_SHAPES = frozenset({(4, 3), (10, 6), (20, 10), (35, 15)})
+
+
+def _check_scale(alpha: Any, beta: Any) -> Tuple[float, float]:
+    try:
+        alpha, beta = float(alpha), float(beta)
+    except (TypeError, ValueError):
+        raise InvalidParameterError(f"alpha and beta must be numbers (got {alpha!r}, {beta!r})") from None
+    if not (np.isfinite(alpha) and np.isfinite(beta)):
+        raise InvalidParameterError(f"alpha and beta must be finite (got {alpha}, {beta})")
+    return alpha, beta
+
+
+def _family_group_sizes(plan: KernelPlan, einsum: BatchedEinsum) -> Tuple[int, ...]:
+    """Fields per launch of a family plan: consecutive rows that share J and the operator (as ``_FamilyLaunch`` groups
+    them)."""
+    role, rows = plan.roles, einsum.args
+    op_role = "D" if "D" in role else "R"
+    key = lambda row: (row[role["J"]].name if "J" in role else None, row[role[op_role]].name)   # noqa: E731
+    sizes: list = []
+    for k, row in enumerate(rows):
+        if k and key(row) == key(rows[k - 1]) and plan.family != FAMILY_DIVCOMP:
+            sizes[-1] += 1
+        else:
+            sizes.append(1)
+    return tuple(sizes)
+
+
+def accumulate_route(einsum: BatchedEinsum, transform: Any = None) -> str:
+    """
+    Which way an accumulating evaluation of *einsum* (``evaluate(..., alpha=, beta=)`` other than (1, 0)) takes under
+    *transform*, from the einsum alone (no device): ``"kernel"`` -- the accumulating face-mass kernel
+    (``fe_facemass_acc_f64``): float64 face-mass of tetrahedra p = 1..4, every launch group of two or more fields, the
+    variant ``"auto"`` or ``"mfma"`` -- or ``"axpby"``: the einsum's ordinary launch into a temporary, then ``fe_axpby``.
+    ``transform={"accumulate": "axpby"}`` forces the second; ``{"accumulate": "kernel"}`` insists on the first
+    (``NotImplementedError`` where it does not exist).
+    """
+    forced = transform.get("accumulate") if isinstance(transform, Mapping) else None
+    if forced is not None and forced not in ACCUMULATE_ROUTES:
+        raise InvalidParameterError(f"accumulate must be one of {ACCUMULATE_ROUTES}, got {forced!r}")
+    variant = _variant_from_transform(transform)
+    plan = match_family(einsum) if variant in (None, "auto", "mfma", 0, 2) else None
+    fused = (plan is not None and plan.family == FAMILY_FACEMASS and not plan.params.get("f32")
+             and plan.params.get("nf") == 4 and (plan.params.get("Np"), plan.params.get("Nfp")) in _ACC_FACEMASS_SHAPES
+             and min(_family_group_sizes(plan, einsum)) >= 2)
+    if forced == "kernel" and not fused:
+        raise NotImplementedError(
+            f"einsum '{einsum.get_subscripts()}' x {einsum.b} has no accumulating kernel under this transform (float64"
+            " face-mass of tetrahedra p = 1..4, two or more fields per launch, variant auto or mfma)")
+    return "kernel" if fused and forced != "axpby" else "axpby"
+
+
+class _AxpbyLaunch:
+    """The fallback route of an accumulating evaluation: *inner* evaluates into *temps* (one per output, allocated at bind
+    time on the queue's stream, so that the bound launch can be captured and replayed), then ``fe_axpby`` combines each
+    with its output on the same stream."""
+
+    def __init__(self, inner: Any, temps: Sequence[Any], outs: Sequence[Any], alpha: float, beta: float) -> None:
+        import torch
+
+        self.inner, self.temps, self.scale = inner, tuple(temps), (alpha, beta)
+        self._keep = tuple(outs)
+        self.passes = [(o.data_ptr(), t.data_ptr(), int(o.numel()), o.dtype == torch.float64) for o, t in zip(outs, temps)]
+
+    def launch(self, stream_ptr: int) -> None:
+        self.inner.launch(stream_ptr)
+        for out, tmp, n, f64 in self.passes:
+            _hip.axpby(out, tmp, n, self.scale[0], self.scale[1], f64, stream_ptr)
+
+    def time_batch(self, n: int, stream_ptr: int) -> float:
+        return _hip.time_with_events(self.launch, n, stream_ptr)
+
+
 def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
           out_dict: Optional[Mapping[str, Any]], transform: Any, prepare: bool = False,
-          schedule: Optional[ContractionSchedule] = None):
+          schedule: Optional[ContractionSchedule] = None, alpha: float = 1.0, beta: float = 0.0):
     import torch
 
     q = _as_queue(cq)
@@ -572,6 +653,12 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
         if name in given:
             _check_tensor(name, given[name], out_shape, result_dtype(einsum, k), q)
     _refuse_aliased_outputs(einsum, arg_dict, given)     # before anything is allocated, prepared or launched
+    alpha, beta = _check_scale(alpha, beta)
+    route = None if (alpha, beta) == (1.0, 0.0) else accumulate_route(einsum, transform)
+    if beta != 0.0 and len(given) != len(einsum.output_names):
+        raise InvalidParameterError(
+            f"beta = {beta} adds onto the outputs: every one of them must be handed in through out_dict (missing: "
+            f"{sorted(set(einsum.output_names) - set(given))})")
     outs = []
     allocated: dict = {}      # outputs this call allocated itself: name -> "split" | "torch" | "torch (<why>)"
     owned = []                # ... and the arrays: they belong to the queue's stream (DeviceQueue)
@@ -585,6 +672,10 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
                 outs.append(tensor)
                 owned.append(tensor)
                 allocated[name] = how
+        final_outs = outs
+        if route == "axpby":    # the launch writes temporaries of the queue's stream; fe_axpby combines them with the outputs
+            outs = [torch.empty_like(t) for t in final_outs]
+            owned.extend(outs)
     kind = launch_kind(einsum, transform, sizes)
     if kind == "contraction":
         bound = ContractionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
@@ -596,15 +687,20 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
         with torch.cuda.device(q.torch_device):
             bound = AdjointLaunch(match_operator_adjoint(einsum), einsum, arg_dict, outs, stream=q.stream)
     elif kind == "family":
-        bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform))
-        if _prepared_from_transform(transform, prepare):
+        bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform),
+                              scale=(alpha, beta) if route == "kernel" else None)
+        if route != "kernel" and _prepared_from_transform(transform, prepare):
             with torch.cuda.device(q.torch_device), _on_stream_of(q):
                 bound.prepare_operators(q.stream_ptr)
     else:
         bound = _GenericLaunch(einsum, arg_dict, outs)
+    if route == "axpby":
+        bound, temps, outs = _AxpbyLaunch(bound, outs, final_outs, alpha, beta), outs, final_outs
+    #: None (the outputs are overwritten), or which way the launch adds onto them: "kernel" | "axpby" (accumulate_route)
+    bound.accumulate = route
     # byte ranges the launch reads and writes (operator.py checks them before reordering launches)
-    bound.reads = tuple(_span(arg_dict[name]) for name in sorted(einsum.all_args))
-    bound.writes = tuple(_span(t) for t in outs)
+    bound.reads = tuple(_span(arg_dict[name]) for name in sorted(einsum.all_args)) + (tuple(_span(t) for t in outs) if beta != 0.0 else ())
+    bound.writes = tuple(_span(t) for t in outs) + (tuple(_span(t) for t in temps) if route == "axpby" else ())
     bound.output_allocations = MappingProxyType(allocated)
     bound.owned_arrays, bound.owned_stream_ptr = tuple(owned), q.stream_ptr   # (operator.py: launches on another stream mark them)
     return q, bound, outs
@@ -643,12 +739,26 @@ def _allocate_output(shape: Tuple[int, ...], dtype: Any, device: Any, transform:
 
 def evaluate(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *,
              out_dict: Optional[Mapping[str, Any]] = None, transform: Any = None,
-             wait: bool = False, schedule: Optional[ContractionSchedule] = None) -> Mapping[str, Any]:
+             wait: bool = False, schedule: Optional[ContractionSchedule] = None,
+             alpha: float = 1.0, beta: float = 0.0) -> Mapping[str, Any]:
     """
     Enqueue *einsum* on the queue's stream and return ``{"_fe_out": tensor, ...}``
     (the replacement for ``t_unit.executor(cq, ...)(cq, **arg_dict)``,
     reference measure.py:163-165).  Asynchronous unless *wait*; outputs are
     fully overwritten.  *schedule*: see the module docstring.
+
+    Accumulating: with *alpha*, *beta* (Python floats, finite) other than (1, 0) every output row k becomes
+    ``out_k <- alpha * E_k + beta * out_k``, ``E_k`` being what the call computes otherwise (``C <- alpha A B + beta C`` of
+    BLAS; a time stepper's ``k <- a k + dt rhs``).  ``beta != 0`` needs every output in *out_dict*
+    (``InvalidParameterError``, like the aliasing rule below and in the same place); ``beta == 0`` does not read the
+    outputs: NaN or infinity sitting in them does not reach the result.  Float32 outputs get alpha and beta cast to
+    float32.  Rounding: ``E_k`` is bitwise what the non-accumulating launch of the same kernel produces; the combine,
+    ``fma(alpha, E_k, beta * out_k)``, adds at most two roundings per entry; with alpha and beta signed powers of two both
+    products are exact and the result is bitwise ``fl(alpha E_k + beta out_k)``.  It works under every transform, one of
+    two ways (:func:`accumulate_route`; the bound launch says which in ``bound.accumulate``): the accumulating face-mass
+    kernel, which reads the old output where it stores the new one, or the ordinary launch into a temporary (allocated at
+    bind time on the queue's stream) followed by ``fe_axpby`` on the same stream.  (1, 0), the default, is the code path
+    without any of this.  DESIGN.md section 3m.
 
     Aliasing: an output handed in through *out_dict* may not share a byte with any input, nor with another output
     (``InvalidParameterError``, raised before anything is allocated, prepared or launched, under every transform): the
@@ -664,7 +774,7 @@ def evaluate(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *,
     """
     import torch
 
-    q, bound, outs = _bind(einsum, cq, arg_dict, out_dict, transform, schedule=schedule)
+    q, bound, outs = _bind(einsum, cq, arg_dict, out_dict, transform, schedule=schedule, alpha=alpha, beta=beta)
     with torch.cuda.device(q.torch_device):
         bound.launch(q.stream_ptr)
     if wait:

@@ -265,7 +265,8 @@ class BoundOperator:
 
 def bind_operator(stages: Sequence[StageT], cq: Any, *,
                   out_dicts: Optional[Sequence[Optional[Mapping[str, Any]]]] = None,
-                  transform: Any = None, fuse: bool = True, prepare: bool = False) -> BoundOperator:
+                  transform: Any = None, fuse: bool = True, prepare: bool = False,
+                  alpha: float = 1.0, beta: float = 0.0) -> BoundOperator:
     """Bind every stage (shape / dtype / device checks as in ``evaluate``) and merge what can share a launch.
 
     *prepare* (off by default: the bound arrays stay the operands, whatever is written into them between
@@ -281,6 +282,11 @@ def bind_operator(stages: Sequence[StageT], cq: Any, *,
 
     Stream order as in ``evaluate``: the outputs not handed in and the prepared operators are allocated under the
     queue's stream and belong to it; ``launch`` / ``replay`` on another stream mark them as used there."""
+    if (alpha, beta) != (1.0, 0.0) or (isinstance(transform, Mapping) and "accumulate" in transform):
+        # (in the one-launch wave operator different blocks are in different bodies at once: a lift adding onto div's
+        # output would race -- DESIGN.md section 3m)
+        raise NotImplementedError("bind_operator: stages do not accumulate (alpha, beta); use evaluate(..., alpha=, beta=)"
+                                  " stage by stage")
     if out_dicts is not None and len(out_dicts) != len(stages):
         raise ValueError("out_dicts: need one entry (or None) per stage")
     queue, bound, outputs = None, [], []
@@ -297,13 +303,14 @@ def bind_operator(stages: Sequence[StageT], cq: Any, *,
 
 def evaluate_operator(stages: Sequence[StageT], cq: Any, *,
                       out_dicts: Optional[Sequence[Optional[Mapping[str, Any]]]] = None,
-                      transform: Any = None, fuse: bool = True, wait: bool = False) -> List[Mapping[str, Any]]:
+                      transform: Any = None, fuse: bool = True, wait: bool = False,
+                      alpha: float = 1.0, beta: float = 0.0) -> List[Mapping[str, Any]]:
     """Enqueue all stages; returns one ``{"_fe_out": tensor, ...}`` mapping per stage.  The aliasing rule of
     :func:`bind_operator` holds: no stage may write what it reads itself, a later stage may read what an earlier one
     wrote."""
     import torch
 
-    op = bind_operator(stages, cq, out_dicts=out_dicts, transform=transform, fuse=fuse)
+    op = bind_operator(stages, cq, out_dicts=out_dicts, transform=transform, fuse=fuse, alpha=alpha, beta=beta)
     if op.queue is not None:
         with torch.cuda.device(op.queue.torch_device):
             op.launch()

@@ -233,6 +233,26 @@ int fe_facemass_f64(const double* J, const double* R,
                     int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
                     int32_t layout_flags, int32_t variant, void* stream);
 
+/* ---- accumulating evaluation: out <- alpha * E + beta * out ------------
+ * face-mass that adds onto what its outputs already hold:
+ *   out_k[e,i] <- alpha * sum_{f,j} J[e,f] R[f,i,j] v_k[f,e,j] + beta * out_k[e,i]
+ * Arguments as fe_facemass_f64 (no variant: the matrix-core kernel, static walk); alpha, beta finite (FE_EINVAL).
+ * The sum is bitwise what fe_facemass_f64 stores; the combine is fma(alpha, sum, beta * out): two roundings at most, one
+ * when alpha and beta are signed powers of two.  beta == 0 does not read out (what it holds, NaN included, is ignored).
+ * Every entry is read and written by the same thread, so an output may hold any earlier result -- but, as everywhere, it
+ * may not overlap an input or another output.
+ * Compiled for tetrahedra p = 1..4 ((Np, Nfp) = (4,3), (10,6), (20,10), (35,15), nf = 4), b >= 2 (fields go in groups of
+ * 2..4 per launch), all eight layouts; anything else is FE_EUNSUPPORTED: evaluate into an array of your own and combine
+ * with fe_axpby. */
+int fe_facemass_acc_f64(const double* J, const double* R,
+                        const double* const* v, double* const* out,
+                        int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
+                        int32_t layout_flags, double alpha, double beta, void* stream);
+/* out[i] <- alpha * x[i] + beta * out[i], i < n, contiguous; dtype FE_DTYPE_F64 or FE_DTYPE_F32 (alpha and beta are
+ * cast to it); pointers aligned to the element size, out and x not overlapping; the same combine and the same beta == 0
+ * rule as above.  Asynchronous on `stream`. */
+int fe_axpby(void* out, const void* x, int64_t n, double alpha, double beta, int32_t dtype, void* stream);
+
 /* ---- prepared operators ------------------------------------------------------------------
  * The operator matrices (D of grad / div, R or L of face-mass) are constant across the launches
  * of a time-stepping code, while every launch rebuilds their MFMA register fragments from the
