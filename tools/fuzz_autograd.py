@@ -1055,37 +1055,133 @@ def _exact(rng: np.random.Generator, shapes: Dict[str, Tuple[int, ...]], rows, s
     return m, x
 
 
-def run_kernels(seed: int, geom_runs=None, fm_runs=None) -> Stats:
+KERNEL_PLACEMENTS = ("aligned", "all", "only:geometry", "only:operator", "only:field", "only:last-field", "only:output",
+                     "only:last-output")
+
+
+def kernel_shifts(placement: Optional[str], ins: Sequence[Tuple[str, str]], outs: Sequence[str]) -> Dict[str, int]:
+    """Shift in elements (float64: 8 bytes) per array of a direct kernel call: *ins* ``(name, role)`` with role
+    "geometry", "operator" or "field", *outs* the output names (tools/fuzz_dg.py: placements)."""
+    assert placement is None or placement in KERNEL_PLACEMENTS, placement
+    names = [n for n, _ in ins] + list(outs)
+    fields = [n for n, r in ins if r == "field"]
+    hit = {None: [], "aligned": [], "all": names,
+           "only:geometry": [n for n, r in ins if r == "geometry"], "only:operator": [n for n, r in ins if r == "operator"],
+           "only:field": fields[:1], "only:last-field": fields[-1:], "only:output": list(outs[:1]),
+           "only:last-output": list(outs[-1:])}[placement]
+    return {n: int(n in hit) for n in names}
+
+
+class _KernelArrays:
+    """The device arrays of one direct kernel call.  Without a placement: inputs from the allocator, outputs between
+    guard bands.  With one: every array embedded by ``fuzz_dg.embed`` (inputs between NaN bands and snapshotted,
+    outputs between sentinel bands) at its shift."""
+
+    def __init__(self, torch, placement: Optional[str], x: Dict[str, np.ndarray], ins: Sequence[Tuple[str, str]],
+                 outs: Dict[str, Tuple[int, ...]]) -> None:
+        self.placement = placement
+        self.out: Dict[str, Any] = {}
+        if placement is None:
+            self.d = _to_dev(torch, x)
+            self._bufs = []
+            for name, shape in outs.items():
+                buf, out, nn = _guarded(torch, shape, torch.float64)
+                self._bufs.append((buf, nn))
+                self.out[name] = out
+            return
+        shifts = kernel_shifts(placement, ins, list(outs))
+        self._ins = {}
+        for name, _ in ins:
+            emb = D.embed(torch, x[name].shape, torch.float64, shifts[name], "in", torch.from_numpy(x[name]), DEVICE)
+            self._ins[name] = (emb, emb.snapshot())
+        self.d = {name: emb.view for name, (emb, _) in self._ins.items()}
+        self._outs = {name: D.embed(torch, shape, torch.float64, shifts[name], "out", device=DEVICE)
+                      for name, shape in outs.items()}
+        self.out = {name: emb.view for name, emb in self._outs.items()}
+
+    def guards_intact(self) -> bool:
+        if self.placement is None:
+            return all(_guards_intact(buf, nn) for buf, nn in self._bufs)
+        return all(emb.guards_intact() for emb in self._outs.values())
+
+    def changed_inputs(self) -> List[str]:
+        if self.placement is None:
+            return []
+        return [name for name, (emb, snap) in self._ins.items() if not emb.unchanged(snap)]
+
+
+def _kernel_checks(st: Stats, label: str, arrays: _KernelArrays, got) -> None:
+    """Guards, inputs unchanged, then every ``(name, output, int64 reference)`` of *got*: NaNs the reference does not
+    have (``leak:``), bitwise equality."""
+    import torch
+
+    if not arrays.guards_intact():
+        st.fail(f"{label}: wrote outside its outputs")
+        return
+    for name in arrays.changed_inputs():
+        st.fail(f"{label}: input {name} changed by the launch")
+    for name, g, w in got:
+        want = torch.from_numpy(w.astype(np.float64)).to(DEVICE)
+        st.exact_runs += 1
+        _, leaked = D.nan_entries(g, want)
+        if leaked:
+            st.cov["leak:nan-entries"] += leaked
+            st.fail(f"{label}: {name}: over-read: {leaked} NaN entries from behind an input")
+        bad = ref_.differing_entries(g, want)
+        if bad:
+            st.fail(f"{label}: {name}: {bad} entries differ from the exact result")
+        else:
+            st.exact_equal += 1
+
+
+def placement_kernel_runs(seed: int):
+    """``(geomadj runs, facemass runs)`` of the placement pass: a subset of :func:`geomadj_runs` (every Np, output
+    layout and operator layout; every (X, R) of "xre") and face-mass runs of every compiled shape and layout with b
+    in {1, 2, 4} and one b = 9 (two launch groups), at the E of :data:`KERNEL_E`."""
+    rng = random.Random(seed + 37)
+    geom, combos, xr = [], set(), set()
+    for run in geomadj_runs(seed):
+        Np, X, R, op, lay, E, _ = run
+        if E != MULTI_TRIP_E and ((Np, lay, op) not in combos or (lay == "xre" and (X, R) not in xr)):
+            combos.add((Np, lay, op))
+            xr.update({(X, R)} if lay == "xre" else ())
+            geom.append(run)
+    fm = []
+    for shape in FACEMASS_ADJ_SHAPES:
+        for k, lay in enumerate(FM_LAYOUT_FLAGS):
+            b = (1, 2, 4)[(k + len(fm)) % 3]
+            fm.append((shape, lay, b, ("both", "dv", "dJ")[k % 3], rng.choice(KERNEL_E), rng.randrange(1 << 30)))
+        fm.append((shape, rng.choice(FM_LAYOUT_FLAGS), 9, "both", rng.choice(KERNEL_E), rng.randrange(1 << 30)))
+    return geom, fm
+
+
+def run_kernels(seed: int, geom_runs=None, fm_runs=None, placement: Optional[str] = None) -> Stats:
     """Every :func:`geomadj_runs` / :func:`facemass_runs` combination through ``_hip.geomadj`` /
-    ``_hip.facemass_adj``, exact data (scale 1), outputs in NaN-filled buffers between guard bands."""
+    ``_hip.facemass_adj``, exact data (scale 1), outputs in NaN-filled buffers between guard bands.  With *placement*
+    (:data:`KERNEL_PLACEMENTS`) every array sits at that placement's address offset between bands
+    (:class:`_KernelArrays`), and the inputs must come back unchanged."""
     import torch
 
     from feinsum_amd import _hip
 
-    st = Stats(f"adjoint kernels seed={seed}")
+    st = Stats(f"adjoint kernels seed={seed}" + (f" {placement}" if placement else ""))
+    if placement:
+        st.cov["leak:nan-entries"] += 0
+    tag = f" [{placement}]" if placement else ""
     for Np, X, R, op, lay, E, s in (geomadj_runs(seed) if geom_runs is None else geom_runs):
         rng = np.random.default_rng(s)
         m, x = _exact(rng, {"D": (R, Np, Np), "a": (E, Np), "b": (X, E, Np)}, [(["D", "a", "b"], Np * Np)])
-        d = _to_dev(torch, x)
-        want = torch.from_numpy(geomadj_reference(m["D"], m["a"], m["b"], op, lay).astype(np.float64)).to(DEVICE)
         shape = {"xre": (X, R, E), "re": (R, E), "er": (E, R), "e": (E,)}[lay]
         strides = {"xre": (R * E, E, 1), "re": (0, E, 1), "er": (0, 1, R), "e": (0, 0, 1)}[lay]
-        buf, out, nn = _guarded(torch, shape, torch.float64)
+        arrays = _KernelArrays(torch, placement, x, [("D", "operator"), ("a", "field"), ("b", "field")], {"out": shape})
+        d, out = arrays.d, arrays.out["out"]
         _hip.geomadj(d["D"].data_ptr(), d["a"].data_ptr(), d["b"].data_ptr(), out.data_ptr(), E, X, R, Np, strides,
                      op_flags=op)
         torch.cuda.synchronize()
-        label = f"geomadj Np={Np} X={X} R={R} op={op} {lay} E={E} seed={s}"
+        label = f"geomadj Np={Np} X={X} R={R} op={op} {lay} E={E} seed={s}{tag}"
         st.cov.update([f"geomadj:Np{Np}", f"geomadj:{lay}", f"geomadj:op{op}", f"geomadj:X{X}R{R}",
-                       f"E:{'multi-trip' if E == MULTI_TRIP_E else E}"])
-        if not _guards_intact(buf, nn):
-            st.fail(f"{label}: wrote outside its output")
-            continue
-        st.exact_runs += 1
-        bad = ref_.differing_entries(out, want)
-        if bad:
-            st.fail(f"{label}: {bad} entries differ from the exact result")
-        else:
-            st.exact_equal += 1
+                       f"E:{'multi-trip' if E == MULTI_TRIP_E else E}"] + ([f"place:{placement}"] if placement else []))
+        _kernel_checks(st, label, arrays, [("out", out, geomadj_reference(m["D"], m["a"], m["b"], op, lay))])
     for (nf, Np, Nfp), (jl, rl, flags), b, what, E, s in (facemass_runs(seed) if fm_runs is None else fm_runs):
         rng = np.random.default_rng(s)
         shapes = {"J": (E, nf) if jl == "ef" else (nf, E), "R": _r_shape(rl, nf, Np, Nfp)}
@@ -1095,41 +1191,27 @@ def run_kernels(seed: int, geom_runs=None, fm_runs=None) -> Stats:
             shapes[f"v{k}"] = (nf, E, Nfp)
             rows += [(["J", "R", f"g{k}"], Np), (["R", f"g{k}", f"v{k}"], b * Np * Nfp)]
         m, x = _exact(rng, shapes, rows)
-        d = _to_dev(torch, x)
         with_dv, with_dJ = what in ("dv", "both"), what in ("dJ", "both")
         dv_want, dJ_want = facemass_references(m["J"], m["R"], [m[f"g{k}"] for k in range(b)],
                                                [m[f"v{k}"] for k in range(b)] if with_dJ else None, jl, rl)
-        bufs = []
-        dvs = []
-        if with_dv:
-            for k in range(b):
-                buf, out, nn = _guarded(torch, (nf, E, Nfp), torch.float64)
-                bufs.append((buf, nn))
-                dvs.append(out)
-        dJ = None
-        if with_dJ:
-            buf, dJ, nn = _guarded(torch, shapes["J"], torch.float64)
-            bufs.append((buf, nn))
+        ins = [("J", "geometry"), ("R", "operator")] + [(f"g{k}", "field") for k in range(b)] + \
+              ([(f"v{k}", "field") for k in range(b)] if with_dJ else [])
+        outs = {**({f"dv{k}": (nf, E, Nfp) for k in range(b)} if with_dv else {}), **({"dJ": shapes["J"]} if with_dJ else {})}
+        arrays = _KernelArrays(torch, placement, x, ins, outs)
+        d = arrays.d
+        dvs = [arrays.out[f"dv{k}"] for k in range(b)] if with_dv else []
+        dJ = arrays.out["dJ"] if with_dJ else None
         _hip.facemass_adj(d["J"].data_ptr(), d["R"].data_ptr(), [d[f"g{k}"].data_ptr() for k in range(b)],
                           [d[f"v{k}"].data_ptr() for k in range(b)] if with_dJ else None,
                           [t.data_ptr() for t in dvs] if with_dv else None,
                           dJ.data_ptr() if with_dJ else None, E, Np, nf, Nfp, layout_flags=flags)
         torch.cuda.synchronize()
-        label = f"facemass_adj (nf, Np, Nfp)=({nf}, {Np}, {Nfp}) {jl},{rl} b={b} {what} E={E} seed={s}"
+        label = f"facemass_adj (nf, Np, Nfp)=({nf}, {Np}, {Nfp}) {jl},{rl} b={b} {what} E={E} seed={s}{tag}"
         st.cov.update([f"facemass_adj:Np{Np}", f"facemass_adj:{jl},{rl}", f"facemass_adj:b{b}",
-                       f"facemass_adj:{what}", f"E:{'multi-trip' if E == MULTI_TRIP_E else E}"])
-        if not all(_guards_intact(buf, nn) for buf, nn in bufs):
-            st.fail(f"{label}: wrote outside its outputs")
-            continue
-        got = ([(f"dv{k}", dvs[k], dv_want[k]) for k in range(b)] if with_dv else []) + \
-              ([("dJ", dJ, dJ_want)] if with_dJ else [])
-        for name, g, w in got:
-            st.exact_runs += 1
-            bad = ref_.differing_entries(g, torch.from_numpy(w.astype(np.float64)).to(DEVICE))
-            if bad:
-                st.fail(f"{label}: {name}: {bad} entries differ from the exact result")
-            else:
-                st.exact_equal += 1
+                       f"facemass_adj:{what}", f"E:{'multi-trip' if E == MULTI_TRIP_E else E}"]
+                      + ([f"place:{placement}"] if placement else []))
+        _kernel_checks(st, label, arrays, ([(f"dv{k}", dvs[k], dv_want[k]) for k in range(b)] if with_dv else []) +
+                       ([("dJ", dJ, dJ_want)] if with_dJ else []))
     return st
 
 

@@ -3,6 +3,8 @@ product, triangles, the fused operator) through every transform that accepts the
 oracle/einsum_ref.py (test infrastructure, like tests/).
 
     python tools/fuzz_dg.py [n_cases] [seed]
+    python tools/fuzz_dg.py --placement [seed]
+    python tools/fuzz_dg.py --repro '<REPRO line of either kind>'
 
 Passes:
 
@@ -16,6 +18,14 @@ Passes:
 ``run_poison``     the same launch on all-NaN inputs of another size first: the clean launch after it stays exact.
 ``run_large``      whole-array exact checks at E = 98 304 ... 1 000 007 (8e6 on request) with the walk, tail, load and
                    store knobs and the output allocation varied; float32 at E = 70 004 and 1 000 004.
+``run_placement``  a fixed case list with every operand 0 or 8 bytes (float64), 0, 4, 8 or 12 bytes (float32) past a
+                   256-byte boundary (:func:`embed`): one array shifted at a time, all of them, a random mix, against
+                   the aligned launch.  Inputs sit between NaN bands, so a value read from behind an input shows as
+                   a NaN (``leak:``); every input buffer must come back bitwise unchanged.  Exact data: bitwise the
+                   int64 einsum.  Signed data: the bound, and every all-float64 result bitwise that of the aligned
+                   launch (no float64 route looks at more than ``& 7`` of a pointer, so the same kernel runs the same
+                   arithmetic; float32 and mixed cases may move between the matrix-core and the tiled kernel and
+                   get the bound alone).  A launch accepted aligned must be accepted at every placement.
 
 Outputs land in NaN-filled buffers between sentinel guard bands (tools/fuzz_einsum.py).  Runs are counted per family,
 order, dtype, transform, E class, walk and fused / prepared (:data:`MINIMUMS`).
@@ -792,7 +802,559 @@ def run_large(seed: int, sizes: Sequence[int] = LARGE_E, only: Optional[Sequence
     return st
 
 
+# --------------------------------------------------------------------------
+# operands at every accepted address offset
+# --------------------------------------------------------------------------
+
+#: elements of NaN (inputs) or SENTINEL (outputs) on either side of an embedded array; 4 and 8 x BAND bytes are
+#: multiples of 256
+BAND = 1024
+assert BAND >= GUARD and BAND * 4 % 256 == 0
+#: the bands of an input: NaNs with this payload (integer view), so that "unchanged" is a bitwise statement
+IN_NAN = {8: 0x7FF8_0000_DEAD_BEEF, 4: 0x7FC0_BEEF}
+#: the payload of an output before the launch: a NaN no arithmetic makes, so an entry that was never written can be
+#: told from a NaN that was computed from an over-read
+OUT_NAN = {8: 0x7FF8_0000_0000_0BAD, 4: 0x7FC0_0BAD}
+K_MAX_FIELDS = 8   # fe_common.h kMaxFields: fields per launch group
+PLACEMENTS = ("aligned", "only:geometry", "only:operator", "only:field", "only:last-field", "only:output",
+              "only:last-output", "all", "mixed")
+FULL_TRANSFORMS = ("auto", "mfma")   # every placement; the other transforms run "aligned" and "all"
+#: orders with float32 matrix-core kernels (fe_launch_f32), and the kinds that reach them
+F32_MFMA_ORDERS = ((4, 3), (10, 6), (20, 10), (35, 15))
+F32_MFMA_KINDS = ("grad", "div", "bgrad", "bdiv", "fm", "fm_ifj", "fm_jfi", "fm_fji")
+
+
+class Embedded:
+    """An array ``shift`` elements past a 256-byte boundary inside a larger buffer (:func:`embed`)."""
+
+    def __init__(self, torch, buf, lead: int, shape, role: str, shift: int) -> None:
+        self._torch, self.buf, self.lead, self.role, self.shift = torch, buf, lead, role, shift
+        self.n = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
+        self.view = buf[lead:lead + self.n].view(tuple(shape))
+        self.esize = buf.element_size()
+
+    def ints(self):
+        """The whole buffer, bands and payload, as integers."""
+        return self.buf.view(self._torch.int64 if self.esize == 8 else self._torch.int32)
+
+    def bands(self):
+        return self.buf[:self.lead], self.buf[self.lead + self.n:]
+
+    def guards_intact(self) -> bool:
+        """(outputs) both bands still hold SENTINEL."""
+        lo, hi = self.bands()
+        return bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all())
+
+    def snapshot(self, checksum: bool = False):
+        """A copy of :meth:`ints`, or with *checksum* its integer sum and xor."""
+        return _checksum(self.ints()) if checksum else self.ints().clone()
+
+    def unchanged(self, snap) -> bool:
+        if isinstance(snap, tuple):
+            return _checksum(self.ints()) == snap
+        return bool(self._torch.equal(self.ints(), snap))
+
+    def first_change(self, snap) -> Optional[int]:
+        """Index, relative to the array's first element, of the first changed entry (negative: the band in front)."""
+        if isinstance(snap, tuple):
+            return None
+        where = (self.ints() != snap).nonzero()
+        return int(where[0]) - self.lead if len(where) else None
+
+
+def _checksum(ints) -> Tuple[int, int]:
+    """``(sum mod 2^64, xor)`` of an integer tensor."""
+    import torch
+
+    x = ints.reshape(-1)
+    total = int(x.sum(dtype=torch.int64))
+    while x.numel() > 1:
+        h = x.numel() // 2
+        folded = x[:h] ^ x[h:2 * h]
+        if x.numel() % 2:
+            folded[0] ^= x[2 * h]
+        x = folded
+    return total, int(x[0]) if x.numel() else 0
+
+
+def embed(torch, shape, dtype, shift: int, role: str, values=None, device: str = "cuda") -> Embedded:
+    """Place an array of *shape* ``shift`` elements past a 256-byte boundary of a new buffer, at least :data:`BAND`
+    elements from either end.  *role* ``"in"``: the bands are NaNs of payload :data:`IN_NAN`, the array is *values*;
+    ``"out"``: the bands are SENTINEL, the array NaNs of payload :data:`OUT_NAN`.  The address of the view is ``shift``
+    elements mod 256 bytes, so mod 16 exactly ``shift * itemsize % 16`` (asserted)."""
+    esize = 4 if dtype == torch.float32 else 8
+    assert dtype in (torch.float32, torch.float64) and 0 <= shift < 16 // esize and role in ("in", "out")
+    n = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
+    buf = torch.empty(n + 2 * BAND + 256 // esize + 4, dtype=dtype, device=device)
+    base = buf.data_ptr()
+    assert base % esize == 0
+    lead = BAND + (-base % 256) // esize + shift
+    emb = Embedded(torch, buf, lead, shape, role, shift)
+    ints = emb.ints()
+    if role == "in":
+        ints.fill_(IN_NAN[esize])
+        emb.view.copy_(values)
+    else:
+        buf.fill_(SENTINEL)
+        ints[lead:lead + n] = OUT_NAN[esize]
+    ptr = emb.view.data_ptr()
+    assert ptr % 256 == shift * esize and ptr % 16 == shift * esize % 16, (ptr, shift, esize)
+    assert emb.view.is_contiguous() and tuple(emb.view.shape) == tuple(shape)
+    assert lead >= BAND and buf.numel() - lead - n >= BAND
+    return emb
+
+
+@dataclass(frozen=True)
+class PlacedRun:
+    """One launch of the placement pass: the case, its data ("exact" / "signed"), the transform's name, the
+    placement's name and its non-zero shifts (elements) by slot: a data key, or ``out:<stage>:<output name>``."""
+
+    case: DGCase
+    data: str
+    transform: str
+    placement: str
+    shifts: Tuple[Tuple[str, int], ...] = ()
+    knobs: Tuple[Tuple[str, Any], ...] = ()
+
+    def repro(self) -> str:
+        return json.dumps({"case": asdict(self.case), "data": self.data, "transform": self.transform,
+                           "placement": self.placement, "shifts": dict(self.shifts), "knobs": dict(self.knobs)},
+                          separators=(",", ":"))
+
+    @staticmethod
+    def from_repro(text: str) -> "PlacedRun":
+        d = json.loads(text)
+        return PlacedRun(DGCase(**d["case"]), d["data"], d["transform"], d["placement"],
+                         tuple(sorted(d["shifts"].items())), tuple(sorted(d["knobs"].items())))
+
+
+def slots_of(case: DGCase):
+    """``(inputs, outputs)``: ``[(data key, role, numpy dtype, shape)]`` in the order of first use, role "geometry",
+    "operator" or "field" as in :func:`plant_sites`; ``[(slot, stage, output name, numpy dtype, shape)]``."""
+    ins: Dict[str, Tuple[str, str, Any, Tuple[int, ...]]] = {}
+    outs = []
+    out_dt = np.dtype("float32") if case.dtype == "float32" else np.dtype("float64")
+    for s, (expr, keys) in enumerate(case.stages()):
+        for row in expr.args:
+            for a in row:
+                role = "operator" if _e_axis(expr, a.name) is None else "field" if a is row[-1] else "geometry"
+                ins.setdefault(keys[a.name], (keys[a.name], role, np.dtype(a.dtype), _shape(expr, a.name, case.E)))
+        shape = tuple(case.E if isinstance(d, f.SizeParam) else int(d) for d in expr.shape)
+        outs += [(f"out:{s}:{name}", s, name, out_dt, shape) for name in expr.output_names]
+    return list(ins.values()), outs
+
+
+def placements_of(case: DGCase, full: bool) -> List[Tuple[str, Tuple[Tuple[str, int], ...]]]:
+    """``(placement name, non-zero shifts)`` of the case (deterministic in ``case.seed``): "aligned" first; with *full*
+    every ``only:<role>`` (each geometry and operator array, the first and the last field and output, and one of each
+    in the second launch group of more than K_MAX_FIELDS fields), "all" and "mixed"; else "aligned" and "all".  A
+    float64 array shifts by one element (8 bytes); float32 arrays take 1, 2 and 3 elements in turn ("only:"), or at
+    random ("all", "mixed")."""
+    rng = random.Random(case.seed + 31)
+    ins, outs = slots_of(case)
+    dts = {**{k: dt for k, _, dt, _ in ins}, **{slot: dt for slot, _, _, dt, _ in outs}}
+    turn = [case.seed % 3]
+
+    def nz(slot: str, random_: bool = False) -> int:
+        if dts[slot].itemsize == 8:
+            return 1
+        if random_:
+            return rng.choice([1, 2, 3])
+        turn[0] += 1
+        return 1 + turn[0] % 3
+
+    everything = list(dts)
+    out = [("aligned", ())]
+    if full:
+        fields = [k for k, role, _, _ in ins if role == "field"]
+        oslots = [slot for slot, *_ in outs]
+        only = [("only:geometry", k) for k, role, _, _ in ins if role == "geometry"]
+        only += [("only:operator", k) for k, role, _, _ in ins if role == "operator"]
+        only += [("only:field", fields[0])] + ([("only:last-field", fields[-1])] if len(fields) > 1 else [])
+        only += [("only:field", fields[K_MAX_FIELDS])] if len(fields) > K_MAX_FIELDS else []
+        only += [("only:output", oslots[0])] + ([("only:last-output", oslots[-1])] if len(oslots) > 1 else [])
+        only += [("only:output", oslots[K_MAX_FIELDS])] if len(oslots) > K_MAX_FIELDS and case.kind != "pipeline" else []
+        out += [(name, ((slot, nz(slot)),)) for name, slot in only]
+    out.append(("all", tuple(sorted((slot, nz(slot, True)) for slot in everything))))
+    if full and len(everything) > 1:
+        while True:
+            pick = [slot for slot in everything if rng.random() < 0.5]
+            if 0 < len(pick) < len(everything):
+                break
+        out.append(("mixed", tuple(sorted((slot, nz(slot, True)) for slot in pick))))
+    return out
+
+
+def _c(kind, order, b, op, dtype, E, seed, scale="normal", fuse=True) -> DGCase:
+    return DGCase(kind, order[0], order[1], b, op, dtype, E, eclass_of(E), seed, scale, fuse)
+
+
+def placement_cases(seed: int) -> Dict[str, List[DGCase]]:
+    """The fixed list, by part.  "small": every kind, every matrix-core order, a tiled-only and a triangle order, E in
+    {1, 5, 16, 17, 64, 65, 1003, 4099} (the large E with the low orders: the host references stay cheap); float32 at
+    E in {16, 64, 1024, 4096}, where only the pointer can keep a launch off the matrix cores, and at 17 and 1003;
+    mixed; the fused operator both ways.  These run on exact and on signed data.  "range": an overflow and a
+    subnormal case per dtype.  "rounds": p = 4 at E = 20 004 (several rounds of the walk).  "large": quarter tails on
+    a static walk (grad, div at 100 007) and the dynamic walk (grad at 170 003)."""
+    rng = random.Random(seed + 29)
+    o1, o2, o3, o4, o5, t7, t13 = ORDERS3
+    small = []
+    ops = ["rij", "rji"]
+
+    def add(kind, order, E, b=1, dtype="float64", fuse=True):
+        op = ops[len(small) % 2]
+        small.append(_c(kind, order, b, op[1:] if kind in ("mass", "apply") else op, dtype, E, rng.randrange(1 << 30),
+                        "normal", fuse))
+
+    for order, E in ((o1, 4099), (o2, 1003), (o3, 65), (o4, 17), (o5, 16), (t7, 64), (o4, 1), (o4, 5)):
+        add("grad", order, E)
+    for order, E in ((o1, 1003), (o2, 4099), (o3, 17), (o4, 65), (o5, 5), (t13, 16)):
+        add("div", order, E)
+    for order, E, b in ((o1, 65, 9), (o2, 17, 2), (o3, 1003, 1), (o4, 64, 3), (o5, 16, 2)):
+        add("fm", order, E, b)
+    add("bgrad", o3, 64, 9)
+    add("bdiv", o2, 65, 9)
+    add("divcomp", o4, 17)
+    add("cross", o3, 65)
+    add("fm_ifj", o2, 16, 2)
+    add("fm_jfi", o4, 5, 2)
+    add("fm_fji", o3, 1003, 3)
+    add("mass", o4, 64, 2)
+    add("apply", o5, 17)
+    add("grad2", ORDERS2[2], 65)
+    add("div2", ORDERS2[3], 17)
+    add("lift2", ORDERS2[1], 64, 2)
+    add("pipeline", o3, 65, 2, fuse=True)
+    add("pipeline", o2, 1003, 3, fuse=False)
+    for order, E in ((o4, 16), (o3, 64), (o2, 1024), (o1, 4096), (o4, 17)):
+        add("grad", order, E, dtype="float32")
+    for order, E in ((o4, 64), (o3, 16), (o2, 4096), (o1, 1024), (o3, 1003)):
+        add("div", order, E, dtype="float32")
+    for order, E, b in ((o4, 1024, 2), (o3, 4096, 1), (o2, 16, 3), (o1, 64, 9)):
+        add("fm", order, E, b, dtype="float32")
+    add("bgrad", o3, 64, 9, dtype="float32")
+    add("grad", o3, 64, dtype="mixed")
+    add("fm", o2, 65, 2, dtype="mixed")
+    S = lambda: rng.randrange(1 << 30)   # noqa: E731
+    range_ = [_c("grad", o3, 1, "rij", "float64", 17, S(), "overflow"), _c("div", o2, 1, "rji", "float64", 65, S(), "subnormal"),
+              _c("grad", o2, 1, "rij", "float32", 64, S(), "overflow"), _c("fm", o3, 2, "rij", "float32", 16, S(), "subnormal")]
+    rounds = [_c("grad", o4, 1, "rij", "float64", 20_004, S()), _c("div", o4, 1, "rij", "float64", 20_004, S()),
+              _c("fm", o4, 2, "rij", "float64", 20_004, S()), _c("grad", o3, 1, "rij", "float32", 20_004, S())]
+    large = [_c("grad", o4, 1, "rij", "float64", 100_007, S()), _c("div", o4, 1, "rij", "float64", 100_007, S()),
+             _c("grad", o4, 1, "rij", "float64", 170_003, S())]
+    return {"small": small, "range": range_, "rounds": rounds, "large": large}
+
+
+#: knobs of the three large cases (as :func:`large_cases`): quarter tails on a static walk; the defaults (dynamic walk)
+LARGE_KNOBS = {100_007: (("quarter_tail", True), ("staggered_start", False), ("tail_rounds", -1)), 170_003: ()}
+
+
+def placement_runs(seed: int, part: str) -> List[List[PlacedRun]]:
+    """The runs of *part* ("exact", "signed" or "large"), one list per case, grouped by transform with "aligned" in
+    front of each group."""
+    cases = placement_cases(seed)
+    data = "signed" if part == "signed" else "exact"
+    todo = cases["large"] if part == "large" else cases["small"] + (cases["range"] + cases["rounds"] if part == "exact" else [])
+    out = []
+    for case in todo:
+        runs = []
+        for t in ["auto"] if part == "large" else [tname(t) for t in case.transforms()]:
+            full = t in FULL_TRANSFORMS and part != "large"
+            runs += [PlacedRun(case, data, t, name, shifts, LARGE_KNOBS[case.E] if part == "large" else ())
+                     for name, shifts in placements_of(case, full)]
+        out.append(runs)
+    return out
+
+
+def placement_buckets(run: PlacedRun) -> List[str]:
+    case, t = run.case, run.transform
+    ins, outs = slots_of(case)
+    dts = {**{k: dt for k, _, dt, _ in ins}, **{slot: dt for slot, _, _, dt, _ in outs}}
+    roles = {k: role for k, role, _, _ in ins}
+    b = buckets_of(case, t) + ["place:" + run.placement]
+    sizes = sorted({(dts[slot].itemsize, s * dts[slot].itemsize) for slot, s in run.shifts})
+    b += [f"shift:f{8 * w}:{nbytes}" for w, nbytes in sizes]
+    mfma = t in FULL_TRANSFORMS
+    if mfma and run.placement.startswith("only:"):
+        b.append(f"role:{case.kind}:{run.placement[5:]}")
+    fam = "fm" if case.kind.startswith("fm") else case.kind[1:] if case.kind in ("bgrad", "bdiv") else case.kind
+    if case.dtype == "float32" and fam in ("grad", "div", "fm"):
+        b += [f"shift:f32:{nbytes}:{fam}" for w, nbytes in sizes if w == 4]
+    if (mfma and case.dtype == "float32" and case.kind in F32_MFMA_KINDS and (case.Np, case.Nfp) in F32_MFMA_ORDERS
+            and case.E % 4 == 0 and case.E >= 16 and run.shifts):
+        b.append("path:f32-pointer-fallback")
+    if (mfma and case.dtype == "float64" and case.kind in ("grad", "bgrad") and case.Np in PADDED_ORDERS and case.E >= 16
+            and any(roles.get(slot) == "field" for slot, _ in run.shifts)):
+        b.append("path:lds-dma-8")
+    return b
+
+
+def placement_coverage(seed: int, part: str) -> Counter:
+    """Host-only counterpart of the pass's coverage (:func:`accepted_on_host` per case and transform)."""
+    cnt: Counter = Counter()
+    for runs in placement_runs(seed, part):
+        ok: Dict[str, bool] = {}
+        for run in runs:
+            if run.transform not in ok:
+                ok[run.transform] = accepted_on_host(run.case, _transform_of(run))
+            if ok[run.transform]:
+                cnt.update(placement_buckets(run))
+    return cnt
+
+
+def _transform_of(run: PlacedRun) -> Any:
+    if run.case.kind == "pipeline":
+        return None
+    return {"prepared": True} if run.transform == "prepared" else run.transform
+
+
+def _pair_minimums() -> Dict[str, int]:
+    """Every (kind, role) pair once under "auto" or "mfma"."""
+    m = {}
+    for kind in KINDS + ("pipeline",):
+        roles = ["operator", "field", "output"]
+        roles += ["geometry"] if kind != "apply" else []
+        roles += ["last-field", "last-output"] if kind not in ("grad", "div", "apply", "grad2", "div2") else []
+        m.update({f"role:{kind}:{r}": 1 for r in roles})
+    return m
+
+
+#: minimum runs per bucket of the fixed-seed placement pass, by part (tests/test_dg_placement_cpu.py,
+#: tests/test_gpu_dg_placement.py): every (kind, role) pair under "auto" or "mfma", every float32 shift per family
+PLACEMENT_MINIMUMS = {
+    "exact": {**_pair_minimums(),
+              **{f"shift:f32:{n}:{fam}": 1 for n in (4, 8, 12) for fam in ("grad", "div", "fm")},
+              "place:aligned": 200, "place:only:geometry": 80, "place:only:operator": 80, "place:only:field": 80,
+              "place:only:last-field": 30, "place:only:output": 80, "place:only:last-output": 30, "place:all": 200,
+              "place:mixed": 80, "shift:f64:8": 400, "shift:f32:4": 60, "shift:f32:8": 60, "shift:f32:12": 60,
+              "path:f32-pointer-fallback": 100, "path:lds-dma-8": 30,
+              **{f"family:{k}": 10 for k in KINDS}, "family:pipeline": 20,
+              **{f"order:3d-{n}": 10 for n, _ in ORDERS3}, "order:2d-6": 10, "order:2d-10": 10, "order:2d-15": 10,
+              "dtype:float64": 400, "dtype:float32": 200, "dtype:mixed": 20,
+              "transform:auto": 300, "transform:mfma": 150, "transform:tiled": 50, "transform:generic": 50,
+              "transform:prepared": 20, "E:one": 10, "E:sub-tile": 20, "E:tiles": 200, "E:ragged": 200,
+              "E:static-rounds": 40, "range:overflow": 20, "range:subnormal": 20, "fused:yes": 10, "fused:no": 10},
+    "signed": {"place:aligned": 150, "place:all": 150, "place:mixed": 60, "place:only:field": 60,
+               "place:only:geometry": 60, "place:only:operator": 60, "place:only:output": 60,
+               "shift:f64:8": 300, "shift:f32:4": 50, "shift:f32:8": 50, "shift:f32:12": 50,
+               "path:f32-pointer-fallback": 80, "path:lds-dma-8": 20, "dtype:float64": 300, "dtype:float32": 150,
+               "dtype:mixed": 20, "transform:mfma": 100, "transform:tiled": 40, "transform:generic": 40},
+    "large": {"place:aligned": 3, "place:all": 3, "shift:f64:8": 3, "family:grad": 4, "family:div": 2,
+              "E:quarter-tail": 4, "E:dynamic": 2},
+}
+
+
+class _Knobs:
+    """Set the walk and tail knobs of a large case; every knob is restored on exit (as :func:`run_large`)."""
+
+    def __init__(self, knobs: Dict[str, Any]) -> None:
+        self.knobs = knobs
+
+    def __enter__(self):
+        k = self.knobs
+        self.saved = (_hip.set_tail_rounds(0), _hip.set_grad_quarter_tail(True), _hip.set_div_quarter_tail(True),
+                      _hip.set_grad_staggered_start(True))
+        self._restore()
+        if k.get("tail_rounds") is not None:
+            _hip.set_tail_rounds(k["tail_rounds"])
+        if "quarter_tail" in k:
+            _hip.set_grad_quarter_tail(k["quarter_tail"])
+            _hip.set_div_quarter_tail(k["quarter_tail"])
+        if "staggered_start" in k:
+            _hip.set_grad_staggered_start(k["staggered_start"])
+
+    def _restore(self) -> None:
+        _hip.set_tail_rounds(self.saved[0])
+        _hip.set_grad_quarter_tail(self.saved[1])
+        _hip.set_div_quarter_tail(self.saved[2])
+        _hip.set_grad_staggered_start(self.saved[3])
+
+    def __exit__(self, *exc) -> None:
+        self._restore()
+
+
+def check_inputs(st: Stats, label: str, run, ins: Dict[str, Tuple[Embedded, Any]]) -> bool:
+    """Every input buffer, bands and payload, is bitwise its snapshot."""
+    ok = True
+    for key, (emb, snap) in ins.items():
+        if not emb.unchanged(snap):
+            ok = False
+            at = emb.first_change(snap)
+            st.fail(f"{label}: input {key} changed by the launch" + (f" (first at element {at})" if at is not None else "")
+                    + f"  REPRO {run.repro()}")
+    return ok
+
+
+def nan_entries(got, ref) -> Tuple[int, int]:
+    """``(unwritten, leaked)``: entries of *got* that still hold :data:`OUT_NAN`, and other NaN entries where *ref*
+    has none: only a value read from an input's NaN band can make those."""
+    import torch
+
+    esize = got.element_size()
+    nan = torch.isnan(got)
+    if ref is not None:
+        nan = nan & ~torch.isnan(ref)
+    unwritten = nan & (got.contiguous().view(torch.int64 if esize == 8 else torch.int32) == OUT_NAN[esize])
+    return int(unwritten.sum()), int(nan.sum()) - int(unwritten.sum())
+
+
+def check_outputs(st: Stats, label: str, run, outs: List[Dict[str, Embedded]], refs=None, aligned=None) -> bool:
+    """Guard bands; NaNs from behind an input (``leak:`` bucket: the line says *over-read*) and unwritten entries; with
+    *refs* every output bitwise the exact reference (:func:`_compare`); with *aligned* (integer copies of the outputs
+    of the aligned launch) every output bitwise that launch's."""
+    ok = True
+    for per in outs:
+        for name, emb in per.items():
+            if not emb.guards_intact():
+                ok = False
+                st.fail(f"{label}: output {name}: wrote outside its output  REPRO {run.repro()}")
+    for s, per in enumerate(outs):
+        for name, emb in per.items():
+            unwritten, leaked = nan_entries(emb.view, refs[s][name] if refs is not None else None)
+            if leaked:
+                ok = False
+                st.cov["leak:nan-entries"] += leaked
+                st.fail(f"{label}: output {name}: over-read: {leaked} NaN entries from behind an input  REPRO {run.repro()}")
+            if unwritten:
+                ok = False
+                st.cov["unwritten:entries"] += unwritten
+                st.fail(f"{label}: output {name}: {unwritten} entries never written  REPRO {run.repro()}")
+    if refs is not None:
+        ok = _compare(st, label, refs, [{n: e.view for n, e in per.items()} for per in outs], [], run) and ok
+    if aligned is not None:
+        for per, base in zip(outs, aligned):
+            for name, emb in per.items():
+                st.exact_runs += 1
+                mine = emb.view.contiguous().view(base[name].dtype)
+                bad = int((mine != base[name]).sum())
+                if bad:
+                    ok = False
+                    st.fail(f"{label}: output {name}: {bad} entries differ bitwise from the aligned launch  REPRO {run.repro()}")
+                else:
+                    st.exact_equal += 1
+    return ok
+
+
+def _int_copy(torch, emb: Embedded):
+    return emb.view.contiguous().view(torch.int64 if emb.esize == 8 else torch.int32).clone()
+
+
+def _placed_case(torch, st: Stats, runs: Sequence[PlacedRun], checksum: bool = False) -> None:
+    """All runs of one case: its data and references once, every input embedded once per shift (the launches must
+    leave them unchanged, which every run checks), fresh outputs per run."""
+    case, data = runs[0].case, runs[0].data
+    refs = bounds = None
+    if data == "exact":
+        if case.E > 50_000:
+            dev, scales, sig = device_data(torch, case)
+            refs = _device_refs(torch, case, dev, scales, sig, st)
+        else:
+            arrays, mants, scales, sig = host_data(case)
+            dev = {k: torch.from_numpy(np.ascontiguousarray(a)).cuda() for k, a in arrays.items()}
+            refs = references(torch, case, arrays, mants, scales, sig, dev, st)
+    else:
+        nrng = np.random.default_rng(case.seed)
+        host, dev = {}, {}
+        for expr, keys in case.stages():
+            for nm, k in keys.items():
+                if k not in host:
+                    host[k] = (nrng.random(_shape(expr, nm, case.E)) * 2 - 1).astype(expr.arg_to_dtype[nm])
+                    dev[k] = torch.from_numpy(host[k]).cuda()
+        bounds = []
+        for expr, keys in case.stages():
+            nb = ref_.bound_terms(expr.get_subscripts(), _extent(expr, case.E), 3)
+            bounds.append({name: ref_.bounded_reference(expr.get_subscripts(), [host[keys[a.name]] for a in row]) + (nb,)
+                           for name, row in zip(expr.output_names, expr.args)})
+    u = ref_.U32 if case.dtype == "float32" else ref_.U64
+    ins_slots, out_slots = slots_of(case)
+    cache: Dict[Tuple[str, int], Tuple[Embedded, Any]] = {}
+    aligned: Dict[str, Any] = {}     # transform -> integer copies of the aligned launch's outputs (None: not accepted)
+    for run in runs:
+        t = run.transform
+        if run.placement != "aligned" and aligned.get(t) is None:
+            continue     # the aligned launch of this (case, transform) is not accepted
+        shifts = dict(run.shifts)
+        ins = {}
+        for key, _, dt, shape in ins_slots:
+            at = (key, shifts.get(key, 0))
+            if at not in cache:
+                emb = embed(torch, shape, getattr(torch, dt.name), at[1], "in", dev[key])
+                cache[at] = (emb, emb.snapshot(checksum))
+            ins[key] = cache[at]
+        outs: List[Dict[str, Embedded]] = [{} for _ in case.stages()]
+        for slot, s, name, dt, shape in out_slots:
+            outs[s][name] = embed(torch, shape, getattr(torch, dt.name), shifts.get(slot, 0), "out")
+        label = f"placement {run.placement} {data} {t}: {case.kind} Np={case.Np} b={case.b} {case.op} {case.dtype}" \
+                f" E={case.E} {case.scale}"
+        try:
+            with _Knobs(dict(run.knobs)):
+                info = launch(torch, case, {k: e.view for k, (e, _) in ins.items()}, _transform_of(run),
+                              [{n: e.view for n, e in per.items()} for per in outs])
+        except NotImplementedError as exc:
+            if run.placement == "aligned":
+                st.cov["not-accepted:" + t] += 1
+                aligned[t] = None
+            else:
+                st.fail(f"{label}: refused ({exc}), but the aligned launch is accepted  REPRO {run.repro()}")
+            continue
+        except f.InvalidParameterError as exc:
+            st.fail(f"{label}: refused ({exc})  REPRO {run.repro()}")
+            continue
+        st.cov.update(placement_buckets(run) + _walk_buckets(case, info))
+        check_inputs(st, label, run, ins)
+        f64_family = case.dtype == "float64"
+        base = aligned.get(t) if (data == "signed" and f64_family and run.placement != "aligned") else None
+        check_outputs(st, label, run, outs, refs, base)
+        if run.placement == "aligned":
+            aligned[t] = [{n: _int_copy(torch, e) for n, e in per.items()} for per in outs]
+        if bounds is not None:
+            bk = placement_buckets(run)
+            for per, bnd, base_ in zip(outs, bounds, aligned[t]):
+                for name, emb in per.items():
+                    if run.placement != "aligned" and torch.equal(_int_copy(torch, emb), base_[name]):
+                        continue     # bitwise the aligned launch, which was held to the bound
+                    r, ar, nb = bnd[name]
+                    ratio = ref_.bound_ratio(emb.view.cpu().numpy(), r, ar, nb, u)
+                    for b_ in bk:
+                        st.worst[b_] = max(st.worst.get(b_, 0.0), ratio)
+                    if ratio > 1:
+                        st.fail(f"{label}: output {name}: |got - ref| = {ratio:.3g} x the bound  REPRO {run.repro()}")
+
+
+def run_placement(seed: int, part: str = "all") -> Stats:
+    """Every case of :func:`placement_cases` with its operands at every accepted address offset (DESIGN.md section
+    3, "Alignment"): *part* "exact", "signed", "large" or "all"."""
+    import torch
+
+    st = Stats(f"dg placement {part} seed={seed}")
+    st.cov["leak:nan-entries"] += 0
+    for p in ("exact", "signed", "large") if part == "all" else (part,):
+        for runs in placement_runs(seed, p):
+            _placed_case(torch, st, runs, checksum=p == "large")
+    return st
+
+
+def repro_placement(text: str) -> Stats:
+    """Replay one ``REPRO`` line of the placement pass (the aligned launch of its case and transform first)."""
+    import torch
+
+    run = PlacedRun.from_repro(text)
+    st = Stats("repro")
+    st.cov["leak:nan-entries"] += 0
+    first = [PlacedRun(run.case, run.data, run.transform, "aligned", (), run.knobs)] if run.placement != "aligned" else []
+    _placed_case(torch, st, first + [run], checksum=run.case.E > 50_000)
+    return st
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--placement":
+        st = run_placement(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+        print(st.report())
+        sys.exit(1 if st.failures else 0)
+    if len(sys.argv) > 2 and sys.argv[1] == "--repro" and "placement" in json.loads(sys.argv[2]):
+        st = repro_placement(sys.argv[2])
+        print(st.report())
+        sys.exit(1 if st.failures else 0)
     if len(sys.argv) > 2 and sys.argv[1] == "--repro":
         import torch
 
