@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "fe_split_alloc", "fe_split_free", "fe_split_info", "fe_split_stats", "fe_split_reserve", "fe_split_trim", "fe_launch_f32", "fe_set_tail_rounds", "fe_set_tail_min_rounds",
     "fe_set_cu_limit", "fe_set_phase_priority_p5", "fe_set_div_interleave", "fe_set_div_quarter_tail", "fe_set_grad_quarter_tail", "fe_set_grad_staggered_start", "fe_last_launch_info", "fe_stream_retired", "fe_capture_id", "fe_graph_retired", "fe_tail_stats", "fe_tail_check", "fe_tail_plant", "fe_set_temporal_loads_mib", "fe_set_write_through_mib",
     "fe_geomadj_f64", "fe_facemass_adj_f64", "fe_opgrad_plan", "fe_opgrad_f64", "fe_facemass_opgrad_f64",
-    "fe_facemass_acc_f64", "fe_axpby",
+    "fe_facemass_acc_f64", "fe_axpby", "fe_grad3d_acc_f64", "fe_div3d_acc_f64",
 )
 FAMILY_F32 = 0x100    # FE_FAMILY_F32
 
@@ -275,6 +275,9 @@ def load_library() -> C.CDLL:
     lib.fe_facemass_acc_f64.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64,
                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                         C.c_void_p]
+    for fn in (lib.fe_grad3d_acc_f64, lib.fe_div3d_acc_f64):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p]
     lib.fe_axpby.restype = C.c_int
     lib.fe_axpby.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_void_p]
     _lib = lib
@@ -407,6 +410,19 @@ def facemass_acc(J: int, R: int, v: Sequence[int], out: Sequence[int], E: int, N
         raise InvalidParameterError("face-mass: need as many outputs as fields")
     check(load_library().fe_facemass_acc_f64(J, R, _ptr_array(v), _ptr_array(out), E, Np, nf, Nfp, len(v), layout_flags,
                                              float(alpha), float(beta), stream))
+
+
+def grad3d_acc(J: int, D: int, u: int, out: int, E: int, Np: int, alpha: float, beta: float, op_flags: int = 0,
+               stream: int = 0) -> None:
+    """``out <- alpha * grad(u) + beta * out`` inside the matrix-core kernel (fe_grad3d_acc_f64).  NotImplementedError: the
+    order has no accumulating kernel (tetrahedra p = 1..4)."""
+    check(load_library().fe_grad3d_acc_f64(J, D, u, out, E, Np, op_flags, float(alpha), float(beta), stream))
+
+
+def div3d_acc(J: int, D: int, u: int, out: int, E: int, Np: int, alpha: float, beta: float, op_flags: int = 0,
+              stream: int = 0) -> None:
+    """``out <- alpha * div(u) + beta * out`` inside the matrix-core kernel (fe_div3d_acc_f64); as :func:`grad3d_acc`."""
+    check(load_library().fe_div3d_acc_f64(J, D, u, out, E, Np, op_flags, float(alpha), float(beta), stream))
 
 
 def axpby(out: int, x: int, n: int, alpha: float, beta: float, float64: bool = True, stream: int = 0) -> None:

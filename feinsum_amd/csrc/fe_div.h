@@ -86,6 +86,8 @@ struct DivGeom {
     static constexpr int J_ROW_CHUNKS = TEL / 2, J_CHUNKS = NJ * J_ROW_CHUNKS, J_INSTR = (J_CHUNKS + 63) / 64;
     static constexpr int SUB_CHUNKS = SUB_D / 2, SUB_INSTR = (SUB_CHUNKS + 63) / 64;
     static constexpr int LOADS = NPLANES * P_INSTR + J_INSTR, STORES = NOUT * M * SUB_INSTR;
+    static constexpr int ACC_LOADS = STORES;            // kAcc: a unit reads every 16-byte chunk it is about to write (older than
+                                                        // every load a counted wait waits for: in no count, see div3d_mfma_body)
     // ALDS div ("plane streaming"): the ND u planes of a tile pass through TWO plane buffers one after
     // the other and the second buffer doubles as the output transposition buffer -- with all ND planes
     // and a separate o buffer resident (86 + 29 KB for four waves at Np = 56) there is no room for
@@ -121,12 +123,24 @@ struct DivGeom {
 // (fe_common.h, dynamic walk); `tail` = the launch's counters (null: static walk), `t_static` = statically walked tiles.
 // kIlv (round 5; short launches of the plain div, static walk): the B fragments are built k-quad by k-quad BETWEEN the MFMA groups
 // of the same wave instead of all up front -- see the loop.
+// kAcc (plain div of tetrahedra: register fragments, static walk, the plain operator, all B fragments up front, the walk not
+// split): out <- alpha (the sum above) + beta out (axpby_combine).  With beta != 0 a unit reads the 16-byte chunks it is about to
+// write -- every chunk by the lane that stores it, so nothing has to be ordered across waves -- into registers, by plain loads
+// issued behind the unit's B fragments and IN FRONT OF the next unit's loads, so that they run under the unit's MFMAs and return
+// ahead of the prefetch.  In issue order a unit is  O(unit) L(unit + 1) S(unit):  younger than L(unit + 1) at the top of the
+// next unit are the stores alone, as without kAcc -- the old-value loads are older than every load a counted wait waits for, so
+// no count has to include them (DivGeom::ACC_LOADS says how many there are).  The loads are the compiler's own: it places its
+// own wait in front of their first use (it does not see the LDS-DMA prefetch and waits for that too, as in fe_facemass.h).
+// With beta == 0 nothing is read: one scalar branch per unit.  The remainder code accumulates alike.
 template <int NP, int M, int kDbg = 0, int MODE = 0, int ND = 3, bool ALDS = false, bool W8 = false, bool kPrep = false,
-          bool kDyn = false, bool kIlv = false>
+          bool kDyn = false, bool kIlv = false, bool kAcc = false>
 __device__ __forceinline__ void div3d_mfma_body(
     const double* __restrict__ J, const double* __restrict__ D, const void* __restrict__ prep, const FieldPtrs& P,
     int nb, int64_t E, int64_t nTiles, int op_flags, int jes, const unsigned bid, const unsigned nblk,
-    const GradFields* __restrict__ Q = nullptr, unsigned* __restrict__ tail = nullptr, int64_t t_static = 0) {
+    const GradFields* __restrict__ Q = nullptr, unsigned* __restrict__ tail = nullptr, int64_t t_static = 0,
+    const double alpha = 1.0, const double beta = 0.0) {
+    static_assert(!kAcc || (MODE == 0 && ND == 3 && !ALDS && !W8 && !kPrep && !kDyn && !kIlv && kDbg == 0),
+                  "accumulating launches: plain div of tetrahedra, register fragments, static walk, B fragments up front");
     static_assert(!kPrep || (!ALDS && MODE == 0 && ND == 3), "prepared operators: plain div of tetrahedra");
     static_assert(!kDyn || ((MODE == 0 || MODE == 4) && !ALDS && !W8 && !kPrep) || ((MODE == 4 || MODE == 0) && ND == 3 && W8),
                   "dynamic walk: div (tetrahedra, triangles), grad by components (triangles), or the eight-wave kernels (p = 5)");
@@ -168,7 +182,7 @@ __device__ __forceinline__ void div3d_mfma_body(
             for (int k = 0; k < nb; ++k) {
                 const double* uk = field_in(P, k);
                 double* ok = field_out(P, k);
-                if (MODE == 0 && ND == 3) div3d_item(J, Dsrc, uk, ok, E, NP, e, i, opT);
+                if (MODE == 0 && ND == 3) div3d_item<kAcc>(J, Dsrc, uk, ok, E, NP, e, i, opT, alpha, beta);
                 else if (MODE == 0) div_nd_item(J, Dsrc, uk, ok, E, NP, ND, e, i, opT);
                 else if (MODE == 4) grad_nd_item(J, Dsrc, uk, ok, E, NP, ND, e, i, opT);
                 else if (MODE == 5) {
@@ -218,7 +232,7 @@ __device__ __forceinline__ void div3d_mfma_body(
     // boundary between the two classes of physical memory in the middle of the output array then splits (DESIGN.md
     // section 3d: 0.1914 against 0.1993 ms at E = 1e6; 1.3 % slower than the plain walk anywhere else)
     const int64_t half_tiles = (nTiles + 1) / 2;
-    const bool split_walk = (op_flags & kDivWalkSplit) != 0;
+    const bool split_walk = !kAcc && (op_flags & kDivWalkSplit) != 0;
     auto phys = [&](int64_t t) -> int64_t { return split_walk ? ((t & 1) ? half_tiles + (t >> 1) : (t >> 1)) : t; };
     auto issue_loads = [&](int64_t tile, int fk, bool with_j) {
         const int64_t e0 = phys(tile) * G::TEL;
@@ -879,6 +893,7 @@ __device__ __forceinline__ void div3d_mfma_body(
     unsigned* const counter = tail_pool_counters(tail, pool);
     unsigned* const done = tail_pool_reports(counter);
     bool pending = false, reported = false;
+    const bool acc_reads = kAcc && beta != 0.0;   // wave-uniform (a kernel argument)
     auto static_next = [&](int64_t t) -> int64_t { return (t < t_static && t + stride < t_static) ? t + stride : -1; };
     // the next unit's tile under the dynamic walk (called once per unit, in front of the next unit's loads and behind the wait for
     // this unit's: vector-memory ops in issue order [ticket or report] L(next unit) S(this unit))
@@ -1076,6 +1091,22 @@ __device__ __forceinline__ void div3d_mfma_body(
 #pragma unroll
                 for (int k = 0; k < ND * ND; ++k) asm volatile("" : "+v"(jkeep[m][k]));
         }
+        // ---- kAcc: the chunks this unit will overwrite, ahead of the next unit's loads (see the head of this function)
+        v2d old[kAcc ? M : 1][kAcc ? G::SUB_INSTR : 1];
+        if constexpr (kAcc) {
+            if (acc_reads) {
+#pragma unroll
+                for (int m = 0; m < M; ++m) {
+                    const double* op = out + (e0 + 16 * m) * NP;
+#pragma unroll
+                    for (int c = 0; c < G::SUB_INSTR; ++c) {
+                        const int qc = c * 64 + lane;
+                        if ((c + 1) * 64 <= G::SUB_CHUNKS || qc < G::SUB_CHUNKS)
+                            old[m][c] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(op + 2 * qc));
+                    }
+                }
+            }
+        }
         resolve_next_tile(tile, fk, next_new_tile, nt);   // (dynamic walk: the ticket asked for earlier is read here)
         if (nt < tEnd && !x_no_loads) issue_loads(nt, nk, next_new_tile);
         FE_TILE_STAMP(x_stamps, smem + G::LDS_BYTES, wave, lane, dbg_it, 1);   // B fragments built, the next unit's loads issued
@@ -1212,7 +1243,11 @@ __device__ __forceinline__ void div3d_mfma_body(
             for (int c = 0; c < G::SUB_INSTR; ++c) {
                 const int qc = c * 64 + lane;
                 if ((c + 1) * 64 <= G::SUB_CHUNKS || qc < G::SUB_CHUNKS) {
-                    const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * tile_dst_chunk<NP>(qc));
+                    v2d val = *reinterpret_cast<const v2d*>(ob + 2 * tile_dst_chunk<NP>(qc));
+                    if constexpr (kAcc) {
+                        if (acc_reads) val = axpby_combine(v2d{alpha, alpha}, val, v2d{beta, beta}, old[m][c]);
+                        else val = v2d{alpha, alpha} * val;
+                    }
                     if (x_no_stores) { if (val[0] == 1.2345e-300) op[2 * qc] = val[1]; }
                     else __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * qc));
                 }
@@ -1327,6 +1362,15 @@ template <int NP, int kDbg = 0>
 __global__ __launch_bounds__(256, 2) void div3d_mfma_ilv_kernel(
     const double* __restrict__ J, const double* __restrict__ D, FieldPtrs P, int nb, int64_t E, int64_t nTiles, int opT) {
     div3d_mfma_body<NP, 1, kDbg, 0, 3, false, false, false, false, true>(J, D, nullptr, P, nb, E, nTiles, opT, 0, blockIdx.x, gridDim.x);
+}
+
+// out <- alpha (the div sum) + beta out: tetrahedra p = 1..4, one field, static walk (div3d_mfma_body, kAcc)
+template <int NP, int M>
+__global__ __launch_bounds__(256, 2) void div3d_mfma_acc_kernel(
+    const double* __restrict__ J, const double* __restrict__ D, FieldPtrs P, int64_t E, int64_t nTiles, int opT, double alpha,
+    double beta) {
+    div3d_mfma_body<NP, M, 0, 0, 3, false, false, false, false, false, true>(J, D, nullptr, P, 1, E, nTiles, opT, 0, blockIdx.x,
+                                                                             gridDim.x, nullptr, nullptr, 0, alpha, beta);
 }
 
 // the plain single-field div with a dynamic walk (see fe_common.h)

@@ -9,9 +9,11 @@
 namespace fe {
 
 // div: out[e,i] = sum_{x,r,j} J[x,r,e] D[r,i,j] u[x,e,j]
+// kAcc: out[e,i] = alpha * (that sum) + beta * out[e,i]; beta == 0 does not read the output (axpby_combine, fe_common.h)
+template <bool kAcc = false>
 __device__ __forceinline__ void div3d_item(const double* __restrict__ J, const double* __restrict__ D,
                                            const double* __restrict__ u, double* __restrict__ out, int64_t E,
-                                           int Np, int64_t e, int i, int opT) {
+                                           int Np, int64_t e, int i, int opT, double alpha = 1.0, double beta = 0.0) {
     double jac[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) jac[k] = J[(int64_t)k * E + e];
@@ -31,7 +33,12 @@ __device__ __forceinline__ void div3d_item(const double* __restrict__ J, const d
         const double ju2 = jac[2] * a + jac[5] * b + jac[8] * c;
         acc += d0[j * sj] * ju0 + d1[j * sj] * ju1 + d2[j * sj] * ju2;
     }
-    out[e * Np + i] = acc;
+    if constexpr (kAcc) {
+        double* o = out + (e * Np + i);
+        *o = beta != 0.0 ? axpby_combine(alpha, acc, beta, *o) : alpha * acc;
+    } else {
+        out[e * Np + i] = acc;
+    }
 }
 
 __global__ __launch_bounds__(256) void div3d_generic_kernel(
@@ -40,6 +47,15 @@ __global__ __launch_bounds__(256) void div3d_generic_kernel(
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (E - e_begin) * Np) return;
     div3d_item(J, D, u, out, E, Np, e_begin + idx / Np, (int)(idx % Np), opT);
+}
+
+// the accumulating form (fe_div3d_acc_f64) for launches of fewer elements than a wave tile
+__global__ __launch_bounds__(256) void div3d_generic_acc_kernel(
+    const double* __restrict__ J, const double* __restrict__ D, const double* __restrict__ u,
+    double* __restrict__ out, int64_t E, int Np, int64_t e_begin, int opT, double alpha, double beta) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (E - e_begin) * Np) return;
+    div3d_item<true>(J, D, u, out, E, Np, e_begin + idx / Np, (int)(idx % Np), opT, alpha, beta);
 }
 
 // grad / div of ND-dimensional elements (ND = 2: triangles), entry (e, i): J [ND][ND][E], D [ND][Np][Np]

@@ -62,6 +62,7 @@ struct GradGeom {
                                                        // (J only with the first field of a tile) ...
     static constexpr int PLANE_STORES = M * SUB_INSTR; // ... and stores, per output plane
     static constexpr int STORES = 3 * PLANE_STORES;
+    static constexpr int ACC_LOADS = STORES;           // kAcc: a unit reads every 16-byte chunk it is about to write
     struct WaveLds {             // input side, one per wave from the start of the block's LDS
         double u[2][TILE_D];     // prefetch double buffer
         double j[2][9 * TEL];    // J[x*3+r][e0 + 0..TEL-1], double buffered (by tile)
@@ -79,7 +80,7 @@ struct GradGeom {
     static constexpr int OP_BYTES = (OP_D * 8 + 15) / 16 * 16;
     static constexpr int LDS_BYTES = IN_BYTES + (OUT_BYTES > OP_BYTES ? OUT_BYTES : OP_BYTES);
     static_assert(4 * TG >= NP, "row permutation must cover every i");
-    static_assert(LOADS + STORES <= 60, "counted vmcnt must fit the 6-bit field");
+    static_assert(LOADS + STORES + ACC_LOADS <= 60, "counted vmcnt must fit the 6-bit field");
     static_assert(2 * LDS_BYTES <= 160 * 1024, "two blocks per CU");
 };
 
@@ -133,12 +134,47 @@ __device__ __forceinline__ void grad3d_item(const double* __restrict__ J, const 
             J[(int64_t)(x * 3 + 2) * E + e] * t2;
 }
 
+// the accumulating form: out[x,e,i] = alpha * (that sum) + beta * out[x,e,i]; beta == 0 does not read the output
+// (axpby_combine, fe_common.h).  A function of its own, so that the plain one and every kernel it is inlined into stay as they are.
+__device__ __forceinline__ void grad3d_item_acc(const double* __restrict__ J, const double* __restrict__ D,
+                                                const double* __restrict__ u, double* __restrict__ out, int64_t E,
+                                                int Np, int64_t e, int i, int opT, double alpha, double beta) {
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+    const double* ue = u + e * Np;
+    const int si = opT ? 1 : Np, sj = opT ? Np : 1;
+    const double* d0 = D + (int64_t)0 * Np * Np + (int64_t)i * si;
+    const double* d1 = D + (int64_t)1 * Np * Np + (int64_t)i * si;
+    const double* d2 = D + (int64_t)2 * Np * Np + (int64_t)i * si;
+#pragma unroll 5
+    for (int j = 0; j < Np; ++j) {
+        const double uj = ue[j];
+        t0 += d0[j * sj] * uj;
+        t1 += d1[j * sj] * uj;
+        t2 += d2[j * sj] * uj;
+    }
+    for (int x = 0; x < 3; ++x) {
+        const double v = J[(int64_t)(x * 3 + 0) * E + e] * t0 + J[(int64_t)(x * 3 + 1) * E + e] * t1 +
+                         J[(int64_t)(x * 3 + 2) * E + e] * t2;
+        double* o = out + (((int64_t)x * E + e) * Np + i);
+        *o = beta != 0.0 ? axpby_combine(alpha, v, beta, *o) : alpha * v;
+    }
+}
+
 __global__ __launch_bounds__(256) void grad3d_generic_kernel(
     const double* __restrict__ J, const double* __restrict__ D, const double* __restrict__ u,
     double* __restrict__ out, int64_t E, int Np, int64_t e_begin, int opT) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (E - e_begin) * Np) return;
     grad3d_item(J, D, u, out, E, Np, e_begin + idx / Np, (int)(idx % Np), opT);
+}
+
+// the accumulating form (fe_grad3d_acc_f64) for launches of fewer elements than a wave tile
+__global__ __launch_bounds__(256) void grad3d_generic_acc_kernel(
+    const double* __restrict__ J, const double* __restrict__ D, const double* __restrict__ u,
+    double* __restrict__ out, int64_t E, int Np, int64_t e_begin, int opT, double alpha, double beta) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (E - e_begin) * Np) return;
+    grad3d_item_acc(J, D, u, out, E, Np, e_begin + idx / Np, (int)(idx % Np), opT, alpha, beta);
 }
 
 // wait until at most BASE + nx * PER vector-memory operations are outstanding
@@ -220,6 +256,23 @@ constexpr int kDbgTileLdsBytes = 4 * 128;
 #define FE_TILE_STAMPS_OUT(ENABLED, LDS_END, WAVE, LANE, GLOBAL_WAVE) do {} while (0)
 #endif
 
+// kAcc (grad3d_mfma_body): the 16-byte chunks of one [16][NP] output sub-tile at `op`, every chunk into the lane that will store it
+template <int N>
+struct GradOldValues {
+    v2d v[2][N];   // two planes: the one being combined and, where the registers allow, the next
+};
+template <>
+struct GradOldValues<0> {};
+template <int NP, int N>
+__device__ __forceinline__ void grad_load_old(const double* op, int lane, v2d (&dst)[N]) {
+    constexpr int CHUNKS = 16 * NP / 2;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        const int qc = c * 64 + lane;
+        if ((c + 1) * 64 <= CHUNKS || qc < CHUNKS) dst[c] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(op + 2 * qc));
+    }
+}
+
 // kDbg: experiment flags, 0 in the product build (tools/fe_check.cpp "ab" mode uses the others
 // through build/libfeinsum_hip_exp.so): 1 skip MFMAs, 2 skip stores, 4 plain (temporal) stores,
 // 8 skip loads, 16 plain (temporal) loads, 32 per-wave timestamps, 64 no priority balancing.
@@ -235,15 +288,28 @@ constexpr int kDbgTileLdsBytes = 4 * 128;
 // never meet.  D itself is still needed by the remainder code.
 // kDyn (plain single-field launches): the LAST rounds of the walk are handed out by tickets -- see "dynamic tail" below;
 // `tail` = the launch's ticket counters (null: static walk), `t_static` = number of statically walked tiles.
-template <int NP, int M, int kDbg = 0, bool kPlain = true, bool kPrep = false, bool kDyn = false>
+// kAcc (plain launches, static walk, the plain operator; full tiles with the separate fragment build, non-temporal stores):
+// out <- alpha (the sum above) + beta out (axpby_combine).  With beta != 0 a unit reads the 16-byte chunks it is about to write
+// -- every chunk by the lane that stores it, so nothing has to be ordered across waves -- into registers by plain loads, which
+// the compiler waits for in front of their first use.  kAccAhead (p = 1..3): one plane ahead -- plane 0 of a sub-tile in front
+// of its stage 1, so that the latency runs under the MFMAs, the next plane's while a plane is combined and stored; p = 4 has no
+// registers for a second plane's 20 beside 126 of A fragments and 56 of accumulators, and reads each plane's old values in
+// front of that plane's stage 2 (their latency is covered by the partner wave only).  In issue order a unit is
+// L(unit + 1) | [O S](plane 0) [O S](plane 1) [O S](plane 2), all of it younger than L(unit + 1): the counted waits at the top of
+// the next unit count the ACC_LOADS old-value loads beside the stores, under the wave-uniform beta != 0 branch.  With beta == 0
+// nothing is read.  The remainder code accumulates alike.
+template <int NP, int M, int kDbg = 0, bool kPlain = true, bool kPrep = false, bool kDyn = false, bool kAcc = false>
 __device__ __forceinline__ void grad3d_mfma_body(
     const GradFields& P, const double* __restrict__ D, const void* __restrict__ prep, int nb, int nx_, int64_t E,
     int64_t nTiles, int op_flags, const unsigned bid, const unsigned nblk, unsigned* __restrict__ tail = nullptr,
-    int64_t t_static = 0) {
+    int64_t t_static = 0, const double alpha = 1.0, const double beta = 0.0) {
     static_assert(!kDyn || (kPlain && !kPrep), "dynamic walk: plain launches of one field");
+    static_assert(!kAcc || (kPlain && !kPrep && !kDyn && kDbg == 0), "accumulating launches: plain grad, static walk, the plain operator");
+    constexpr bool kAccAhead = kAcc && NP != 35;
+    const bool acc_reads = kAcc && beta != 0.0;   // wave-uniform (a kernel argument)
     const int opT = op_flags & 1;                                  // operator stored transposed
     const bool tload = (op_flags & kOpLoadsTemporal) != 0;         // the u tiles by plain loads (fe_common.h)
-    const bool wthrough = kPlain && (op_flags & kOpStoresWriteThrough) != 0;   // short launches: fe_common.h
+    const bool wthrough = kPlain && !kAcc && (op_flags & kOpStoresWriteThrough) != 0;   // short launches: fe_common.h
     const int nx = kPlain ? 3 : nx_;
     using G = GradGeom<NP, M>;
     using WaveLds = typename G::WaveLds;
@@ -251,7 +317,7 @@ __device__ __forceinline__ void grad3d_mfma_body(
 #ifdef FE_EXPERIMENTS
     const unsigned long long t_entry = (kDbg & 32) ? __builtin_amdgcn_s_memrealtime() : 0;
 #endif
-    if constexpr (kPlain && !kPrep && !kDyn && M == 1) {   // (fe_common.h: every second CU of an XCD starts half a tile period late)
+    if constexpr (kPlain && !kPrep && !kDyn && M == 1 && !kAcc) {   // (fe_common.h: every second CU of an XCD starts half a tile period late)
         if ((op_flags & kOpStaggeredStart) && ((bid >> 3) & 1))
             for (int i = 0; i < kStaggerSleeps; ++i) __builtin_amdgcn_s_sleep(16);
     }
@@ -286,7 +352,7 @@ __device__ __forceinline__ void grad3d_mfma_body(
     // Same products in the same order as a full tile: bitwise the same results.
     int64_t q_e0 = -1;            // first element of this wave's quarter tile, or -1
     int64_t t_full = nTiles;      // tiles walked as full tiles
-    if constexpr (kPlain && !kPrep && M == 1) {
+    if constexpr (kPlain && !kPrep && M == 1 && !kAcc) {
         if ((op_flags & kOpQuarterTail) && nb == 1 && !(kDyn && tail != nullptr)) {
             const int64_t r = nTiles % stride;
             if (r > 0 && 4 * r <= stride && nTiles > stride) {   // (what is possible; the launcher sets the flag by its own, narrower rule)
@@ -300,7 +366,7 @@ __device__ __forceinline__ void grad3d_mfma_body(
 
     double afrag[G::RT][G::KS];
     // (one sub-tile per wave tile) stage 1 of the wave's first unit runs with the fragment build: see the prologue
-    constexpr bool kFusedFirst = (M == 1) && !kPrep && !kDyn && !(x_no_mfma || x_no_stores || x_plain_stores || x_no_loads || x_plain_loads || x_no_balance || x_split_walk);   // (the dynamic-walk kernels have no registers to spare for it)
+    constexpr bool kFusedFirst = (M == 1) && !kPrep && !kDyn && !kAcc && !(x_no_mfma || x_no_stores || x_plain_stores || x_no_loads || x_plain_loads || x_no_balance || x_split_walk);   // (the dynamic-walk kernels have no registers to spare for it)
     v4d acc_first[G::RT];
     bool first_ready = false;
     // experiment (kDbg & 128): the walk covers both halves of the element range at once (see fe_div.h, kDbg & 4)
@@ -331,7 +397,8 @@ __device__ __forceinline__ void grad3d_mfma_body(
             for (int k = 0; k < nb; ++k) {
                 const double* uk = grad_field_u(P, k);
                 if (kPlain) {
-                    grad3d_item(P.j[0], Dsrc, uk, grad_plane_out(P, k, 0), E, NP, e, i, opT);
+                    if constexpr (kAcc) grad3d_item_acc(P.j[0], Dsrc, uk, grad_plane_out(P, k, 0), E, NP, e, i, opT, alpha, beta);
+                    else grad3d_item(P.j[0], Dsrc, uk, grad_plane_out(P, k, 0), E, NP, e, i, opT);
                 } else {
                     double* const o[3] = {grad_plane_out(P, k, 0), grad_plane_out(P, k, 1), grad_plane_out(P, k, 2)};
 #pragma unroll
@@ -355,6 +422,11 @@ __device__ __forceinline__ void grad3d_mfma_body(
         out_x[2] = kPlain ? out_x[0] + 2 * E * NP : grad_plane_out(P, fk, 2);
         int obuf = 0;
         const int64_t e0 = phys(tile_) * G::TEL;
+        // kAcc: the old values of plane q = 3 m + x of the unit, in old.v[q & 1] (see the head of this function)
+        GradOldValues<kAcc ? G::SUB_INSTR : 0> old;
+        if constexpr (kAccAhead) {
+            if (acc_reads) grad_load_old<NP>(out_x[0] + e0 * NP, lane, old.v[0]);
+        }
 #pragma unroll
         for (int m = 0; m < M; ++m) {
             // ---- stage 1 on sub-tile m
@@ -392,6 +464,17 @@ __device__ __forceinline__ void grad3d_mfma_body(
                 if (!kPlain && out_x[x] == nullptr) continue;   // plane not asked for (wave-uniform)
                 double* ob = LO->o[kPlain ? (m * 3 + x) & 1 : obuf];
                 obuf ^= 1;
+                if constexpr (kAcc) {
+                    if (acc_reads) {
+                        // (plane q = 3 m + x; q + 1 is plane (x + 1) % 3 of sub-tile m + (x + 1) / 3)
+                        if constexpr (!kAccAhead) {
+                            grad_load_old<NP>(out_x[x] + (e0 + 16 * m) * NP, lane, old.v[(3 * m + x) & 1]);
+                        } else {
+                            if (3 * m + x + 1 < 3 * M)
+                                grad_load_old<NP>(out_x[(x + 1) % 3] + (e0 + 16 * (m + (x + 1) / 3)) * NP, lane, old.v[(3 * m + x + 1) & 1]);
+                        }
+                    }
+                }
                 const double j0 = jt[(x * 3 + 0) * G::TEL + 16 * m + n];
                 const double j1 = jt[(x * 3 + 1) * G::TEL + 16 * m + n];
                 const double j2 = jt[(x * 3 + 2) * G::TEL + 16 * m + n];
@@ -404,6 +487,17 @@ __device__ __forceinline__ void grad3d_mfma_body(
                     const double v = __builtin_fma(j2, t2, __builtin_fma(j1, t1, j0 * t0));   // explicit: no contraction choice left to the compiler
                     const int i = G::TG * g + k;
                     if (G::TG * 3 + k < NP || i < NP) ob[n * NP + i] = v;
+                }
+                if constexpr (kAcc) {
+                    // The padding slots of the last row tile (s >= 3 TG) are never read, so their registers are free the moment the
+                    // last MFMA is issued -- and behind the wave-uniform beta branch that follows stage 1 here the compiler gave one
+                    // to an LDS read (a J value) four wait states behind that MFMA, whose later passes then overwrote the value in
+                    // the lane groups g >= 1 (seen on MI355X at p = 3: plane 0 of the second sub-tile wrong, from run to run in
+                    // different lane groups).  Plane 0 keeps them allocated until its stage 2 has read the last MFMA's real rows.
+                    if (x == 0) {
+#pragma unroll
+                        for (int s = 3 * G::TG; s < 4 * G::RT; ++s) asm volatile("" ::"v"(acc[s >> 2][s & 3]) : "memory");
+                    }
                 }
                 wave_lds_fence();
                 double* op = out_x[x] + (e0 + 16 * m) * NP;
@@ -424,7 +518,11 @@ __device__ __forceinline__ void grad3d_mfma_body(
                 for (int c = 0; c < G::SUB_INSTR; ++c) {
                     const int q = c * 64 + lane;
                     if ((c + 1) * 64 <= G::SUB_CHUNKS || q < G::SUB_CHUNKS) {
-                        const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * q);
+                        v2d val = *reinterpret_cast<const v2d*>(ob + 2 * q);
+                        if constexpr (kAcc) {
+                            if (acc_reads) val = axpby_combine(v2d{alpha, alpha}, val, v2d{beta, beta}, old.v[(3 * m + x) & 1][c]);
+                            else val = v2d{alpha, alpha} * val;
+                        }
                         if (x_no_stores) { if (val[0] == 1.2345e-300) op[2 * q] = val[1]; }   // keep the value live
                         else if (x_plain_stores) *reinterpret_cast<v2d*>(op + 2 * q) = val;
                         else __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * q));
@@ -584,12 +682,14 @@ __device__ __forceinline__ void grad3d_mfma_body(
             if (next_new_tile) {
                 if (!pre) grad_issue_j<NP, M, kPlain>(P, E, phys(nt), lane, lds_addr_uniform(L->j[jbuf ^ 1]));
                 if (x_no_stores || first) wait_vmcnt<G::LOADS>();
+                else if (kAcc && acc_reads) wait_vmcnt<G::LOADS + G::STORES + G::ACC_LOADS>();   // + the previous unit's old-value loads
                 else wait_vmcnt_planes<G::LOADS, G::PLANE_STORES>(nx);
             } else if (kDyn && extra) {
                 if (first) wait_vmcnt<G::U_INSTR + 1>();
                 else wait_vmcnt<G::U_INSTR + G::STORES + 1>();
             } else {
                 if (x_no_stores || first) wait_vmcnt<G::U_INSTR>();
+                else if (kAcc && acc_reads) wait_vmcnt<G::U_INSTR + G::STORES + G::ACC_LOADS>();
                 else wait_vmcnt_planes<G::U_INSTR, G::PLANE_STORES>(nx);
             }
         } else if (q_e0 >= 0) {   // (static walk, one field) the last full tile: behind its loads go the quarter tile's
@@ -599,6 +699,7 @@ __device__ __forceinline__ void grad3d_mfma_body(
         } else {
             if (kDyn && extra) wait_vmcnt<G::STORES + 1>();
             else if (first || x_no_stores) wait_vmcnt<0>();
+            else if (kAcc && acc_reads) wait_vmcnt<G::STORES + G::ACC_LOADS>();
             else wait_vmcnt_planes<0, G::PLANE_STORES>(nx);
         }
         first = false;
@@ -788,7 +889,7 @@ __device__ __forceinline__ void grad3d_mfma_body(
         static_top();
         static_bottom(std::false_type{});
     }
-    if constexpr (kPlain && !kPrep && M == 1) {
+    if constexpr (kPlain && !kPrep && M == 1 && !kAcc) {
         if (q_e0 >= 0) {
             wait_vmcnt<G::STORES>();                         // younger than the quarter tile's loads: the last full tile's stores
             const double* ut = L->u[ub];
@@ -853,6 +954,14 @@ __global__ __launch_bounds__(256, 2) void grad3d_mfma_kernel(
     GradFields P, const double* __restrict__ D, const void* __restrict__ prep, int nb, int nx, int64_t E,
     int64_t nTiles, int opT) {
     grad3d_mfma_body<NP, M, kDbg, kPlain, kPrep>(P, D, prep, nb, nx, E, nTiles, opT, blockIdx.x, gridDim.x);
+}
+
+// out <- alpha (the grad sum) + beta out: tetrahedra p = 1..4, one field, static walk (grad3d_mfma_body, kAcc)
+template <int NP, int M>
+__global__ __launch_bounds__(256, 2) void grad3d_mfma_acc_kernel(
+    GradFields P, const double* __restrict__ D, int64_t E, int64_t nTiles, int opT, double alpha, double beta) {
+    grad3d_mfma_body<NP, M, 0, true, false, false, true>(P, D, nullptr, 1, 3, E, nTiles, opT, blockIdx.x, gridDim.x, nullptr, 0,
+                                                         alpha, beta);
 }
 
 // the plain single-field launch with a dynamic tail (see fe_common.h)

@@ -950,6 +950,41 @@ int launch_fm_acc(const double* J, const double* R, const fe::FieldPtrs& P, int 
     return fail(FE_EINVAL, "accumulating face-mass: internal field grouping error (nb=%d)", nb);
 }
 
+// The accumulating grad and div launches (fe_grad3d_acc_f64, fe_div3d_acc_f64; fe_grad.h / fe_div.h, kAcc): one field, static
+// walk, the plain operator, full tiles, non-temporal stores -- op_flags carries the operator layout and the temporal-load bit
+// only (no write-through, quarter tiles, staggered start, split walk; the kernels compile those forms out anyway).
+template <int NP, int M>
+int launch_grad_acc(const fe::GradFields& P, const double* D, int64_t E, int opT, double alpha, double beta, hipStream_t s,
+                    bool* launched) {
+    using G = fe::GradGeom<NP, M>;
+    const int64_t nTiles = E / G::TEL;   // full wave tiles; the launch covers the elements behind the last one too
+    *launched = nTiles > 0;
+    if (nTiles == 0) return FE_OK;
+    // (with beta != 0 the launch reads its output too: it counts as an input for the cache rule)
+    const int64_t in_doubles = 9 + (int64_t)NP + (beta != 0.0 ? 3 * (int64_t)NP : 0);
+    const int f = (opT ? 1 : 0) | temporal_flag(in_doubles * E * 8);
+    char what[96];
+    snprintf(what, sizeof(what), "grad Np=%d M=%d, accumulating", NP, M);
+    return mfma_launch<fe::grad3d_mfma_acc_kernel<NP, M>>(s, walk_static(nTiles), {G::WAVES, 256, G::LDS_BYTES, 2, 8 / G::WAVES}, what,
+                                                          [&](const Launch&) { return call(f, 0, P, D, E, nTiles, f, alpha, beta); });
+}
+
+template <int NP, int M>
+int launch_div_acc(const double* J, const double* D, const fe::FieldPtrs& P, int64_t E, int opT, double alpha, double beta,
+                   hipStream_t s, bool* launched) {
+    using G = fe::DivGeom<NP, M>;
+    const int64_t nTiles = E / G::TEL;
+    *launched = nTiles > 0;
+    if (nTiles == 0) return FE_OK;
+    const int64_t in_doubles = 9 + 3 * (int64_t)NP + (beta != 0.0 ? (int64_t)NP : 0);
+    const int f = (opT ? 1 : 0) | temporal_flag(in_doubles * E * 8, kTemporalFloorDiv, kTemporalCapDivMib);
+    char what[96];
+    snprintf(what, sizeof(what), "div Np=%d M=%d, accumulating", NP, M);
+    return mfma_launch<fe::div3d_mfma_acc_kernel<NP, M>>(
+        s, walk_static(nTiles), {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, 8 / G::WAVES}, what,
+        [&](const Launch&) { return call(f, 0, J, D, P, E, nTiles, f, alpha, beta); });
+}
+
 // 'xre,rij,ej->xei' operands as grad-type planes: j[x] = J[x], out[k][x] = out_k[x]
 fe::GradFields grad_fields(const double* J, const double* const* u, double* const* out, int nb, int64_t E,
                            int Np) {
@@ -2188,6 +2223,80 @@ int fe_facemass_acc_f64(const double* J, const double* R, const double* const* v
 #undef FE_FM_ACC_CASE
         }
         k0 += nb;
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+// the argument checks the two accumulating DG entry points below share (`who`: "accumulating grad" / "accumulating div")
+static int check_acc(const char* who, const double* J, const double* D, const double* u, double* out, int64_t E, int32_t Np,
+                     int32_t op_flags, double alpha, double beta) {
+    if (E < 0) return fail(FE_EINVAL, "%s: E must be >= 0 (got %lld)", who, (long long)E);
+    if (Np <= 0) return fail(FE_EINVAL, "%s: Np must be positive (got %d)", who, Np);
+    if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, op_flags);
+    if (!std::isfinite(alpha) || !std::isfinite(beta))
+        return fail(FE_EINVAL, "%s: alpha and beta must be finite (got %g, %g)", who, alpha, beta);
+    if ((reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(u) |
+         reinterpret_cast<uintptr_t>(out)) & 7u)
+        return fail(FE_EINVAL, "%s: device pointers must be 8-byte aligned", who);
+    // the compiled scope: tetrahedra p = 1..4; the caller evaluates anything else into an array of its own and combines with fe_axpby
+    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
+        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no accumulating kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
+    if (E == 0) return FE_OK;
+    if (!J || !D || !u || !out) return fail(FE_EINVAL, "%s: null device pointer", who);
+    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    return FE_OK;
+}
+
+int fe_grad3d_acc_f64(const double* J, const double* D, const double* u, double* out, int64_t E, int32_t Np, int32_t op_flags,
+                      double alpha, double beta, void* stream) {
+    forget_last_launch();
+    if (int rc = check_acc("accumulating grad", J, D, u, out, E, Np, op_flags, alpha, beta)) return rc;
+    if (E == 0) return FE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
+    const double* ua[1] = {u};
+    double* oa[1] = {out};
+    const fe::GradFields P = grad_fields(J, ua, oa, 1, E, Np);
+    bool launched = false;
+    int rc = FE_OK;
+    switch (Np) {   // the (Np, M) geometries of fe_grad3d_f64
+        case 35: rc = launch_grad_acc<35, 1>(P, D, E, opT, alpha, beta, s, &launched); break;
+        case 20: rc = launch_grad_acc<20, 2>(P, D, E, opT, alpha, beta, s, &launched); break;
+        case 10: rc = launch_grad_acc<10, 3>(P, D, E, opT, alpha, beta, s, &launched); break;
+        default: rc = launch_grad_acc<4, 5>(P, D, E, opT, alpha, beta, s, &launched); break;
+    }
+    if (rc != FE_OK) return rc;
+    if (!launched) {   // fewer elements than a wave tile: one thread per entry
+        hipLaunchKernelGGL(fe::grad3d_generic_acc_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, u, out, E, Np,
+                           (int64_t)0, opT, alpha, beta);
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+int fe_div3d_acc_f64(const double* J, const double* D, const double* u, double* out, int64_t E, int32_t Np, int32_t op_flags,
+                     double alpha, double beta, void* stream) {
+    forget_last_launch();
+    if (int rc = check_acc("accumulating div", J, D, u, out, E, Np, op_flags, alpha, beta)) return rc;
+    if (E == 0) return FE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
+    fe::FieldPtrs P = {};
+    P.v[0] = u;
+    P.out[0] = out;
+    bool launched = false;
+    int rc = FE_OK;
+    switch (Np) {   // the (Np, M) geometries of fe_div3d_f64
+        case 35: rc = launch_div_acc<35, 1>(J, D, P, E, opT, alpha, beta, s, &launched); break;
+        case 20: rc = launch_div_acc<20, 1>(J, D, P, E, opT, alpha, beta, s, &launched); break;
+        case 10: rc = launch_div_acc<10, 3>(J, D, P, E, opT, alpha, beta, s, &launched); break;
+        default: rc = launch_div_acc<4, 5>(J, D, P, E, opT, alpha, beta, s, &launched); break;
+    }
+    if (rc != FE_OK) return rc;
+    if (!launched) {
+        hipLaunchKernelGGL(fe::div3d_generic_acc_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, u, out, E, Np,
+                           (int64_t)0, opT, alpha, beta);
     }
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;

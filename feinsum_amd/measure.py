@@ -35,8 +35,8 @@ Argument conventions kept from the reference:
                (``feinsum_amd.placement.zeros``; ``evaluate`` allocates the outputs it
                is not handed the same way), ``"separate"`` takes every array
                from torch; ``timeit_details(...).placement`` reports which was used;
-               ``"accumulate"`` (``"kernel"`` / ``"axpby"``): which way an accumulating ``evaluate(..., alpha=, beta=)``
-               adds onto its outputs, instead of what :func:`accumulate_route` picks.
+               ``"accumulate"`` (``"kernel"`` / ``"axpby"`` / ``"epilogue"``): which way an accumulating
+               ``evaluate(..., alpha=, beta=)`` adds onto its outputs, instead of what :func:`accumulate_route` picks.
 ``schedule``   followed by the ``"contraction"`` transform (default: the optimal one) and by the
                ``"reduction"`` transform where the einsum does not stream in one launch; the
                other kernels implement the optimal schedule and ignore it.
@@ -277,7 +277,9 @@ class _FamilyLaunch:
     def __init__(self, plan: KernelPlan, einsum: BatchedEinsum, arg_dict: Mapping[str, Any],
                  outs: Sequence[Any], variant: Any, scale: Optional[Tuple[float, float]] = None) -> None:
         self.plan, self.variant = plan, _hip.variant_code(variant)
-        self.scale = scale    # (alpha, beta) of an accumulating face-mass launch (fe_facemass_acc_f64), else None
+        # (alpha, beta) of a launch that accumulates inside its kernel -- face-mass (fe_facemass_acc_f64), grad and div of
+        # tetrahedra (fe_grad3d_acc_f64 / fe_div3d_acc_f64, one launch per field) -- else None
+        self.scale = scale
         role = plan.roles
         rows = einsum.args
         first = rows[0]
@@ -400,7 +402,12 @@ class _FamilyLaunch:
     def launch(self, stream_ptr: int) -> None:
         lib = _hip.load_library()
         for pack in self.groups:
-            if self.scale is not None:
+            if self.scale is not None and self.plan.family in (FAMILY_GRAD, FAMILY_DIV):
+                entry = lib.fe_grad3d_acc_f64 if self.plan.family == FAMILY_GRAD else lib.fe_div3d_acc_f64
+                for k in range(pack.b):     # one accumulating launch per field
+                    _hip.check(entry(pack.J, pack.D, pack.v[k], pack.outs[k], pack.E, pack.Np, pack.layout_flags,
+                                     self.scale[0], self.scale[1], stream_ptr))
+            elif self.scale is not None:
                 _hip.check(lib.fe_facemass_acc_f64(pack.J, pack.D, pack.v, pack.outs, pack.E, pack.Np, pack.nf, pack.Nfp,
                                                    pack.b, pack.layout_flags, self.scale[0], self.scale[1], stream_ptr))
             elif self.f32:
@@ -559,9 +566,11 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     return "generic"
 
 
-ACCUMULATE_ROUTES = ("kernel", "axpby")
+ACCUMULATE_ROUTES = ("kernel", "axpby", "epilogue")
 #: (Np, Nfp) of the tetrahedral orders p = 1..4: the shapes fe_facemass_acc_f64 is compiled for
 _ACC_FACEMASS_SHAPES = frozenset({(4, 3), (10, 6), (20, 10), (35, 15)})
+#: Np of the same orders: the shapes fe_grad3d_acc_f64 and fe_div3d_acc_f64 are compiled for
+_ACC_EPILOGUE_NP = frozenset(np_ for np_, _ in _ACC_FACEMASS_SHAPES)
 
 
 def _check_scale(alpha: Any, beta: Any) -> Tuple[float, float]:
@@ -597,6 +606,12 @@ def accumulate_route(einsum: BatchedEinsum, transform: Any = None) -> str:
     variant ``"auto"`` or ``"mfma"`` -- or ``"axpby"``: the einsum's ordinary launch into a temporary, then ``fe_axpby``.
     ``transform={"accumulate": "axpby"}`` forces the second; ``{"accumulate": "kernel"}`` insists on the first
     (``NotImplementedError`` where it does not exist).
+
+    A third route is opt-in and never chosen by default: ``{"accumulate": "epilogue"}`` returns ``"epilogue"`` -- the
+    accumulating grad / div kernels (``fe_grad3d_acc_f64`` / ``fe_div3d_acc_f64``, one launch per field), which read the old
+    output where they store the new one -- for float64 grad and div of tetrahedra p = 1..4, either operator layout, the
+    variant ``"auto"`` or ``"mfma"``; ``NotImplementedError`` for everything else (face-mass accumulates through
+    ``"kernel"``).
     """
     forced = transform.get("accumulate") if isinstance(transform, Mapping) else None
     if forced is not None and forced not in ACCUMULATE_ROUTES:
@@ -606,6 +621,15 @@ def accumulate_route(einsum: BatchedEinsum, transform: Any = None) -> str:
     fused = (plan is not None and plan.family == FAMILY_FACEMASS and not plan.params.get("f32")
              and plan.params.get("nf") == 4 and (plan.params.get("Np"), plan.params.get("Nfp")) in _ACC_FACEMASS_SHAPES
              and min(_family_group_sizes(plan, einsum)) >= 2)
+    if forced == "epilogue":
+        if (plan is not None and plan.family in (FAMILY_GRAD, FAMILY_DIV) and not plan.params.get("f32")
+                and plan.params.get("ndim", 3) == 3 and plan.params.get("Np") in _ACC_EPILOGUE_NP):
+            return "epilogue"
+        hint = ('; face-mass accumulates inside its kernel through {"accumulate": "kernel"}'
+                if plan is not None and plan.family == FAMILY_FACEMASS else "")
+        raise NotImplementedError(
+            f"einsum '{einsum.get_subscripts()}' x {einsum.b} has no accumulating epilogue under this transform (float64"
+            f" grad or div of tetrahedra p = 1..4, variant auto or mfma){hint}")
     if forced == "kernel" and not fused:
         raise NotImplementedError(
             f"einsum '{einsum.get_subscripts()}' x {einsum.b} has no accumulating kernel under this transform (float64"
@@ -688,15 +712,15 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
             bound = AdjointLaunch(match_operator_adjoint(einsum), einsum, arg_dict, outs, stream=q.stream)
     elif kind == "family":
         bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform),
-                              scale=(alpha, beta) if route == "kernel" else None)
-        if route != "kernel" and _prepared_from_transform(transform, prepare):
+                              scale=(alpha, beta) if route in ("kernel", "epilogue") else None)
+        if route not in ("kernel", "epilogue") and _prepared_from_transform(transform, prepare):
             with torch.cuda.device(q.torch_device), _on_stream_of(q):
                 bound.prepare_operators(q.stream_ptr)
     else:
         bound = _GenericLaunch(einsum, arg_dict, outs)
     if route == "axpby":
         bound, temps, outs = _AxpbyLaunch(bound, outs, final_outs, alpha, beta), outs, final_outs
-    #: None (the outputs are overwritten), or which way the launch adds onto them: "kernel" | "axpby" (accumulate_route)
+    #: None (the outputs are overwritten), or which way the launch adds onto them: "kernel" | "axpby" | "epilogue" (accumulate_route)
     bound.accumulate = route
     # byte ranges the launch reads and writes (operator.py checks them before reordering launches)
     bound.reads = tuple(_span(arg_dict[name]) for name in sorted(einsum.all_args)) + (tuple(_span(t) for t in outs) if beta != 0.0 else ())
@@ -757,7 +781,8 @@ def evaluate(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *,
     products are exact and the result is bitwise ``fl(alpha E_k + beta out_k)``.  It works under every transform, one of
     two ways (:func:`accumulate_route`; the bound launch says which in ``bound.accumulate``): the accumulating face-mass
     kernel, which reads the old output where it stores the new one, or the ordinary launch into a temporary (allocated at
-    bind time on the queue's stream) followed by ``fe_axpby`` on the same stream.  (1, 0), the default, is the code path
+    bind time on the queue's stream) followed by ``fe_axpby`` on the same stream.  ``transform={"accumulate": "epilogue"}``
+    opts grad and div of tetrahedra p = 1..4 into kernels that accumulate the same way as the face-mass one.  (1, 0), the default, is the code path
     without any of this.  DESIGN.md section 3m.
 
     Aliasing: an output handed in through *out_dict* may not share a byte with any input, nor with another output

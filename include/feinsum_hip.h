@@ -248,6 +248,20 @@ int fe_facemass_acc_f64(const double* J, const double* R,
                         const double* const* v, double* const* out,
                         int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
                         int32_t layout_flags, double alpha, double beta, void* stream);
+/* grad and div of tetrahedra that add onto what their output already holds, inside the matrix-core kernel:
+ *   grad: out[x,e,i] <- alpha * sum_{r,j} J[x,r,e] D[r,i,j] u[e,j]     + beta * out[x,e,i]
+ *   div:  out[e,i]   <- alpha * sum_{x,r,j} J[x,r,e] D[r,i,j] u[x,e,j] + beta * out[e,i]
+ * Arrays as fe_grad3d_f64_ex / fe_div3d_f64_ex (one field; op_flags: FE_OP_TRANSPOSED or 0; no variant: the matrix-core
+ * kernel, static walk); alpha, beta finite (FE_EINVAL).  The sum is bitwise what the plain entry point stores, the combine
+ * and the beta == 0 rule are those of fe_facemass_acc_f64, and so is the aliasing rule: every entry is read and written by
+ * the same thread, but out may not overlap an input.  Launches of fewer elements than one wave tile run a
+ * one-thread-per-entry kernel with the same combine.  Asynchronous on `stream`; E = 0 is a no-op.
+ * Compiled for p = 1..4 (Np = 4, 10, 20, 35); any other Np is FE_EUNSUPPORTED: evaluate into an array of your own and
+ * combine with fe_axpby. */
+int fe_grad3d_acc_f64(const double* J, const double* D, const double* u, double* out,
+                      int64_t E, int32_t Np, int32_t op_flags, double alpha, double beta, void* stream);
+int fe_div3d_acc_f64(const double* J, const double* D, const double* u, double* out,
+                     int64_t E, int32_t Np, int32_t op_flags, double alpha, double beta, void* stream);
 /* out[i] <- alpha * x[i] + beta * out[i], i < n, contiguous; dtype FE_DTYPE_F64 or FE_DTYPE_F32 (alpha and beta are
  * cast to it); pointers aligned to the element size, out and x not overlapping; the same combine and the same beta == 0
  * rule as above.  Asynchronous on `stream`. */
