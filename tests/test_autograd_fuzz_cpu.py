@@ -311,6 +311,143 @@ def Counter_of(cases):
     return A.coverage(cases)
 
 
+# --------------------------------------------------------------------------
+# operator gradients on the matrix cores (operator_gradients="kernel")
+# --------------------------------------------------------------------------
+
+def test_kernel_mode_routes_follow_match_operator_adjoint():
+    """Hand-checked routes, then every case of the list: a term takes "opgrad_d" / "opgrad_r" exactly where
+    ``match_operator_adjoint`` accepts it under "kernel", and today's route everywhere else (p = 5, the tiled-only orders,
+    float32, mixed, rows with different J)."""
+    from feinsum_amd.family import match_operator_adjoint
+
+    def routes(kind, Np, Nfp, b, dtype, **kw):
+        return A.predicted_launches(A.AGCase(D.DGCase(kind, Np, Nfp, b, "rij", dtype, 17, "ragged", 1), None, "auto",
+                                             operator_gradients="kernel", **kw))
+    assert routes("grad", 35, 15, 1, "float64") == {"geomadj": 1, "family": 1, "opgrad_d": 1}
+    assert routes("fm", 35, 15, 9, "float64") == {"facemass_v": 9, "facemass_j": 1, "opgrad_r": 1}
+    assert routes("bgrad", 20, 10, 9, "float64") == {"geomadj": 1, "family": 9, "opgrad_d": 1}
+    assert routes("grad", 56, 21, 1, "float64") == {"family": 1, "auto": 2}             # the fall-backs: today's routes
+    assert routes("grad", 35, 15, 1, "float32") == routes("grad", 35, 15, 1, "mixed") == {"family": 1, "auto": 2}
+    assert routes("fm", 7, 4, 2, "float64") == {"auto": 4}
+    assert routes("cross", 10, 6, 1, "float64") == {"geomadj": 3, "family": 4, "auto": 1}
+    assert routes("fm", 35, 15, 9, "float64", drop=(0, 3)) == {"facemass_v": 7, "facemass_j": 1, "opgrad_r": 1}
+    assert routes("fm", 35, 15, 3, "float64", frozen=("R",)) == {"facemass_v": 3, "facemass_j": 1}      # no opgrad launch
+    assert routes("grad", 35, 15, 1, "float64", frozen=("R",)) == {"geomadj": 1, "family": 1}
+    kernel = [c for c in _cases() if c.operator_gradients == "kernel"]
+    assert len(kernel) >= 60 and all(c.dg is not None for c in kernel)
+    n_op = 0
+    for c in kernel:
+        for wrt, route, sub, _ in A.plan_backward(c.expr(), c.drop, "kernel", c.frozen):
+            plan = match_operator_adjoint(sub)
+            assert (route in A.OPGRAD_ROUTES) == (plan is not None) and (plan is None or route == plan.kind)
+            assert plan is None or wrt in A.operator_names(c.expr())
+            assert route == A.route_of(sub, "kernel") and (plan is not None or route == A.route_of(sub))
+            n_op += plan is not None
+        assert not set(c.frozen) & {w for w, *_ in A.plan_backward(c.expr(), c.drop, "kernel", c.frozen)}
+        assert A.AGCase.from_repro(c.repro()) == c and '"operator_gradients":"kernel"' in c.repro()
+    assert n_op >= 30
+    # "auto" never predicts them, and a line written before the field existed replays as "auto"
+    assert all(r not in A.OPGRAD_ROUTES for c in _cases() if c.operator_gradients == "auto" for r in A.predicted_launches(c))
+    old = A.AGCase(D.DGCase("grad", 10, 6, 1, "rij", "float64", 17, "ragged", 3), None, "auto")
+    import json
+    line = json.dumps({k: v for k, v in json.loads(old.repro()).items() if k not in ("operator_gradients", "frozen")})
+    assert A.AGCase.from_repro(line) == old
+
+
+def test_kernel_mode_reaches_every_pass():
+    nf = Counter_of(A.nonfinite_cases(N_NONFINITE, SEED))
+    bounded = Counter_of(A.bounded_cases(N_BOUNDED, SEED))
+    large = [c for c in A.large_cases(SEED) if c.operator_gradients == "kernel"]
+    for cnt in (nf, bounded, Counter_of(large)):
+        assert cnt["route:opgrad_d"] >= 3 and cnt["route:opgrad_r"] >= 3
+    assert bounded["opgrad:b>8"] >= 2 and nf["opgrad:b>8"] >= 1
+    assert {(c.kind, c.dg.b) for c in large} >= {("grad", 1), ("div", 1), ("fm", 9)} and all(c.E == A.MULTI_TRIP_E for c in large)
+    from feinsum_amd import _hip
+    assert A.MULTI_TRIP_E > 64 * 1023 and _hip.opgrad_plan(A.MULTI_TRIP_E, 48)[0] == 1024      # past the slice cap
+    # no other large case was added
+    assert len(A.large_cases(SEED)) == 10 + len(large) and len(large) == 6
+
+
+def test_bound_of_a_kernel_term_is_the_one_derived_from_the_plan():
+    from feinsum_amd import _hip
+
+    case = A.AGCase(D.DGCase("grad", 35, 15, 1, "rij", "float64", 1003, "ragged", 9), None, "auto", operator_gradients="kernel")
+    n, u, rounded = A.bound_of(case.expr(), (), "R", 1003, "kernel")
+    assert (n, u, rounded) == (2 + 3 * 1003 + 6 + -(-_hip.opgrad_plan(1003, 3 * 35 * 35)[0] // 64), R.U64, False)
+    assert A.bound_of(case.expr(), (), "R", 1003)[0] < n                    # (today's route: a shorter chain)
+    assert A.bound_of(case.expr(), (), "J", 1003, "kernel") == A.bound_of(case.expr(), (), "J", 1003)
+    fm = A.AGCase(D.DGCase("fm", 35, 15, 9, "rij", "float64", 129, "ragged", 9), None, "auto", operator_gradients="kernel")
+    n, _, _ = A.bound_of(fm.expr(), (), "R", 129, "kernel")
+    assert n == 2 + 129 + 6 + 1 + 8                                         # nine rows summed in the kernel: eight additions
+
+
+def test_checker_rejects_a_slice_of_an_operator_gradient_summed_twice():
+    """dR of face-mass x 9 at E = 133 (three slices of 64 elements): the elements of one slice added once more -- a
+    second launch that adds to its slice twice, or a combine that reads a slice twice."""
+    case = A.AGCase(D.DGCase("fm", 10, 6, 9, "rij", "float64", 133, "ragged", 11), None, "auto", operator_gradients="kernel")
+    arrays, mants, scales = A.host_data(case)
+    expr = case.expr()
+    ref = A.grad_reference(expr, (), mants, scales, "R", case.E)
+    assert A.predicted_launches(case)["opgrad_r"] == 1
+    sl = {k: (np.take(m, range(64, 128), axis=m.shape.index(case.E)) if case.E in m.shape else m) for k, m in mants.items()}
+    assert sum(v.shape != mants[k].shape for k, v in sl.items()) == 1 + 9 + 9          # J, the fields, the output gradients
+    twice = ref + A.grad_reference(expr, (), sl, scales, "R", 64)
+    assert R.differing_entries(ref.copy(), ref) == 0 and R.differing_entries(twice, ref) > 0
+    # one field's rows of the second launch (fields 8..) summed twice, and left out
+    assert R.differing_entries(A.grad_reference(expr, (), mants, scales, "R", case.E, extra=(0, 8)), ref) > 0
+    assert R.differing_entries(A.grad_reference(expr, (), mants, scales, "R", case.E, skip=(0, 8)), ref) > 0
+    st = A.Stats("planted")
+    st.fail = lambda line: setattr(st, "failures", st.failures + 1)
+    assert not A._compare(st, "planted", case, {}, {"R": twice}, {}, {"R": ref}) and st.failures == 1
+    assert A._compare(st, "planted", case, {}, {"R": ref.copy()}, {}, {"R": ref}) and st.failures == 1
+    # a frozen operator: a gradient that shows up anyway is a failure
+    frozen = A.with_kernel(case, frozen=("R",))
+    assert not A._compare(st, "planted", frozen, {}, {"R": ref}, {}, {"R": None}) and st.failures == 2
+
+
+def test_direct_operator_gradient_runs_and_references():
+    from feinsum_amd.family import FACEMASS_ADJ_SHAPES, GEOMADJ_NP
+
+    og = A.opgrad_runs(SEED)
+    assert {(Np, lay, ol) for Np, _, _, lay, ol, _, _, _ in og} == {(Np, lay, ol) for Np in GEOMADJ_NP for lay in A.GEOM_LAYOUTS
+                                                                    for ol in A.OPGRAD_OUT_LAYOUTS}
+    assert {E for *_, E, _ in og} == set(A.OPGRAD_E) == set(A.KERNEL_E) | {65, 66}
+    assert {X for _, X, *_ in og} == {R_ for _, _, R_, *_ in og} == {1, 2, 3} and {nk for *_, nk, _, _ in og} == {1, 2}
+    assert all((lay == "xre" or X == 1) and (lay != "e" or R_ == 1) for _, X, R_, lay, *_ in og)
+    fm = A.facemass_opgrad_runs(SEED)
+    assert {(s, lay[2]) for s, lay, *_ in fm} == {(s, fl) for s in FACEMASS_ADJ_SHAPES for _, _, fl in A.FM_LAYOUT_FLAGS}
+    assert len({fl for _, _, fl in A.FM_LAYOUT_FLAGS}) == 8
+    assert {(lay[2], b) for s, lay, b, *_ in fm} >= {(fl, b) for _, _, fl in A.FM_LAYOUT_FLAGS for b in (1, 2, 4, 9)}
+    assert {E for *_, E, _ in fm} == set(A.OPGRAD_E)
+    pog, pfm = A.placement_opgrad_runs(SEED)
+    assert set(pog) <= set(og) and set(pfm) <= set(fm)
+    assert {(lay, ol) for _, _, _, lay, ol, *_ in pog} == {(lay, ol) for lay in A.GEOM_LAYOUTS for ol in A.OPGRAD_OUT_LAYOUTS}
+    assert {lay[2] for _, lay, *_ in pfm} == set(range(8)) and {b for _, _, b, *_ in pfm} == {1, 2, 4, 9}
+    assert {E for *_, E, _ in pog} | {E for *_, E, _ in pfm} <= set(A.OPGRAD_E)
+    # the references against the einsum definitions of tests/test_gpu_opgrad.py (small integers)
+    rng = np.random.default_rng(3)
+    X, R_, E, Np = 2, 3, 5, 4
+    J, a, b = rng.integers(-3, 4, size=(X, R_, E)), rng.integers(-3, 4, size=(2, E, Np)), rng.integers(-3, 4, size=(2, X, E, Np))
+    want = sum(np.einsum("xre,eq,xep->rpq", J, a[k], b[k]) for k in range(2))
+    assert np.array_equal(A.opgrad_reference(J, list(a), list(b), "xre", "rpq"), want)
+    assert np.array_equal(A.opgrad_reference(J, list(a), list(b), "xre", "rqp"), want.transpose(0, 2, 1))
+    one = np.einsum("xre,eq,xep->rpq", J[:1], a[0], b[0][:1])
+    assert np.array_equal(A.opgrad_reference(np.ascontiguousarray(J[0].T), [a[0]], [b[0][:1]], "er", "rpq"), one)
+    assert np.array_equal(A.opgrad_reference(J[0], [a[0]], [b[0][:1]], "re", "rpq"), one)
+    assert np.array_equal(A.opgrad_reference(J[0, 0], [a[0]], [b[0][:1]], "e", "rpq"), one[:1])
+    nf, Nfp = 4, 3
+    Jf, g, v = rng.integers(-3, 4, size=(nf, E)), rng.integers(-3, 4, size=(2, E, Np)), rng.integers(-3, 4, size=(2, nf, E, Nfp))
+    dR = np.einsum("kei,fe,kfej->fij", g, Jf, v)
+    assert np.array_equal(A.facemass_opgrad_reference(Jf, list(g), list(v), "fe", "jfi"), dR.transpose(2, 0, 1))
+    assert A.facemass_opgrad_reference(Jf, list(g), list(v), "fe", "jfi").shape == A._r_shape("jfi", nf, Np, Nfp)
+    assert np.array_equal(A.facemass_opgrad_reference(Jf.T, list(g), list(v), "ef", "ifj"), dR.transpose(1, 0, 2))
+    # the workspace is an output of exactly the planned bytes
+    from feinsum_amd import _hip
+    outs, nbytes = A._with_workspace({"out": (3, 4, 4)}, 1003, 48)
+    assert nbytes == _hip.opgrad_plan(1003, 48)[1] > 0 and outs["ws"] == (nbytes // 8,) and list(outs) == ["out", "ws"]
+
+
 def test_plant_sites_reach_tile_ends_and_every_role():
     import random
 

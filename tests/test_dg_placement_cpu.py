@@ -352,3 +352,41 @@ def test_kernel_placement_runs_cover_every_layout():
         assert {b for sh, _, b, *_ in fm if sh == s} >= {1, 2, 4}
     assert {w for _, _, _, w, _, _ in fm} == {"dv", "dJ", "both"}
     assert {E for *_, E, _ in geom} | {E for *_, E, _ in fm} <= set(A.KERNEL_E)
+
+
+def test_operator_gradient_placement_runs_cover_every_layout():
+    """The counts tests/test_gpu_dg_placement.py asks of the operator-gradient kernels, from the run lists alone:
+    "aligned" and "all" run every run, each of the six "only:" placements every third one."""
+    from collections import Counter
+
+    og, fm = A.placement_opgrad_runs(SEED)
+    assert len(og) == 32 and len(fm) == 16
+    cnt = Counter()
+    for k, placement in enumerate(A.KERNEL_PLACEMENTS):
+        every = placement in ("aligned", "all")
+        for Np, X, R, lay, ol, nk, E, s in (og if every else og[k % 3::3]):
+            cnt.update([f"opgrad:{lay},{ol}", f"opgrad:E{E}", "place:" + placement, "opgrad:workspace"])
+        for shape, (jl, rl, flags), b, E, s in (fm if every else fm[k % 3::3]):
+            cnt.update([f"opgrad_fm:{jl},{rl}", f"opgrad_fm:b{b}", f"opgrad:E{E}", "place:" + placement, "opgrad:workspace"])
+    assert all(cnt[f"opgrad:{lay},{ol}"] >= 8 for lay in A.GEOM_LAYOUTS for ol in A.OPGRAD_OUT_LAYOUTS)
+    assert all(cnt[f"opgrad_fm:{jl},{rl}"] >= 4 for jl, rl, _ in A.FM_LAYOUT_FLAGS)
+    assert all(cnt[f"opgrad_fm:b{b}"] >= 16 for b in (1, 2, 4, 9)) and all(cnt[f"opgrad:E{E}"] >= 8 for E in A.OPGRAD_E)
+    assert all(cnt["place:" + p] >= 15 for p in A.KERNEL_PLACEMENTS) and cnt["place:aligned"] == cnt["place:all"] == 48
+    assert cnt["opgrad:workspace"] >= 192
+    # the workspace (256-byte aligned by contract) is never shifted: every placement leaves it on its boundary
+    outs, _ = A._with_workspace({"out": (3, 4, 4)}, 65, 48)
+    x = {"J": np.zeros((3, 3, 65)), "a0": np.zeros((65, 4)), "b0": np.zeros((3, 65, 4))}
+    ins = [("J", "geometry"), ("a0", "field"), ("b0", "field")]
+    saved, A.DEVICE = A.DEVICE, "cpu"
+    try:
+        for placement in A.KERNEL_PLACEMENTS:
+            arrays = A._KernelArrays(torch, placement, x, ins, outs)
+            assert arrays.out["ws"].data_ptr() % 256 == 0 and arrays.out["ws"].numel() * 8 == A._with_workspace({}, 65, 48)[1]
+            assert arrays.out["out"].data_ptr() % 256 == (8 if placement in ("all", "only:output", "only:last-output") else 0)
+            assert arrays.d["b0"].data_ptr() % 256 == (8 if placement in ("all", "only:last-field") else 0)
+            arrays.out["ws"].fill_(1.0)
+            assert arrays.guards_intact()
+            arrays._outs["ws"].buf[arrays._outs["ws"].lead + arrays._outs["ws"].n] = 0.0      # one element behind the planned bytes
+            assert not arrays.guards_intact()
+    finally:
+        A.DEVICE = saved

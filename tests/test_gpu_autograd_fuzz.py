@@ -50,7 +50,9 @@ def _check(st, minimums=None):
         assert not A.missing_buckets(st.cov, minimums), A.missing_buckets(st.cov, minimums)
 
 
-ROUTE_MINIMUMS = {f"route:{r}": 3 for r in A.ROUTES}
+ROUTE_MINIMUMS = {f"route:{r}": 3 for r in A.ROUTES if r not in A.OPGRAD_ROUTES}
+# under operator_gradients="kernel" (DESIGN.md section 3l): the operator-gradient kernels, per pass
+OPGRAD_MINIMUMS = {"route:opgrad_d": 3, "route:opgrad_r": 3}
 
 
 @pytest.mark.timeout(900)
@@ -65,7 +67,8 @@ def test_exact_gradients_every_kind_route_and_transform(torch_cuda):
 def test_gradients_within_the_error_bound(torch_cuda):
     st = A.run_bounded(N_BOUNDED, SEED)
     _check(st, {"dtype:float64": 10, "dtype:float32": 5, "dtype:mixed": 5, "b:>8": 2, "kind:einsum": 3,
-                **ROUTE_MINIMUMS})
+                **ROUTE_MINIMUMS, **OPGRAD_MINIMUMS, "opgrad:mode": 12, "opgrad:b>8": 2,
+                **{f"opgrad:kind:{k}": 1 for k in ("grad", "div", "fm", "bgrad", "mass", "lift2")}})
 
 
 @pytest.mark.timeout(300)
@@ -73,18 +76,26 @@ def test_nonfinite_values_stay_in_their_gradient_dependency_sets(torch_cuda):
     st = A.run_nonfinite(N_NONFINITE, SEED)
     assert st.exact_runs > 0 and st.exact_equal == st.exact_runs
     _check(st, {"planted:field": 10, "planted:geometry": 10, "planted:operator": 10, "planted:output-grad": 10,
-                "value:nan": 8, "value:inf": 8, "value:-inf": 8, **ROUTE_MINIMUMS})
+                "value:nan": 8, "value:inf": 8, "value:-inf": 8, **ROUTE_MINIMUMS, **OPGRAD_MINIMUMS,
+                "opgrad:planted:output-grad": 5, "opgrad:planted:geometry": 5, "opgrad:planted:field": 5,
+                "opgrad:planted:operator": 5})
 
 
 @pytest.mark.timeout(600)
 def test_large_gradients_whole_array(torch_cuda):
     st = A.run_large(SEED)
     assert st.exact_runs > 0 and st.exact_equal == st.exact_runs
-    _check(st, {**ROUTE_MINIMUMS, "route:facemass_j:b>8": 3, "E:1000003": 3, "dtype:float32": 1})
+    _check(st, {**ROUTE_MINIMUMS, "route:facemass_j:b>8": 3, "E:1000003": 3, "dtype:float32": 1,
+                **OPGRAD_MINIMUMS,
+                **{f"opgrad:large:{k}:E{A.MULTI_TRIP_E}": 1 for k in ("grad", "div", "fm", "fm_jfi", "fm_fji")},
+                f"opgrad:large:grad:E{A.MULTI_TRIP_E}": 2})
 
 
 @pytest.mark.timeout(600)
 def test_adjoint_kernels_every_shape_and_layout(torch_cuda):
     st = A.run_kernels(SEED)
     assert st.exact_runs > 0 and st.exact_equal == st.exact_runs
-    _check(st, {"E:multi-trip": 17, "facemass_adj:b17": 200, "facemass_adj:dJ": 200, "geomadj:er": 40})
+    _check(st, {"E:multi-trip": 17, "facemass_adj:b17": 200, "facemass_adj:dJ": 200, "geomadj:er": 40,
+                **{f"opgrad:{lay},{ol}": 8 for lay in A.GEOM_LAYOUTS for ol in A.OPGRAD_OUT_LAYOUTS},
+                **{f"opgrad_fm:{jl},{rl}": 9 for jl, rl, _ in A.FM_LAYOUT_FLAGS}, **{f"opgrad_fm:b{b}": 18 for b in (1, 2, 4, 9)},
+                **{f"opgrad:E{E}": 15 for E in A.OPGRAD_E}, "opgrad:workspace": 136})

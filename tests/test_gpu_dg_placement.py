@@ -1,4 +1,4 @@
-"""The DG family kernels and the two adjoint kernels with their operands at every accepted address offset
+"""The DG family kernels, the two adjoint kernels and the two operator-gradient kernels with their operands at every accepted address offset
 (tools/fuzz_dg.py ``run_placement``, tools/fuzz_autograd.py ``run_kernels(placement=...)``): each array sits 0 or 8
 bytes (float64), 0, 4, 8 or 12 bytes (float32) past a 256-byte boundary, inputs between NaN bands, outputs between
 sentinel bands; one array shifted at a time, all of them, and a random mix, against the aligned launch.
@@ -72,10 +72,12 @@ def test_adjoint_kernels_at_every_placement(torch_cuda):
     """"aligned" and "all" on every run of the subset, each "only:" placement on every third run (in turn, so that the
     six of them together reach every run twice)."""
     geom, fm = A.placement_kernel_runs(SEED)
+    og, ogfm = A.placement_opgrad_runs(SEED)      # the operator-gradient kernels, their workspace embedded like an output
     total = A.Stats("adjoint kernels, placements")
     for k, placement in enumerate(A.KERNEL_PLACEMENTS):
         every = placement in ("aligned", "all")
-        st = A.run_kernels(SEED, geom if every else geom[k % 3::3], fm if every else fm[k % 3::3], placement=placement)
+        st = A.run_kernels(SEED, geom if every else geom[k % 3::3], fm if every else fm[k % 3::3], placement=placement,
+                           og_runs=og if every else og[k % 3::3], ogfm_runs=ogfm if every else ogfm[k % 3::3])
         total.failures += st.failures
         total.exact_runs += st.exact_runs
         total.exact_equal += st.exact_equal
@@ -83,5 +85,9 @@ def test_adjoint_kernels_at_every_placement(torch_cuda):
     total.cov["leak:nan-entries"] += 0
     layouts = {f"geomadj:{lay}": 8 for lay in A.GEOM_LAYOUTS}
     layouts.update({f"facemass_adj:{jl},{rl}": 8 for jl, rl, _ in A.FM_LAYOUT_FLAGS})
-    _check(total, {**{f"place:{p}": 40 for p in A.KERNEL_PLACEMENTS}, **layouts, "place:aligned": 120, "place:all": 120,
-                   "facemass_adj:b1": 20, "facemass_adj:b2": 20, "facemass_adj:b4": 20, "facemass_adj:b9": 9})
+    layouts.update({f"opgrad:{lay},{ol}": 8 for lay in A.GEOM_LAYOUTS for ol in A.OPGRAD_OUT_LAYOUTS})
+    layouts.update({f"opgrad_fm:{jl},{rl}": 4 for jl, rl, _ in A.FM_LAYOUT_FLAGS})
+    _check(total, {**{f"place:{p}": 40 + 15 for p in A.KERNEL_PLACEMENTS}, **layouts, "place:aligned": 120 + 48, "place:all": 120 + 48,
+                   "facemass_adj:b1": 20, "facemass_adj:b2": 20, "facemass_adj:b4": 20, "facemass_adj:b9": 9,
+                   "opgrad_fm:b1": 16, "opgrad_fm:b2": 16, "opgrad_fm:b4": 16, "opgrad_fm:b9": 16, "opgrad:workspace": 192,
+                   **{f"opgrad:E{E}": 8 for E in A.OPGRAD_E}})

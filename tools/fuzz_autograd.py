@@ -21,8 +21,13 @@ Passes:
                    every other entry bitwise exact.
 ``run_large``      grad, div and face-mass x 9 at E = 98 304 ... 1 000 003 (and float32 grad at about 10^5): every
                    gradient checked over the whole array.
-``run_kernels``    the two adjoint kernels called directly, every compiled shape and layout, outputs in NaN-filled
-                   buffers between sentinel guard bands.
+``run_kernels``    the two adjoint kernels and the two operator-gradient kernels called directly, every compiled shape and
+                   layout, outputs (and the operator-gradient workspace, exactly its planned bytes) in NaN-filled buffers
+                   between sentinel guard bands.
+
+A fixed share of the exact, bounded, non-finite and large passes runs with ``operator_gradients="kernel"`` (the
+operator gradients dD, dR on the matrix cores: routes "opgrad_d" / "opgrad_r", predicted from ``match_operator_adjoint``
+with their fall-backs to the other routes), some of it with the operator ``frozen`` (no gradient asked: no such launch).
 """
 
 from __future__ import annotations
@@ -48,7 +53,7 @@ import fuzz_dg as D  # noqa: E402
 import fuzz_einsum as FE  # noqa: E402
 from feinsum_amd import autograd as AG  # noqa: E402
 from feinsum_amd.family import (FACEMASS_ADJ_SHAPES, FM_J_FE, FM_R_IFJ, FM_R_T, GEOMADJ_NP,  # noqa: E402
-                                OP_TRANSPOSED, match_adjoint_family, match_family)
+                                OP_TRANSPOSED, match_adjoint_family, match_family, match_operator_adjoint)
 from feinsum_amd.measure import launch_kind  # noqa: E402
 from fuzz_einsum import Stats, _guarded, _guards_intact, missing_buckets  # noqa: E402,F401
 from oracle import einsum_ref as ref_  # noqa: E402
@@ -56,7 +61,8 @@ from oracle import einsum_ref as ref_  # noqa: E402
 #: the single-stage DG kinds (the fused pipeline is not differentiable)
 KINDS = tuple(k for k in D.KINDS if k != "pipeline")
 FWD_TRANSFORMS = ("auto", "mfma", "tiled", "generic", "prepared")
-ROUTES = ("geomadj", "facemass_v", "facemass_j", "family", "auto")
+ROUTES = ("geomadj", "facemass_v", "facemass_j", "family", "auto", "opgrad_d", "opgrad_r")
+OPGRAD_ROUTES = ("opgrad_d", "opgrad_r")
 #: E at most this: the int64 reference of the whole array on the host, else torch's float64 einsum on the device
 HOST_REF_MAX_E = D.HOST_REF_MAX_E
 #: the element of a one-trip-past persistent grid of the adjoint kernels (two blocks of four waves per CU, 16 elements
@@ -69,6 +75,11 @@ MINIMUMS = {**{f"kind:{k}": 3 for k in KINDS}, "kind:einsum": 12,
             "dtype:float64": 40, "dtype:float32": 20, "dtype:mixed": 15,
             **{f"transform:{t}": 8 for t in FWD_TRANSFORMS},
             **{f"route:{r}": 10 for r in ROUTES}, "route:facemass_j:b>8": 3, "route:auto:Np56": 3,
+            **{f"opgrad:kind:{k}": 1 for k in KINDS if k not in ("cross", "divcomp", "apply")}, "opgrad:mode": 40,
+            # rows with different J (one kept row of a partial gradient does run on the kernel); no J at all
+            "opgrad:fallback:kind:cross": 1, "opgrad:fallback:kind:divcomp": 1, "opgrad:fallback:kind:apply": 1, "opgrad:b>8": 4, "opgrad:frozen-operator": 4,
+            "opgrad:partial": 4, "opgrad:fallback:Np56": 2, "opgrad:fallback:float32": 2, "opgrad:fallback:mixed": 2,
+            "opgrad:fallback:tiled-order": 2, "opgrad:transform:tiled": 1, "opgrad:transform:prepared": 1,
             "b:>8": 8, "grads:partial": 6, "range:overflow": 3, "range:subnormal": 3,
             "E:one": 3, "E:sub-tile": 3, "E:tiles": 6, "E:ragged": 6, "E:static-rounds": 2,
             "einsum:broadcast": 3, "einsum:twice": 3, "einsum:0d": 3, "einsum:ops3+": 4}
@@ -96,13 +107,17 @@ class EinCase:
 @dataclass(frozen=True)
 class AGCase:
     """One differentiated evaluation: a DG case (``dg``) or a random einsum (``ein``), the forward transform, the rows
-    whose outputs get no gradient (``drop``: ``None`` is passed for them) and the exact-data range."""
+    whose outputs get no gradient (``drop``: ``None`` is passed for them), the exact-data range, how the operator
+    gradients run (``operator_gradients``: "auto" or "kernel", the matrix-core kernels of DESIGN.md section 3l) and the
+    inputs that do not require a gradient (``frozen``)."""
 
     dg: Optional[D.DGCase]
     ein: Optional[EinCase]
     transform: str
     drop: Tuple[int, ...] = ()
     scale: str = "normal"
+    operator_gradients: str = "auto"
+    frozen: Tuple[str, ...] = ()
 
     def expr(self):
         return self.dg.stages()[0][0] if self.dg is not None else self.ein.expr()
@@ -143,7 +158,8 @@ class AGCase:
             e = d["ein"]
             ein = EinCase(e["subs"], tuple(tuple(s) for s in e["shapes"]), tuple(e["dtypes"]), tuple(e["names"]),
                           e["E"], e["seed"])
-        return AGCase(dg, ein, d["transform"], tuple(d["drop"]), d["scale"])
+        return AGCase(dg, ein, d["transform"], tuple(d["drop"]), d["scale"], d.get("operator_gradients", "auto"),
+                      tuple(d.get("frozen", ())))
 
 
 def accepted(case: AGCase) -> bool:
@@ -264,36 +280,89 @@ def gen_cases(n: int, seed: int, n_einsum: Optional[int] = None) -> List[AGCase]
             c = _dg(rng, rng.choice(KINDS), rng.choice(["tiles", "ragged", "sub-tile"]), dt)
             cases.append(_dg_case(rng, c, scale=scale))
     cases += einsum_cases(n // 4 if n_einsum is None else n_einsum, seed)
-    return cases
+    return cases + kernel_cases(cases, seed)
+
+
+def kernel_cases(cases: Sequence[AGCase], seed: int) -> List[AGCase]:
+    """The share of a case list that runs again with ``operator_gradients="kernel"``: every fifth DG case (partial
+    gradients, forward transforms, float32 / mixed and p = 5 fall-backs and the range cases come with them), then fixed
+    ones -- every kind, batched kinds with b = 9 (two launches adding to their own slice), partial gradients, the
+    operator frozen (no opgrad launch), and the fall-backs by name."""
+    rng = random.Random(seed + 59)
+    dg = [c for c in cases if c.dg is not None]
+    out = [with_kernel(c) for c in dg[::5]]
+    small = ["sub-tile", "tiles", "ragged", "ragged"]
+    for kind in KINDS:
+        tri = kind.endswith("2")
+        Np, Nfp = rng.choice(D.ORDERS2) if tri else rng.choice(D.ORDERS3[:4])
+        out.append(with_kernel(_dg_case(rng, _dg(rng, kind, rng.choice(small), "float64", Np=Np, Nfp=Nfp), partial_share=0.0)))
+    for kind in ("fm", "fm_jfi", "bgrad", "bdiv", "mass"):
+        c = _dg(rng, kind, rng.choice(["tiles", "ragged"]), "float64", b=9, Np=20, Nfp=10)
+        out.append(with_kernel(_dg_case(rng, c, partial_share=0.0)))
+    for kind in ("fm", "fm_ifj", "bgrad", "divcomp", "cross", "lift2"):
+        order = dict(Np=10, Nfp=4) if kind == "lift2" else dict(Np=10, Nfp=6)
+        c = _dg(rng, kind, rng.choice(small), "float64", b=4, **order)
+        out.append(with_kernel(_dg_case(rng, c, partial_share=1.0)))
+    for kind in ("grad", "div", "fm", "mass"):
+        c = _dg_case(rng, _dg(rng, kind, rng.choice(small), "float64", b=3, Np=20, Nfp=10), partial_share=0.5)
+        out.append(with_kernel(c, frozen=tuple(operator_names(c.expr()))))
+    for over in (dict(dtype="float64", Np=56, Nfp=21), dict(dtype="float32", Np=20, Nfp=10), dict(dtype="mixed", Np=10, Nfp=6),
+                 dict(dtype="float64", Np=7, Nfp=4)):
+        for kind in ("grad", "fm"):
+            dt = over["dtype"]
+            c = _dg(rng, kind, rng.choice(["tiles", "ragged"]), dt, **{k: v for k, v in over.items() if k != "dtype"})
+            out.append(with_kernel(_dg_case(rng, c, partial_share=0.0)))
+    for t in ("tiled", "prepared"):
+        out.append(with_kernel(_dg_case(rng, _dg(rng, "grad", "ragged", "float64", Np=35, Nfp=15), partial_share=0.0, transform=t)))
+    return out
 
 
 # --------------------------------------------------------------------------
 # routes (host only)
 # --------------------------------------------------------------------------
 
-def route_of(sub) -> str:
-    """The route ``autograd._run_term`` takes for an adjoint einsum (one count in ``launch_counts``)."""
+def route_of(sub, operator_gradients: str = "auto") -> str:
+    """The route ``autograd._run_term`` takes for an adjoint einsum (one count in ``launch_counts``): under
+    ``operator_gradients="kernel"`` the operator-gradient kernels where ``match_operator_adjoint`` accepts the term
+    (float64, a compiled size), else today's routes."""
+    if operator_gradients == "kernel":
+        op_plan = match_operator_adjoint(sub)
+        if op_plan is not None:
+            return op_plan.kind
     plan = match_adjoint_family(sub)
     if plan is not None:
         return plan.kind
     return "family" if match_family(sub) is not None else "auto"
 
 
-def plan_backward(expr, drop: Sequence[int] = ()) -> List[Tuple[str, str, Any, Any]]:
+def plan_backward(expr, drop: Sequence[int] = (), operator_gradients: str = "auto",
+                  frozen: Sequence[str] = ()) -> List[Tuple[str, str, Any, Any]]:
     """``(wrt, route, adjoint einsum of the rows with a gradient, AdjointTerm)`` of every ``_run_term`` call the backward
-    pass makes when every input requires grad and the rows in *drop* get no output gradient."""
+    pass makes when every input outside *frozen* requires grad and the rows in *drop* get no output gradient."""
     out = []
     for wrt in sorted(expr.all_args):
+        if wrt in frozen:
+            continue
         for term in AG.adjoint_terms(expr, wrt):
             rows = tuple(row for row, k in zip(term.einsum.args, term.forward_rows) if k not in drop)
             if rows:
                 sub = term.einsum.copy(args=rows)
-                out.append((wrt, route_of(sub), sub, term))
+                out.append((wrt, route_of(sub, operator_gradients), sub, term))
     return out
 
 
 def predicted_launches(case: AGCase) -> Counter:
-    return Counter(r for _, r, _, _ in plan_backward(case.expr(), case.drop))
+    return Counter(r for _, r, _, _ in plan_backward(case.expr(), case.drop, case.operator_gradients, case.frozen))
+
+
+def operator_names(expr) -> List[str]:
+    """The inputs without an element axis (D, R)."""
+    return [n for n in sorted(expr.all_args) if not any(isinstance(d, f.SizeParam) for d in expr.arg_to_shape[n])]
+
+
+def with_kernel(case: AGCase, **over) -> AGCase:
+    """The case with its operator gradients on the matrix cores."""
+    return replace(case, operator_gradients="kernel", **over)
 
 
 def _eclass(case: AGCase) -> str:
@@ -317,6 +386,19 @@ def buckets_of(case: AGCase, routes: Sequence[str]) -> List[str]:
         b.append("route:facemass_j:b>8")
     if "auto" in routes and case.dg is not None and case.dg.Np == 56:
         b.append("route:auto:Np56")
+    if case.operator_gradients == "kernel":
+        b.append("opgrad:mode")
+        hit = any(r in OPGRAD_ROUTES for r in routes)
+        if set(operator_names(expr)) <= set(case.frozen):
+            b.append("opgrad:frozen-operator")      # (no opgrad launch: _check_routes holds the run to the prediction)
+        elif hit:
+            b += [f"opgrad:kind:{case.kind}", f"opgrad:transform:{case.transform}"]
+            b += ["opgrad:b>8"] if big else []
+            b += ["opgrad:partial"] if case.drop else []
+        elif case.dg is not None:
+            why = case.dtype if case.dtype != "float64" else "Np56" if case.dg.Np == 56 else \
+                "tiled-order" if case.dg.Np in (7, 13) else f"kind:{case.kind}"
+            b.append(f"opgrad:fallback:{why}")
     if case.ein is not None:
         ins = case.ein.subs.split("->")[0].split(",")
         if len(set(case.ein.names)) < len(case.ein.names):
@@ -580,10 +662,11 @@ def forward_backward(torch, case: AGCase, dev: Dict[str, Any]):
     """``(forward outputs, {input: gradient or None}, launch counts of the backward pass)``: every input requires grad,
     every output with a gradient in *dev* passes it to ``torch.autograd.backward``, the others pass ``None``."""
     expr = case.expr()
-    leaves = {n: dev[n].detach().requires_grad_(True) for n in sorted(expr.all_args)}
+    leaves = {n: dev[n].detach().requires_grad_(n not in case.frozen) for n in sorted(expr.all_args)}
     before = Counter(AG.launch_counts)
     try:
-        outs = f.evaluate_differentiable(expr, 0, leaves, transform=case.fwd_transform())
+        outs = f.evaluate_differentiable(expr, 0, leaves, transform=case.fwd_transform(),
+                                         operator_gradients=case.operator_gradients)
     except NotImplementedError as exc:
         raise Refused(str(exc)) from exc
     keep = [k for k in range(expr.b) if k not in case.drop]
@@ -609,7 +692,8 @@ def run_case(torch, st: Stats, case: AGCase, dev):
 
 def _label(what: str, case: AGCase) -> str:
     extra = f" Np={case.dg.Np} b={case.dg.b} {case.dg.op}" if case.dg is not None else f" {case.ein.subs}"
-    return f"{what} {case.kind}{extra} {case.dtype} E={case.E} {case.transform} drop={list(case.drop)} {case.scale}"
+    mode = f" opgrad={case.operator_gradients} frozen={list(case.frozen)}" if case.operator_gradients != "auto" or case.frozen else ""
+    return f"{what} {case.kind}{extra} {case.dtype} E={case.E} {case.transform} drop={list(case.drop)} {case.scale}{mode}"
 
 
 def _compare(st: Stats, label: str, case: AGCase, fwd, grads, rfwd, rgrads, deps=None, value=None) -> bool:
@@ -688,6 +772,7 @@ def _prepare(torch, case: AGCase, st: Stats):
         rfwd, rgrads = device_references(torch, case, dev)
         _slice_checks(torch, st, _label("reference", case), case, dev, scales, rfwd, rgrads,
                       np.random.default_rng(case.seed + 1))
+    rgrads = {k: (None if k in case.frozen else v) for k, v in rgrads.items()}     # an input without requires_grad gets none
     return dev, rfwd, rgrads
 
 
@@ -725,20 +810,37 @@ def bounded_cases(n: int, seed: int) -> List[AGCase]:
               _dg(rng, "bgrad", "ragged", "float64", b=17, Np=20, Nfp=10)):
         out.append(_dg_case(rng, replace(c, E=min(c.E, 129)), partial_share=0.0))
     out += [c for c in einsum_cases(max(n // 4, 4), seed + 5) if c.E <= 1100]
-    return out
+    rng = random.Random(seed + 61)      # a fixed share under operator_gradients="kernel"
+    kernel = [with_kernel(c) for c in out if c.dg is not None][::4]
+    for kind, b in (("grad", 1), ("div", 1), ("fm", 9), ("bgrad", 9), ("divcomp", 1), ("mass", 2), ("lift2", 2)):
+        order = dict(Np=15, Nfp=5) if kind == "lift2" else dict(Np=35, Nfp=15)
+        c = replace(_dg(rng, kind, "ragged", "float64", b=b, **order), E=rng.choice([65, 129, 1003]))
+        kernel.append(with_kernel(_dg_case(rng, c, partial_share=0.0)))
+    return out + kernel
 
 
-def bound_of(expr, drop, wrt: str, E: int) -> Tuple[int, float, bool]:
+def bound_of(expr, drop, wrt: str, E: int, operator_gradients: str = "auto") -> Tuple[int, float, bool]:
     """``(n, u, rounded)`` of a gradient's bound: n = the largest ``operands - 1 + summed points (+ schedule steps)``
     of its term rows plus the additions across terms and rows; u the largest unit roundoff of its rows; *rounded*: a
-    float32 operand of a float64 einsum (one more float32 rounding at the end)."""
+    float32 operand of a float64 einsum (one more float32 rounding at the end).  A term on the operator-gradient
+    kernels: the n tests/test_gpu_opgrad.py derives from ``fe_opgrad_plan`` -- the products per entry, two roundings
+    of the J-weighted factor, and the combine: a lane's slices in order, six butterfly steps."""
+    from feinsum_amd import _hip
+
     ns, us, rows = [], [], 0
-    for w, _, sub, _ in plan_backward(expr, drop):
+    for w, route, sub, _ in plan_backward(expr, drop, operator_gradients):
         if w != wrt:
             continue
         for row in sub.args:
             dts = [a.dtype for a in row]
             k = len(row)
+            if route in OPGRAD_ROUTES:
+                entries = int(np.prod([int(sub.index_to_dim_length[i]) for i in sub.out_idx_set]))
+                slices = _hip.opgrad_plan(E, entries)[0]
+                ns.append(2 + ref_.summed_points(sub.get_subscripts(), _extent(sub, E)) + 6 + -(-slices // 64))
+                us.append(ref_.U64)
+                rows += 1
+                continue
             ns.append(ref_.bound_terms(sub.get_subscripts(), _extent(sub, E), k, k - 1 if k >= 3 else 0))
             us.append(ref_.unit_roundoff(dts, k))
             rows += 1
@@ -810,10 +912,10 @@ def run_bounded(n: int, seed: int) -> Stats:
         st.cov.update(bk)
         for wrt in sorted(expr.all_args):
             if grads[wrt] is None:
-                if any(w == wrt for w, _, _, _ in plan_backward(expr, case.drop)):
+                if wrt not in case.frozen and any(w == wrt for w, _, _, _ in plan_backward(expr, case.drop)):
                     st.fail(f"{label}: d{wrt} missing  REPRO {case.repro()}")
                 continue
-            n_, u, rounded = bound_of(expr, case.drop, wrt, case.E)
+            n_, u, rounded = bound_of(expr, case.drop, wrt, case.E, case.operator_gradients)
             ref, absref = bounded_grad(expr, case.drop, host, wrt)
             ratio = grad_bound_ratio(grads[wrt].cpu().numpy(), ref, absref, n_, u, rounded)
             for b_ in bk:
@@ -879,6 +981,8 @@ def nonfinite_cases(n: int, seed: int) -> List[AGCase]:
              _dg(rng, "mass", "tiles", "float64", b=2, Np=35, Nfp=15)]
     out += [_dg_case(rng, c, partial_share=0.0) for c in fixed]
     out += einsum_cases(4, seed + 7)[:6]
+    # under operator_gradients="kernel": the fixed cases again (plants in the output gradient and in J among them)
+    out += [with_kernel(_dg_case(rng, replace(c, seed=rng.randrange(1 << 30)), partial_share=0.0)) for c in fixed]
     return out
 
 
@@ -901,7 +1005,8 @@ def run_nonfinite(n: int, seed: int) -> Stats:
             label = _label("nonfinite", case) + f" {value} in {key}{list(idx)}"
             _check_routes(st, label, case, delta)
             st.cov.update([f"planted:{role}", f"value:{value}", f"kind:{case.kind}", f"dtype:{case.dtype}"]
-                          + [f"route:{r}" for r in dict.fromkeys(routes)])
+                          + [f"route:{r}" for r in dict.fromkeys(routes)]
+                          + ([f"opgrad:planted:{role}"] if any(r in OPGRAD_ROUTES for r in routes) else []))
             _compare(st, label, case, fwd, grads, rfwd, rgrads, deps, value)
             dev[key][idx] = old
         del dev, rfwd, rgrads
@@ -924,6 +1029,11 @@ def large_cases(seed: int, sizes: Sequence[int] = LARGE_E) -> List[AGCase]:
             out.append(AGCase(c, None, "auto"))
     out.append(AGCase(D.DGCase("grad", 35, 15, 1, "rij", "float32", 100_003, "large", rng.randrange(1 << 30)), None,
                       "auto"))
+    if tuple(sizes) == LARGE_E:      # past the slice cap of fe_opgrad_plan (64 x 1023 elements): the operator-gradient kernels
+        for kind, b, op in (("grad", 1, "rij"), ("div", 1, "rij"), ("fm", 9, "rij"), ("grad", 1, "rji"), ("fm_jfi", 9, "rij"),
+                            ("fm_fji", 2, "rij")):
+            c = D.DGCase(kind, 35, 15, b, op, "float64", MULTI_TRIP_E, "large", rng.randrange(1 << 30))
+            out.append(AGCase(c, None, "auto", operator_gradients="kernel"))
     return out
 
 
@@ -960,6 +1070,7 @@ def run_large(seed: int, sizes: Sequence[int] = LARGE_E) -> Stats:
         routes = _check_routes(st, label, case, delta)
         st.cov.update([f"large:{case.kind}", f"dtype:{case.dtype}", f"E:{case.E}"]
                       + [f"route:{r}" for r in dict.fromkeys(routes)]
+                      + ([f"opgrad:large:{case.kind}:E{case.E}"] if any(r in OPGRAD_ROUTES for r in routes) else [])
                       + (["route:facemass_j:b>8"] if "facemass_j" in routes and case.expr().b > 8 else []))
         _compare(st, label, case, fwd, grads, rfwd, rgrads)
         del dev, rfwd, rgrads, fwd, grads
@@ -1089,7 +1200,7 @@ class _KernelArrays:
                 self._bufs.append((buf, nn))
                 self.out[name] = out
             return
-        shifts = kernel_shifts(placement, ins, list(outs))
+        shifts = {"ws": 0, **kernel_shifts(placement, ins, [n for n in outs if n != "ws"])}     # (a workspace must be 256-byte aligned)
         self._ins = {}
         for name, _ in ins:
             emb = D.embed(torch, x[name].shape, torch.float64, shifts[name], "in", torch.from_numpy(x[name]), DEVICE)
@@ -1134,6 +1245,77 @@ def _kernel_checks(st: Stats, label: str, arrays: _KernelArrays, got) -> None:
             st.exact_equal += 1
 
 
+OPGRAD_E = KERNEL_E + (65, 66)      # 65: the smallest E with two slices (fe_opgrad_plan)
+OPGRAD_OUT_LAYOUTS = ("rpq", "rqp")
+
+
+def opgrad_runs(seed: int) -> List[Tuple[int, int, int, str, str, int, int, int]]:
+    """``(Np, X, R, J layout, output layout, fields, E, seed)`` of direct ``fe_opgrad_f64`` calls: every compiled Np x
+    J layout ("xre", "re", "er", "e") x output layout, (X, R) and one or two fields in turn, E from :data:`OPGRAD_E`."""
+    rng = random.Random(seed + 67)
+    out = []
+    k = 0
+    for Np in GEOMADJ_NP:
+        for lay in GEOM_LAYOUTS:
+            for ol in OPGRAD_OUT_LAYOUTS:
+                X = (1, 2, 3)[k % 3] if lay == "xre" else 1
+                R = 1 if lay == "e" else (3, 1, 2)[(k // 2) % 3]
+                out.append((Np, X, R, lay, ol, 1 + k % 2, OPGRAD_E[(k + k // 7) % len(OPGRAD_E)], rng.randrange(1 << 30)))
+                k += 1
+    return out
+
+
+def facemass_opgrad_runs(seed: int) -> List[Tuple[Tuple[int, int, int], Tuple[str, str, int], int, int, int]]:
+    """``((nf, Np, Nfp), (J layout, R layout, flags), b, E, seed)`` of direct ``fe_facemass_opgrad_f64`` calls: every
+    compiled shape x the eight flag combinations, b in {1, 2, 4, 9} in turn (9: a second launch adding to its own
+    slice), E from :data:`OPGRAD_E`."""
+    rng = random.Random(seed + 71)
+    out = []
+    k = 0
+    for shape in FACEMASS_ADJ_SHAPES:
+        for lay in FM_LAYOUT_FLAGS:
+            out.append((shape, lay, (1, 2, 4, 9)[(k + k // 8) % 4], OPGRAD_E[(k + k // 7) % len(OPGRAD_E)], rng.randrange(1 << 30)))
+            k += 1
+    return out
+
+
+def placement_opgrad_runs(seed: int):
+    """``(opgrad runs, facemass opgrad runs)`` of the placement pass: every J layout x output layout at four of the
+    compiled Np, and every flag combination of face-mass at p = 1 and p = 4 of the tetrahedra."""
+    og = [r for r in opgrad_runs(seed) if r[0] in (4, 10, 21, 35)]
+    fm = [r for r in facemass_opgrad_runs(seed) if r[0] in ((4, 4, 3), (4, 35, 15))]
+    return og, fm
+
+
+_OPGRAD_J = {"xre": (lambda X, R, E: (X, R, E), lambda R, E: (R * E, E, 1)), "re": (lambda X, R, E: (R, E), lambda R, E: (0, E, 1)),
+             "er": (lambda X, R, E: (E, R), lambda R, E: (0, 1, R)), "e": (lambda X, R, E: (E,), lambda R, E: (0, 0, 1))}
+_FM_PERM = {"fij": (0, 1, 2), "ifj": (1, 0, 2), "fji": (0, 2, 1), "jfi": (2, 0, 1)}     # dR [f][i][j] in R's stored layout
+
+
+def opgrad_reference(mJ, ma, mb, layout: str, ol: str) -> np.ndarray:
+    """``out[r, p, q] = sum_k sum_e (sum_x J[x, r, e] b_k[x, e, p]) a_k[e, q]`` in int64, in the output's stored layout."""
+    J = {"xre": lambda j: j, "re": lambda j: j[None], "er": lambda j: j.T[None], "e": lambda j: j[None, None]}[layout](mJ)
+    out = sum(_int_einsum("xre,eq,xep->rpq", [J, a, b]) for a, b in zip(ma, mb))
+    return out if ol == "rpq" else np.ascontiguousarray(out.transpose(0, 2, 1))
+
+
+def facemass_opgrad_reference(mJ, mg, mv, jl: str, rl: str) -> np.ndarray:
+    Jef = mJ if jl == "ef" else mJ.T
+    out = sum(_int_einsum("ei,ef,fej->fij", [g, Jef, v]) for g, v in zip(mg, mv))
+    return np.ascontiguousarray(out.transpose(_FM_PERM[rl]))
+
+
+def _with_workspace(outs: Dict[str, Tuple[int, ...]], E: int, entries: int) -> Tuple[Dict[str, Tuple[int, ...]], int]:
+    """The outputs of an operator-gradient call plus its workspace of exactly the planned bytes (``fe_opgrad_plan``):
+    embedded like an output, so a write behind the planned bytes lands in a guard band; the library asks for a 256-byte
+    aligned workspace, so it is never shifted."""
+    from feinsum_amd import _hip
+
+    nbytes = _hip.opgrad_plan(E, entries)[1]
+    assert nbytes % 8 == 0
+    return ({**outs, "ws": (nbytes // 8,)} if nbytes else dict(outs)), nbytes
+
+
 def placement_kernel_runs(seed: int):
     """``(geomadj runs, facemass runs)`` of the placement pass: a subset of :func:`geomadj_runs` (every Np, output
     layout and operator layout; every (X, R) of "xre") and face-mass runs of every compiled shape and layout with b
@@ -1155,9 +1337,12 @@ def placement_kernel_runs(seed: int):
     return geom, fm
 
 
-def run_kernels(seed: int, geom_runs=None, fm_runs=None, placement: Optional[str] = None) -> Stats:
+def run_kernels(seed: int, geom_runs=None, fm_runs=None, placement: Optional[str] = None, og_runs=None,
+                ogfm_runs=None) -> Stats:
     """Every :func:`geomadj_runs` / :func:`facemass_runs` combination through ``_hip.geomadj`` /
-    ``_hip.facemass_adj``, exact data (scale 1), outputs in NaN-filled buffers between guard bands.  With *placement*
+    ``_hip.facemass_adj``, and every :func:`opgrad_runs` / :func:`facemass_opgrad_runs` combination through
+    ``_hip.opgrad`` / ``_hip.facemass_opgrad`` (the workspace an output of exactly the planned bytes),
+    exact data (scale 1), outputs in NaN-filled buffers between guard bands.  With *placement*
     (:data:`KERNEL_PLACEMENTS`) every array sits at that placement's address offset between bands
     (:class:`_KernelArrays`), and the inputs must come back unchanged."""
     import torch
@@ -1212,6 +1397,44 @@ def run_kernels(seed: int, geom_runs=None, fm_runs=None, placement: Optional[str
                       + ([f"place:{placement}"] if placement else []))
         _kernel_checks(st, label, arrays, ([(f"dv{k}", dvs[k], dv_want[k]) for k in range(b)] if with_dv else []) +
                        ([("dJ", dJ, dJ_want)] if with_dJ else []))
+    for Np, X, R, lay, ol, nk, E, s in (opgrad_runs(seed) if og_runs is None else og_runs):
+        rng = np.random.default_rng(s)
+        shapes = {"J": _OPGRAD_J[lay][0](X, R, E)}
+        for k in range(nk):
+            shapes[f"a{k}"], shapes[f"b{k}"] = (E, Np), (X, E, Np)
+        m, x = _exact(rng, shapes, [(["J", f"a{k}", f"b{k}"], E * X * nk) for k in range(nk)])
+        outs, nbytes = _with_workspace({"out": (R, Np, Np)}, E, R * Np * Np)
+        ins = [("J", "geometry")] + [(f"a{k}", "field") for k in range(nk)] + [(f"b{k}", "field") for k in range(nk)]
+        arrays = _KernelArrays(torch, placement, x, ins, outs)
+        d, out = arrays.d, arrays.out["out"]
+        _hip.opgrad(d["J"].data_ptr(), [d[f"a{k}"].data_ptr() for k in range(nk)], [d[f"b{k}"].data_ptr() for k in range(nk)],
+                    out.data_ptr(), E, X, R, Np, _OPGRAD_J[lay][1](R, E), (Np * Np, Np, 1) if ol == "rpq" else (Np * Np, 1, Np),
+                    arrays.out["ws"].data_ptr() if nbytes else None, nbytes)
+        torch.cuda.synchronize()
+        label = f"opgrad Np={Np} X={X} R={R} {lay} {ol} fields={nk} E={E} seed={s}{tag}"
+        st.cov.update([f"opgrad:Np{Np}", f"opgrad:{lay}", f"opgrad:{ol}", f"opgrad:{lay},{ol}", f"opgrad:E{E}"]
+                      + (["opgrad:workspace"] if nbytes else []) + ([f"place:{placement}"] if placement else []))
+        want = opgrad_reference(m["J"], [m[f"a{k}"] for k in range(nk)], [m[f"b{k}"] for k in range(nk)], lay, ol)
+        _kernel_checks(st, label, arrays, [("out", out, want)])
+    for (nf, Np, Nfp), (jl, rl, flags), b, E, s in (facemass_opgrad_runs(seed) if ogfm_runs is None else ogfm_runs):
+        rng = np.random.default_rng(s)
+        shapes = {"J": (E, nf) if jl == "ef" else (nf, E)}
+        for k in range(b):
+            shapes[f"g{k}"], shapes[f"v{k}"] = (E, Np), (nf, E, Nfp)
+        m, x = _exact(rng, shapes, [(["J", f"g{k}", f"v{k}"], E * b) for k in range(b)])
+        outs, nbytes = _with_workspace({"dR": _r_shape(rl, nf, Np, Nfp)}, E, nf * Np * Nfp)
+        ins = [("J", "geometry")] + [(f"g{k}", "field") for k in range(b)] + [(f"v{k}", "field") for k in range(b)]
+        arrays = _KernelArrays(torch, placement, x, ins, outs)
+        d, dR = arrays.d, arrays.out["dR"]
+        _hip.facemass_opgrad(d["J"].data_ptr(), [d[f"g{k}"].data_ptr() for k in range(b)], [d[f"v{k}"].data_ptr() for k in range(b)],
+                             dR.data_ptr(), E, Np, nf, Nfp, arrays.out["ws"].data_ptr() if nbytes else None, nbytes,
+                             layout_flags=flags)
+        torch.cuda.synchronize()
+        label = f"facemass_opgrad (nf, Np, Nfp)=({nf}, {Np}, {Nfp}) {jl},{rl} b={b} E={E} seed={s}{tag}"
+        st.cov.update([f"opgrad_fm:Np{Np}", f"opgrad_fm:{jl},{rl}", f"opgrad_fm:b{b}", f"opgrad:E{E}"]
+                      + (["opgrad:workspace"] if nbytes else []) + ([f"place:{placement}"] if placement else []))
+        want = facemass_opgrad_reference(m["J"], [m[f"g{k}"] for k in range(b)], [m[f"v{k}"] for k in range(b)], jl, rl)
+        _kernel_checks(st, label, arrays, [("dR", dR, want)])
     return st
 
 

@@ -4,7 +4,8 @@ oracle/einsum_ref.py (test infrastructure, like tests/).
 
     python tools/fuzz_dg.py [n_cases] [seed]
     python tools/fuzz_dg.py --placement [seed]
-    python tools/fuzz_dg.py --repro '<REPRO line of either kind>'
+    python tools/fuzz_dg.py --accumulate [seed]
+    python tools/fuzz_dg.py --repro '<REPRO line of any kind>'
 
 Passes:
 
@@ -26,6 +27,20 @@ Passes:
                    launch (no float64 route looks at more than ``& 7`` of a pointer, so the same kernel runs the same
                    arithmetic; float32 and mixed cases may move between the matrix-core and the tiled kernel and
                    get the bound alone).  A launch accepted aligned must be accepted at every placement.
+
+``run_accumulate`` accumulating evaluation, ``out <- alpha E + beta out``, on the routes "kernel",
+                   "epilogue" and "axpby", the route predicted on the host (``measure.accumulate_route``) and asserted on
+                   the device; a route refused on the host must be refused with every output bitwise unchanged.  Four
+                   parts.  ``run_accumulate_exact``: exact operands, old outputs on the grid of the sum, nine factor
+                   pairs; the contract ``fma(alpha, E, fl(beta old))`` fixes every bit: the whole array for powers of
+                   two (:func:`combine_pow2`), a correctly rounded integer reference (:func:`combine_entry`) for general
+                   factors, float32 rounded once, near overflow and in the subnormal range too.
+                   ``run_accumulate_bounded``: signed data within ``gamma(K + 2, u) (|alpha| absref + |beta| |old|)``,
+                   float64 bitwise the "axpby" route, powers of two bitwise torch's two passes.
+                   ``run_accumulate_nonfinite``: a NaN / Inf in a field, a geometry factor, an operator entry or an old
+                   output; poisoned old outputs under beta = 0; alpha = 0 with a non-finite E gives NaN.
+                   ``run_accumulate_placement``: the placements of ``run_placement`` with the outputs holding old
+                   values between sentinel bands.
 
 Outputs land in NaN-filled buffers between sentinel guard bands (tools/fuzz_einsum.py).  Runs are counted per family,
 order, dtype, transform, E class, walk and fused / prepared (:data:`MINIMUMS`).
@@ -133,6 +148,13 @@ class DGCase:
         elif k.startswith("fm") or k == "lift2":
             nf = 3 if k == "lift2" else 4
             layout = "fm" if k == "lift2" else k
+            if k.startswith("fm:"):   # "fm:<J layout>:<R layout>": the eight layouts of the accumulating pass
+                _, jl, rl = k.split(":")
+                rshape = {"fij": (nf, Np, Nfp), "ifj": (Np, nf, Nfp), "fji": (nf, Nfp, Np), "jfi": (Nfp, nf, Np)}[rl]
+                rows = [[A("J", ("E", nf) if jl == "ef" else (nf, "E")), A("R", rshape), A(f"v{i}", (nf, "E", Nfp), True)]
+                        for i in range(b)]
+                expr = f.batched_einsum(f"{jl},{rl},fej->ei", rows)
+                return [(expr, {nm: nm for nm in expr.all_args})]
             rows = []
             for i in range(b):
                 v = A(f"v{i}", (nf, "E", Nfp), True)
@@ -248,8 +270,9 @@ def _terms(expr) -> int:
     return ref_.summed_points(f"{ins}->{out}", ext)
 
 
-def plan_data(case: DGCase, rng: np.random.Generator):
-    """``(bits, scales, dtypes, significand)`` per data key."""
+def plan_data(case: DGCase, rng: np.random.Generator, headroom: int = 0):
+    """``(bits, scales, dtypes, significand)`` per data key (*headroom*: bits of the significand left unused, for the
+    accumulating pass, which scales the sum and adds an old output to it)."""
     stages = case.stages()
     dtypes = {}
     rows = []
@@ -258,7 +281,7 @@ def plan_data(case: DGCase, rng: np.random.Generator):
             rows.append(([keys[a.name] for a in row], _terms(expr)))
             for a in row:
                 dtypes[keys[a.name]] = np.dtype(a.dtype)
-    sig = 24 if case.dtype == "float32" else 53
+    sig = (24 if case.dtype == "float32" else 53) - headroom
     if case.scale == "subnormal":
         sig -= 4     # every sum below the smallest normal: subnormal results
     f32 = [k for k, d in dtypes.items() if d == np.dtype("float32")]
@@ -276,10 +299,10 @@ def _shape(expr, name: str, E: int) -> Tuple[int, ...]:
     return tuple(E if isinstance(d, f.SizeParam) else int(d) for d in expr.arg_to_shape[name])
 
 
-def host_data(case: DGCase, extra: int = 0):
+def host_data(case: DGCase, extra: int = 0, headroom: int = 0):
     """``(arrays by key, mantissas by key, scales, significand)`` of exact data for the case."""
     rng = np.random.default_rng(case.seed + 7919 * extra)
-    bits, scales, dtypes, sig = plan_data(case, rng)
+    bits, scales, dtypes, sig = plan_data(case, rng, headroom)
     shapes = {}
     for expr, keys in case.stages():
         for nm, k in keys.items():
@@ -702,11 +725,11 @@ def large_cases(seed: int, sizes: Sequence[int] = LARGE_E, f32: bool = True) -> 
     return out
 
 
-def device_data(torch, case: DGCase):
+def device_data(torch, case: DGCase, headroom: int = 0):
     """Exact data made on the device (large E): ``(tensors by key, scales, significand)``; mantissas are recovered from
     the values for the slice checks (``x * 2**-s`` is exact)."""
     rng = np.random.default_rng(case.seed)
-    bits, scales, dtypes, sig = plan_data(case, rng)
+    bits, scales, dtypes, sig = plan_data(case, rng, headroom)
     gen = torch.Generator(device="cuda").manual_seed(case.seed)
     dev = {}
     for expr, keys in case.stages():
@@ -915,17 +938,21 @@ class PlacedRun:
     placement: str
     shifts: Tuple[Tuple[str, int], ...] = ()
     knobs: Tuple[Tuple[str, Any], ...] = ()
+    acc: Tuple[Any, ...] = ()      # an accumulating run: (alpha, beta, forced route, old shift) of its AccCase
 
     def repro(self) -> str:
-        return json.dumps({"case": asdict(self.case), "data": self.data, "transform": self.transform,
-                           "placement": self.placement, "shifts": dict(self.shifts), "knobs": dict(self.knobs)},
-                          separators=(",", ":"))
+        d = {"case": asdict(self.case), "data": self.data, "transform": self.transform,
+             "placement": self.placement, "shifts": dict(self.shifts), "knobs": dict(self.knobs)}
+        if self.acc:
+            d["accumulate"] = list(self.acc)
+        return json.dumps(d, separators=(",", ":"))
 
     @staticmethod
     def from_repro(text: str) -> "PlacedRun":
         d = json.loads(text)
         return PlacedRun(DGCase(**d["case"]), d["data"], d["transform"], d["placement"],
-                         tuple(sorted(d["shifts"].items())), tuple(sorted(d["knobs"].items())))
+                         tuple(sorted(d["shifts"].items())), tuple(sorted(d["knobs"].items())),
+                         tuple(d.get("accumulate", ())))
 
 
 def slots_of(case: DGCase):
@@ -1346,9 +1373,1001 @@ def repro_placement(text: str) -> Stats:
     return st
 
 
+# --------------------------------------------------------------------------
+# accumulating evaluation: out <- alpha E + beta out
+# --------------------------------------------------------------------------
+
+#: the six pairs of tests/test_gpu_accumulate.py (AB), two general pairs (the second with |alpha| < 1 < |beta|) and a pair
+#: of large powers of two
+ACC_AB = ((1.0, 1.0), (-1.0, 1.0), (2.0, -0.5), (0.5, 0.0), (0.0, 1.0), (0.0, 0.0))
+ACC_GENERAL = ((0.3, -1.7), (-0.7, 2.3))
+ACC_BIG = ((-2.0 ** -3, 2.0 ** 5),)
+ACC_PAIRS = ACC_AB + ACC_GENERAL + ACC_BIG
+ACC_ROUTES = (None, "axpby", "kernel", "epilogue")
+#: bits of the significand the operands of an accumulating case leave unused, and the bits of an old output's mantissa
+#: below that budget: with |sum| <= 2^(sig - 8), |old mantissa| < 2^(sig - 16), old outputs 0 or 3 binary places above
+#: the grid of the sum and factors 2^-3 ... 2^5, alpha sum + beta old is below 2^(sig - 3) grid units of the finest of
+#: the three grids (:func:`acc_budget_ok`): exact for every power-of-two pair
+ACC_HEADROOM = 8
+ACC_OLD_BITS_BELOW = 8
+ACC_OLD_SHIFTS = (0, 3)
+#: general pairs: the correctly rounded reference covers the whole array up to this E; above it the first and the last
+#: ACC_EDGE elements (a wave tile is at most 80 elements) and a seeded sample of ACC_SAMPLE entries
+ACC_WHOLE_E = 129
+ACC_EDGE = 80
+ACC_SAMPLE = 4096
+ACC_FM_KINDS = tuple(f"fm:{jl}:{rl}" for jl in ("ef", "fe") for rl in ("fij", "ifj", "fji", "jfi"))
+ACC_KINDS = KINDS + ACC_FM_KINDS
+TET_ORDERS = ORDERS3[:4]                    # p = 1..4: the orders of the three accumulating kernels
+TEL_SIZES = ("tel-1", "tel", "tel+1", "2tel+3")
+ACC_SMALL_E = (1, 5, 16, 17, 33, 64, 65, 129, 1003, 4099)
+FORMAT = {np.dtype("float64"): (53, -1074, 1023), np.dtype("float32"): (24, -149, 127)}   # significand, quantum, emax
+
+
+def is_pow2(x: float) -> bool:
+    """Zero or a signed power of two."""
+    return x == 0.0 or math.frexp(abs(x))[0] == 0.5
+
+
+@dataclass(frozen=True)
+class AccCase:
+    """An accumulating case: the DG case, the factors as the caller passes them, the forced route (``None``: what
+    ``measure.accumulate_route`` picks), the forward transform's name and how many binary places the grid of the old
+    outputs lies above the grid of the sum.  ``case.E == -1``: a size named by ``case.eclass`` ("tel+1", ...,
+    "second-tile") that :func:`acc_resolve` reads from the launcher."""
+
+    case: DGCase
+    alpha: float
+    beta: float
+    route: Optional[str] = None
+    transform: str = "auto"
+    old_shift: int = 0
+
+    def repro(self) -> str:
+        return json.dumps({"accumulate": {"alpha": self.alpha, "beta": self.beta, "route": self.route,
+                                          "transform": self.transform, "old_shift": self.old_shift},
+                           "case": asdict(self.case)}, separators=(",", ":"))
+
+    @staticmethod
+    def from_repro(text: str) -> "AccCase":
+        d = json.loads(text)
+        a = d["accumulate"]
+        return AccCase(DGCase(**d["case"]), float(a["alpha"]), float(a["beta"]), a["route"], a["transform"],
+                       int(a["old_shift"]))
+
+    def out_dtype(self) -> np.dtype:
+        return np.dtype("float32") if self.case.dtype == "float32" else np.dtype("float64")
+
+    def factors(self) -> Tuple[float, float]:
+        """``(alpha, beta)`` as the launch applies them: cast to float32 for float32 outputs."""
+        if self.case.dtype == "float32":
+            return float(np.float32(self.alpha)), float(np.float32(self.beta))
+        return self.alpha, self.beta
+
+    def pow2(self) -> bool:
+        return is_pow2(self.alpha) and is_pow2(self.beta)
+
+    def family(self) -> Optional[str]:
+        """"fm", "grad" or "div" for the kinds the accumulating kernels serve."""
+        k = self.case.kind
+        return "fm" if k.startswith("fm") else k if k in ("grad", "div") else None
+
+
+def acc_transform(ac: AccCase) -> Any:
+    """The ``transform`` argument of the case: the forward transform and the forced route in one mapping."""
+    t: Dict[str, Any] = {}
+    if ac.transform == "prepared":
+        t["prepared"] = True
+    elif ac.transform != "auto":
+        t["variant"] = ac.transform
+    if ac.route is not None:
+        t["accumulate"] = ac.route
+    return t or None
+
+
+def predicted_route(ac: AccCase) -> Optional[str]:
+    """The route the host predicts (``measure.accumulate_route``), or ``None`` where the host refuses the case."""
+    from feinsum_amd.measure import accumulate_route
+
+    expr, _ = ac.case.stages()[0]
+    try:
+        launch_kind(expr, acc_transform(ac), {"E": max(ac.case.E, 1)})
+        return accumulate_route(expr, acc_transform(ac))
+    except NotImplementedError:
+        return None
+
+
+# ---- the combine reference: fl(alpha E + fl(beta old)), E exact
+
+def _decompose(x: float) -> Tuple[int, int]:
+    """``(m, e)`` with ``x == m * 2**e``, Python integers."""
+    m, e = math.frexp(x)
+    return int(m * (1 << 53)), e - 53
+
+
+def fl_int(R: int, g: int, dtype) -> float:
+    """``R * 2**g`` rounded to nearest, ties to even, into *dtype* (subnormals and overflow included): Python integers."""
+    sig, quantum, emax = FORMAT[np.dtype(dtype)]
+    if R == 0:
+        return 0.0
+    a = abs(R)
+    qe = max(a.bit_length() - 1 + g - (sig - 1), quantum)
+    drop = qe - g
+    if drop > 0:
+        q, rem = a >> drop, a & ((1 << drop) - 1)
+        half = 1 << (drop - 1)
+        if rem > half or (rem == half and q & 1):
+            q += 1
+    else:
+        q, qe = a, g
+    if q.bit_length() + qe - 1 > emax:
+        return math.copysign(math.inf, R)
+    return math.copysign(math.ldexp(float(q), qe), R)      # q <= 2**sig: exact
+
+
+def combine_entry(ms: int, t: int, alpha: float, beta: float, old: float, dtype) -> float:
+    """One entry of the contract: ``E = ms * 2**t`` exactly, ``p = fl(beta * old)`` (not read when beta is 0), then the
+    single rounding of ``alpha * E + p``.  *alpha*, *beta* as the launch applies them (:meth:`AccCase.factors`)."""
+    p = 0.0
+    if beta != 0.0:
+        mb, eb = _decompose(beta)
+        mo, eo = _decompose(old)
+        p = fl_int(mb * mo, eb + eo, dtype)
+    ma, ea = _decompose(alpha)
+    mp, ep = _decompose(p)
+    if not mp:
+        return fl_int(ma * ms, t + ea, dtype)
+    g = min(t + ea, ep)
+    return fl_int((ma * ms << (t + ea - g)) + (mp << (ep - g)), g, dtype)
+
+
+def _bit_length(a: np.ndarray) -> np.ndarray:
+    x, n = a.copy(), np.zeros(a.shape, dtype=np.int64)
+    for s in (32, 16, 8, 4, 2, 1):
+        big = (x >> s) != 0
+        n += big * s
+        x = np.where(big, x >> s, x)
+    return n + (x != 0)
+
+
+def round_to_format(R: np.ndarray, g: int, dtype) -> np.ndarray:
+    """:func:`fl_int` on an int64 array with ``|R| < 2**60`` (no overflow of the format: asserted)."""
+    sig, quantum, _ = FORMAT[np.dtype(dtype)]
+    R = np.asarray(R, dtype=np.int64)
+    a = np.abs(R)
+    assert not a.size or int(a.max()) < (1 << 60)
+    qe = np.maximum(_bit_length(a) - 1 + g - (sig - 1), quantum)
+    drop = np.minimum(np.maximum(qe - g, 0), 61)
+    q = a >> drop
+    rem = a - (q << drop)
+    half = np.where(drop > 0, np.int64(1) << np.maximum(drop - 1, 0), 0)
+    q = q + ((drop > 0) & ((rem > half) | ((rem == half) & ((q & 1) == 1))))
+    val = np.ldexp(q.astype(np.float64), (g + drop).astype(np.int64))
+    out = (np.sign(R) * val).astype(np.dtype(dtype))
+    assert np.isfinite(out).all(), "the reference overflows its format"
+    return out
+
+
+def combine_pow2(ms: np.ndarray, t: int, alpha: float, beta: float, mo: np.ndarray, go: int, dtype) -> np.ndarray:
+    """The contract on whole arrays for factors that are zero or signed powers of two: ``E = ms * 2**t``,
+    ``old = mo * 2**go``.  ``beta * old`` rounds where it falls below the quantum of the format, and so does the sum."""
+    assert is_pow2(alpha) and is_pow2(beta)
+    _, quantum, _ = FORMAT[np.dtype(dtype)]
+    ms, mo = np.asarray(ms, dtype=np.int64), np.asarray(mo, dtype=np.int64)
+    A, a = (0, 0) if alpha == 0 else (int(math.copysign(1, alpha)), math.frexp(abs(alpha))[1] - 1)
+    B, b = (0, 0) if beta == 0 else (int(math.copysign(1, beta)), math.frexp(abs(beta))[1] - 1)
+    p = round_to_format(B * mo, go + b, dtype).astype(np.float64)
+    gp = max(quantum, go + b)
+    g = min(t + a, gp) if A and B else (t + a) if A else gp
+    P = np.ldexp(p, -g)
+    assert (P == np.rint(P)).all()
+    return round_to_format(A * ms * (1 << (t + a - g) if A else 0) + P.astype(np.int64), g, dtype)
+
+
+def acc_old_bits(sig: int) -> int:
+    """Mantissa bits of an old output, *sig* being the operands' budget (``plan_data`` with ACC_HEADROOM)."""
+    return max(sig - ACC_OLD_BITS_BELOW, 1)
+
+
+def acc_budget_ok(sig: int, out_sig: int) -> bool:
+    """Whether ``alpha sum + beta old`` is exact for every power-of-two pair of :data:`ACC_PAIRS` and every old shift:
+    in units of the finest grid involved the absolute value stays within ``2**out_sig`` (Python integers)."""
+    ob = acc_old_bits(sig)
+    for alpha, beta in ACC_PAIRS:
+        if not (is_pow2(alpha) and is_pow2(beta)):
+            continue
+        a = math.frexp(abs(alpha))[1] - 1 if alpha else None
+        b = math.frexp(abs(beta))[1] - 1 if beta else None
+        for sh in ACC_OLD_SHIFTS:
+            grids = [x for x in (a, None if b is None else b + sh) if x is not None]
+            if not grids:
+                continue
+            g = min(grids)
+            worst = ((1 << sig) << (a - g) if a is not None else 0) + ((1 << ob) << (b + sh - g) if b is not None else 0)
+            if worst > (1 << out_sig):
+                return False
+    return True
+
+
+def acc_old(ac_case: DGCase, sig: int, t: int, shift: int, out_dt) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """``[(mantissas, values)]`` per output: old outputs ``m * 2**(t + shift)`` on (a multiple of) the grid of the sum,
+    the same for every pair of a case."""
+    expr, _ = ac_case.stages()[0]
+    shape = tuple(ac_case.E if isinstance(d, f.SizeParam) else int(d) for d in expr.shape)
+    rng = np.random.default_rng(ac_case.seed + 104_729 + shift)
+    top = (1 << acc_old_bits(sig)) - 1
+    out = []
+    for _ in expr.output_names:
+        m = rng.integers(-top, top + 1, size=shape, dtype=np.int64)
+        x = np.ldexp(m.astype(np.float64), t + shift).astype(out_dt)
+        assert np.array_equal(np.ldexp(x.astype(np.float64), -(t + shift)), m.astype(np.float64)), "old output not exact"
+        out.append((m, x))
+    return out
+
+
+# ---- the case list (host only)
+
+def _sym(kind, order, b, op, eclass, seed) -> DGCase:
+    return DGCase(kind, order[0], order[1], b, op, "float64", -1, eclass, seed)
+
+
+def acc_cases(seed: int) -> List[AccCase]:
+    """The fixed list of the exact part, cases of one DG case next to each other (they share data and references).
+    Face-mass under "kernel" and the default route: all eight layouts at p = 1..4, b in 2, 3, 4, 5, 8.  grad and div
+    under "epilogue": both operator layouts at p = 1..4.  Per kernel and order the sizes around the wave tile, one size
+    of several rounds and, at p = 4, one at which a wave walks a second tile.  Every kind of KINDS under "axpby" with every
+    forward transform, float64, float32 and mixed, and under the default route; face-mass with b = 1 ... 9 there.  Routes
+    forced where they do not exist (refused on the host).  The range cases.  The nine factor pairs rotate."""
+    rng = random.Random(seed + 41)
+    S = lambda: rng.randrange(1 << 30)   # noqa: E731
+    out: List[AccCase] = []
+    turn = [0]
+
+    def add(case: DGCase, route, transform="auto", n=3):
+        for _ in range(n):
+            alpha, beta = ACC_PAIRS[turn[0] % len(ACC_PAIRS)]
+            turn[0] += 1
+            out.append(AccCase(case, alpha, beta, route, transform, ACC_OLD_SHIFTS[turn[0] % 2]))
+
+    bs = (2, 3, 4, 5, 8)
+    for pi, order in enumerate(TET_ORDERS):
+        for li, kind in enumerate(ACC_FM_KINDS):
+            E = ACC_SMALL_E[(3 * pi + li) % (len(ACC_SMALL_E) - (1 if pi == 3 else 0))]
+            case = _c(kind, order, bs[(pi + li) % 5], "rij", "float64", E, S())
+            add(case, "kernel" if li % 2 else None, "mfma" if li % 4 == 3 else "auto", 4)
+        for fi, fam in enumerate(("grad", "div")):
+            for oi, op in enumerate(("rij", "rji")):
+                E = ACC_SMALL_E[(2 * pi + 5 * fi + 3 * oi + 1) % len(ACC_SMALL_E)]
+                add(_c(fam, order, 1, op, "float64", E, S()), "epilogue", "mfma" if (pi + oi) % 2 else "auto", 4)
+        for k, sym in enumerate(TEL_SIZES):
+            add(_sym(ACC_FM_KINDS[(2 * pi + k) % 8], order, bs[(pi + k) % 5], "rij", sym, S()), "kernel", n=2)
+            add(_sym("grad", order, 1, ("rij", "rji")[k % 2], sym, S()), "epilogue", n=2)
+            add(_sym("div", order, 1, ("rji", "rij")[k % 2], sym, S()), "epilogue", n=2)
+    o1, o2, o3, o4, o5, t7, t13 = ORDERS3
+    for kind, route in (("fm", "kernel"), ("grad", "epilogue"), ("div", "epilogue")):
+        add(_c(kind, o4, 2, "rij", "float64", 20_004, S()), route, n=2)
+        add(_sym(kind, o4, 2, "rij", "second-tile", S()), route, n=2)
+    # every kind under "axpby" with every forward transform and under the default route
+    dts = ("float64", "float32", "mixed")
+    b7 = (1, 2, 3, 4, 5, 8, 9)
+    for ki, kind in enumerate(KINDS):
+        orders = ORDERS2 if kind.endswith("2") else ORDERS3
+        for di in range(2):
+            order = orders[(ki + 3 * di) % len(orders)]
+            op = ("rij", "rji")[(ki + di) % 2]
+            E = (17, 65, 64, 1003, 16, 5, 129)[(ki + 4 * di) % 7]
+            case = _c(kind, order, b7[(ki + 3 * di) % 7], op[1:] if kind in ("mass", "apply") else op, dts[(ki + di) % 3], E, S())
+            for t in TRANSFORMS:
+                add(case, "axpby", t, 1)
+            add(case, None, "auto", 1)
+    for b in b7:       # face-mass of tetrahedra, float64, every field count: a single field takes "axpby" by default
+        add(_c("fm", TET_ORDERS[b % 4], b, "rij", "float64", (65, 17, 129)[b % 3], S()), None, "auto", 2)
+    for dt in dts:
+        add(_c("fm", o3, 4, "rij", dt, 64, S()), None, "auto", 1)
+        add(_c("fm", o2, 3, "rij", dt, 65, S()), "axpby", "mfma", 1)
+    # routes forced where they do not exist: refused on the host, outputs untouched on the device
+    for case, route, t in ((_c("grad", o3, 1, "rij", "float64", 65, S()), "kernel", "auto"),
+                           (_c("fm", o3, 3, "rij", "float64", 65, S()), "epilogue", "auto"),
+                           (_c("fm", o4, 1, "rij", "float64", 17, S()), "kernel", "auto"),
+                           (_c("fm", o2, 9, "rij", "float64", 17, S()), "kernel", "mfma"),
+                           (_c("grad", o5, 1, "rij", "float64", 64, S()), "epilogue", "auto"),
+                           (_c("div2", ORDERS2[2], 1, "rij", "float64", 65, S()), "epilogue", "auto"),
+                           (_c("fm", o3, 4, "rij", "float32", 64, S()), "kernel", "auto"),
+                           (_c("div", o3, 1, "rij", "mixed", 64, S()), "epilogue", "auto"),
+                           (_c("fm", o4, 4, "rij", "float64", 65, S()), "kernel", "tiled"),
+                           (_c("grad", o2, 1, "rji", "float64", 65, S()), "epilogue", "generic")):
+        add(case, route, t, 1)
+    # the range cases
+    for scale in ("overflow", "subnormal"):
+        add(_c("fm:fe:jfi", o3, 3, "rij", "float64", 65, S(), scale), "kernel", n=4)
+        add(_c("grad", o2, 1, "rji", "float64", 129, S(), scale), "epilogue", n=4)
+        add(_c("div", o4, 1, "rij", "float64", 17, S(), scale), "epilogue", n=4)
+        add(_c("cross", o3, 1, "rij", "float64", 33, S(), scale), "axpby", n=3)
+        add(_c("grad", o3, 1, "rij", "float32", 64, S(), scale), "axpby", n=3)
+        add(_c("fm", o2, 2, "rij", "float32", 17, S(), scale), None, n=3)
+    return out
+
+
+def acc_buckets(ac: AccCase) -> List[str]:
+    case = ac.case
+    route = predicted_route(ac)
+    nd = "2d" if case.kind.endswith("2") else "3d"
+    if route is None:
+        return [f"refused:{ac.route}", f"refused-family:{case.kind}"]
+    b = [f"family:{case.kind}", f"route:{route}", f"route:{route}:{nd}-{case.Np}", f"forced:{ac.route}",
+         f"pair:{ac.alpha:g},{ac.beta:g}:{route}", f"dtype:{case.dtype}", f"range:{case.scale}", f"E:{case.eclass}",
+         f"transform:{ac.transform}:{route}", "factors:" + ("pow2" if ac.pow2() else "general"), f"old-shift:{ac.old_shift}"]
+    fam = ac.family()
+    if fam == "fm" and case.dtype == "float64":
+        b.append(f"fm-fields:{case.b}")
+    if route == "kernel":
+        layout = case.kind[3:] if case.kind.startswith("fm:") else {"fm": "ef:fij", "fm_fji": "ef:fji", "fm_ifj": "fe:ifj",
+                                                                    "fm_jfi": "fe:jfi"}[case.kind]
+        b.append(f"fm-layout:{layout}:p{TET_ORDERS.index((case.Np, case.Nfp)) + 1}")
+    if route == "epilogue":
+        b.append(f"op:{fam}:{case.op}:p{TET_ORDERS.index((case.Np, case.Nfp)) + 1}")
+    if route in ("kernel", "epilogue") and case.eclass in TEL_SIZES + ("second-tile",):
+        b.append(f"size:{fam}:p{TET_ORDERS.index((case.Np, case.Nfp)) + 1}:{case.eclass}")
+    return b
+
+
+def acc_coverage(cases: Sequence[AccCase]) -> Counter:
+    cnt: Counter = Counter()
+    for ac in cases:
+        cnt.update(acc_buckets(ac))
+    return cnt
+
+
+def _pairs_by_route() -> Dict[str, int]:
+    return {f"pair:{a:g},{b:g}:{r}": 1 for a, b in ACC_PAIRS for r in ("axpby", "kernel", "epilogue")}
+
+
+#: minimum runs per bucket of the exact part of the accumulating pass (tests/test_dg_accumulate_cpu.py on the case list,
+#: tests/test_gpu_dg_accumulate.py on what ran)
+ACC_MINIMUMS = {
+    **{f"family:{k}": 2 for k in KINDS}, **{f"family:{k}": 3 for k in ACC_FM_KINDS},
+    "route:axpby": 150, "route:kernel": 120, "route:epilogue": 120,
+    **{f"route:axpby:3d-{n}": 4 for n, _ in ORDERS3}, **{f"route:axpby:2d-{n}": 1 for n in (6, 10, 15)},
+    **{f"route:{r}:3d-{n}": 20 for r in ("kernel", "epilogue") for n, _ in TET_ORDERS},
+    **{f"fm-layout:{k[3:]}:p{p}": 2 for k in ACC_FM_KINDS for p in (1, 2, 3, 4)},
+    **{f"op:{fam}:{op}:p{p}": 4 for fam in ("grad", "div") for op in ("rij", "rji") for p in (1, 2, 3, 4)},
+    **{f"size:{fam}:p{p}:{s}": 2 for fam in ("fm", "grad", "div") for p in (1, 2, 3, 4) for s in TEL_SIZES},
+    **{f"size:{fam}:p4:second-tile": 2 for fam in ("fm", "grad", "div")},
+    **_pairs_by_route(), "forced:None": 30, "forced:axpby": 150, "forced:kernel": 60, "forced:epilogue": 120,
+    "dtype:float64": 300, "dtype:float32": 50, "dtype:mixed": 40,
+    **{f"transform:{t}:axpby": 10 for t in TRANSFORMS}, "transform:mfma:kernel": 8, "transform:mfma:epilogue": 8,
+    **{f"fm-fields:{b}": 2 for b in (1, 2, 3, 4, 5, 8, 9)},
+    "range:overflow": 15, "range:subnormal": 15, "factors:pow2": 300, "factors:general": 100,
+    "old-shift:0": 150, "old-shift:3": 150, "E:one": 4, "E:sub-tile": 10, "E:tiles": 40, "E:ragged": 100, "E:static-rounds": 6,
+    "refused:kernel": 4, "refused:epilogue": 5,
+}
+
+
+ACC_SHARES = ("kernel", "epilogue", "axpby", "rounds")
+
+
+def acc_share(cases: Sequence[AccCase], share: str) -> List[AccCase]:
+    """The cases of one share of the exact part (the GPU tests run one share each): "rounds" -- E = 20 004 and the
+    second-tile sizes -- else by the predicted route, the refused cases with "axpby"."""
+    def of(ac: AccCase) -> str:
+        if ac.case.E > HOST_REF_MAX_E or ac.case.eclass == "second-tile":
+            return "rounds"
+        route = predicted_route(ac)
+        return route if route in ("kernel", "epilogue") else "axpby"
+    return [ac for ac in cases if of(ac) == share]
+
+
+def acc_share_minimums(cases: Sequence[AccCase], share: str) -> Dict[str, int]:
+    """What the share must deliver of :data:`ACC_MINIMUMS` when every other share delivers what the host predicts."""
+    total, mine = acc_coverage(cases), acc_coverage(acc_share(cases, share))
+    need = {k: v - (total[k] - mine[k]) for k, v in ACC_MINIMUMS.items()}
+    return {k: v for k, v in need.items() if v > 0}
+
+
+# ---- on the device
+
+_ACC_GEOMETRY: Dict[Tuple[str, int], Tuple[int, int]] = {}
+
+
+def acc_geometry(torch, fam: str, order: Tuple[int, int]) -> Tuple[int, int]:
+    """``(TEL, E2)`` of an accumulating kernel at one order, from what the launcher reports (as ``geometry()`` of
+    tests/test_gpu_accumulate.py): the wave tile TEL = E / tiles at an E that every wave tile divides, and E2 = waves x
+    TEL + TEL + 5, at which some wave of the full grid walks a second tile."""
+    if (fam, order[0]) not in _ACC_GEOMETRY:
+        kind, route = ("fm", "kernel") if fam == "fm" else (fam, "epilogue")
+        E = 4800     # 2^6 3 5^2: a multiple of the wave tiles (16, 32, 48, 80 elements)
+        ac = AccCase(_c(kind, order, 2, "rij", "float64", E, 1), 1.0, 1.0, route)
+        expr, _ = ac.case.stages()[0]
+        dev = {nm: torch.zeros(_shape(expr, nm, E), dtype=torch.float64, device="cuda") for nm in expr.all_args}
+        outs = {n: torch.zeros(tuple(E if isinstance(d, f.SizeParam) else int(d) for d in expr.shape), dtype=torch.float64,
+                               device="cuda") for n in expr.output_names}
+        assert acc_launch(ac, dev, outs) == route
+        tel = E // _hip.last_launch_info()["tiles"]
+        assert tel % 16 == 0 and E % tel == 0, (fam, order, tel)
+        waves = 2 * torch.cuda.get_device_properties(0).multi_processor_count * 4   # two blocks of four waves per CU
+        E2 = waves * tel + tel + 5
+        assert E2 <= 2 * 10 ** 5
+        _ACC_GEOMETRY[fam, order[0]] = (tel, E2)
+    return _ACC_GEOMETRY[fam, order[0]]
+
+
+def acc_resolve(torch, ac: AccCase) -> AccCase:
+    """The case with its named size replaced by the element count (the class keeps the name)."""
+    if ac.case.E >= 0:
+        return ac
+    tel, E2 = acc_geometry(torch, ac.family(), (ac.case.Np, ac.case.Nfp))
+    E = {"tel-1": tel - 1, "tel": tel, "tel+1": tel + 1, "2tel+3": 2 * tel + 3, "second-tile": E2}[ac.case.eclass]
+    return AccCase(DGCase(**{**asdict(ac.case), "E": E}), ac.alpha, ac.beta, ac.route, ac.transform, ac.old_shift)
+
+
+def acc_launch(ac: AccCase, dev, outs) -> Optional[str]:
+    """Bind (``measure._bind``, as tests/test_gpu_accumulate.py does) and launch onto *outs*, which hold the old
+    values; returns ``bound.accumulate``."""
+    from feinsum_amd.measure import _bind
+
+    expr, keys = ac.case.stages()[0]
+    q, bound, _ = _bind(expr, 0, {nm: dev[k] for nm, k in keys.items()}, outs, acc_transform(ac), alpha=ac.alpha, beta=ac.beta)
+    bound.launch(q.stream_ptr)
+    q.finish()
+    return bound.accumulate
+
+
+def _plain_accepted(torch, case: DGCase, dev, tr: str, cache: Dict[str, bool]) -> bool:
+    """Whether the non-accumulating launch of the case under the forward transform is accepted on the device."""
+    if tr not in cache:
+        _, out_dicts = _out_buffers(torch, case)
+        try:
+            launch(torch, case, dev, {"prepared": True} if tr == "prepared" else tr, out_dicts)
+            cache[tr] = True
+        except NotImplementedError:
+            cache[tr] = False
+    return cache[tr]
+
+
+def acc_run(torch, st: Stats, ac: AccCase, dev, olds, label: str, plain_ok: Dict[str, bool], guarded: bool = True):
+    """One accumulating launch onto copies of *olds* (device tensors by output name) between guard bands.  Returns the
+    outputs by name, or ``None`` where the launch was refused -- as the host predicted, with every output buffer bitwise
+    unchanged (counted), or because the plain launch of the same forward transform is refused too (counted); any other
+    refusal, a route other than the predicted one and a write outside an output are failures."""
+    expr, _ = ac.case.stages()[0]
+    want_route = predicted_route(ac)
+    bufs, outs = [], {}
+    for name in expr.output_names:
+        buf, out, n = _guarded(torch, tuple(olds[name].shape), olds[name].dtype)
+        out.copy_(olds[name])
+        bufs.append((buf, n))
+        outs[name] = out
+    before = [buf.clone() for buf, _ in bufs]
+    try:
+        route = acc_launch(ac, dev, outs)
+    except NotImplementedError as exc:
+        torch.cuda.synchronize()
+        same = all(torch.equal(buf.view(torch.int8), b.view(torch.int8)) for (buf, _), b in zip(bufs, before))
+        if not same:
+            st.fail(f"{label}: refused ({exc}) after writing to an output  REPRO {ac.repro()}")
+        elif want_route is None:
+            st.cov.update(acc_buckets(ac))
+        elif not _plain_accepted(torch, ac.case, dev, ac.transform, plain_ok):
+            st.cov["not-accepted:" + ac.transform] += 1
+        else:
+            st.cov["refused:unpredicted"] += 1
+            st.fail(f"{label}: refused ({exc}), but the host predicts the route {want_route!r}  REPRO {ac.repro()}")
+        return None
+    if want_route is None or route != want_route:
+        st.fail(f"{label}: took the route {route!r}, the host predicts {want_route!r}  REPRO {ac.repro()}")
+        return None
+    if not all(_guards_intact(buf, n) for buf, n in bufs):
+        st.fail(f"{label}: wrote outside its output  REPRO {ac.repro()}")
+        return None
+    return outs
+
+
+def _acc_label(part: str, ac: AccCase) -> str:
+    c = ac.case
+    return f"accumulate {part} {ac.route}/{ac.transform} ({ac.alpha:g}, {ac.beta:g}): {c.kind} Np={c.Np} b={c.b} {c.op}" \
+           f" {c.dtype} E={c.E} {c.scale}"
+
+
+def _sample_index(case: DGCase, expr, shape: Tuple[int, ...]) -> np.ndarray:
+    """Flat indices of the entries a general pair is checked on: everything up to ACC_WHOLE_E elements, else the
+    first and the last ACC_EDGE elements and ACC_SAMPLE seeded entries."""
+    n = int(np.prod(shape, dtype=np.int64))
+    if case.E <= ACC_WHOLE_E:
+        return np.arange(n, dtype=np.int64)
+    ax = _e_axis(expr, None)
+    e = np.arange(n, dtype=np.int64).reshape(shape)
+    edge = np.concatenate([np.take(e, range(ACC_EDGE), axis=ax).reshape(-1),
+                           np.take(e, range(case.E - ACC_EDGE, case.E), axis=ax).reshape(-1)])
+    rnd = np.random.default_rng(case.seed + 17).integers(0, n, size=ACC_SAMPLE)
+    return np.unique(np.concatenate([edge, rnd]))
+
+
+def acc_general_reference(ac: AccCase, ms: np.ndarray, t: int, old: np.ndarray) -> np.ndarray:
+    """:func:`combine_entry` on flat arrays of mantissas of the sum and of old values."""
+    alpha, beta = ac.factors()
+    dt = ac.out_dtype()
+    return np.array([combine_entry(int(m), t, alpha, beta, float(o), dt) for m, o in zip(ms, old)], dtype=dt)
+
+
+def _acc_data(torch, case: DGCase, st: Stats):
+    """Exact data with ACC_HEADROOM: ``(dev, refs of the plain einsum by output, integer sums by output or None, t, sig)``."""
+    if case.E > 50_000:
+        dev, scales, sig = device_data(torch, case, ACC_HEADROOM)
+        refs = _device_refs(torch, case, dev, scales, sig, st)[0]
+        mants = None
+    else:
+        arrays, mants, scales, sig = host_data(case, headroom=ACC_HEADROOM)
+        dev = {k: torch.from_numpy(np.ascontiguousarray(a)).cuda() for k, a in arrays.items()}
+        refs = references(torch, case, arrays, mants, scales, sig, dev, st)[0]
+    expr, keys = case.stages()[0]
+    t = sum(scales[keys[a.name]] for a in expr.args[0])
+    sums = None
+    if mants is not None and case.E <= HOST_REF_MAX_E:
+        sums = {name: np.asarray(np.einsum(expr.get_subscripts(), *[mants[keys[a.name]] for a in row], optimize=True),
+                                 dtype=np.int64) for name, row in zip(expr.output_names, expr.args)}
+    return dev, refs, sums, t, sig
+
+
+def acc_check_exact(torch, st: Stats, ac: AccCase, label: str, outs, refs, sums, t: int, olds_host) -> None:
+    """Power-of-two pairs: the whole array, bitwise.  General pairs: the correctly rounded reference on
+    :func:`_sample_index`, bitwise."""
+    expr, _ = ac.case.stages()[0]
+    alpha, beta = ac.factors()
+    dt = ac.out_dtype()
+    for k, name in enumerate(expr.output_names):
+        mo, old = olds_host[k]
+        got = outs[name]
+        st.exact_runs += 1
+        if ac.pow2():
+            if sums is not None:
+                want = torch.from_numpy(combine_pow2(sums[name], t, alpha, beta, mo, t + ac.old_shift, dt)).cuda()
+            else:   # (large E, normal range: every term exact in float64 by the bit budget)
+                assert ac.case.scale == "normal"
+                want = (alpha * refs[name].double() + beta * torch.from_numpy(old).cuda().double()).to(got.dtype)
+            bad = ref_.differing_entries(got, want)
+        else:
+            idx = _sample_index(ac.case, expr, tuple(got.shape))
+            tidx = torch.from_numpy(idx).cuda()
+            if sums is not None:
+                ms = sums[name].reshape(-1)[idx]
+            else:
+                ms = np.ldexp(refs[name].reshape(-1)[tidx].double().cpu().numpy(), -t).astype(np.int64)
+            want = acc_general_reference(ac, ms, t, old.reshape(-1)[idx])
+            bad = ref_.differing_entries(got.reshape(-1)[tidx].cpu().numpy(), want)
+            st.cov["checked:sampled" if ac.case.E > ACC_WHOLE_E else "checked:whole"] += 1
+        if bad:
+            st.fail(f"{label}: output {name}: {bad} entries differ from fl(alpha E + fl(beta old))  REPRO {ac.repro()}")
+        else:
+            st.exact_equal += 1
+
+
+def _groups(cases: Sequence[AccCase]) -> List[List[AccCase]]:
+    out: List[List[AccCase]] = []
+    for ac in cases:
+        if out and out[-1][0].case == ac.case:
+            out[-1].append(ac)
+        else:
+            out.append([ac])
+    return out
+
+
+def _acc_exact_group(torch, st: Stats, group: Sequence[AccCase]) -> None:
+    group = [acc_resolve(torch, ac) for ac in group]
+    case = group[0].case
+    dev, refs, sums, t, sig = _acc_data(torch, case, st)
+    dt = group[0].out_dtype()
+    olds_host = {sh: acc_old(case, sig, t, sh, dt) for sh in sorted({ac.old_shift for ac in group})}
+    expr, _ = case.stages()[0]
+    plain_ok: Dict[str, bool] = {}
+    for ac in group:
+        label = _acc_label("exact", ac)
+        olds = {name: torch.from_numpy(olds_host[ac.old_shift][k][1]).cuda() for k, name in enumerate(expr.output_names)}
+        outs = acc_run(torch, st, ac, dev, olds, label, plain_ok)
+        if outs is None:
+            continue
+        st.cov.update(acc_buckets(ac))
+        acc_check_exact(torch, st, ac, label, outs, refs, sums, t, olds_host[ac.old_shift])
+
+
+def run_accumulate_exact(seed: int, cases: Optional[Sequence[AccCase]] = None) -> Stats:
+    """The exact part of the accumulating pass: :func:`acc_cases`, every output bit fixed by the contract."""
+    import torch
+
+    st = Stats(f"dg accumulate exact seed={seed}")
+    st.cov["refused:unpredicted"] += 0
+    for group in _groups(acc_cases(seed) if cases is None else cases):
+        _acc_exact_group(torch, st, group)
+    return st
+
+
+# ---- signed data
+
+def acc_bounded_cases(seed: int) -> List[AccCase]:
+    """The accepted cases of :func:`acc_cases` in the normal range, E at most 1100 (named sizes included), every other
+    pair of each case."""
+    keep = [ac for ac in acc_cases(seed) if ac.case.scale == "normal" and ac.case.E <= 1100
+            and ac.case.eclass != "second-tile" and predicted_route(ac) is not None]
+    return keep[::2]
+
+
+def run_accumulate_bounded(seed: int, cases: Optional[Sequence[AccCase]] = None) -> Stats:
+    """Signed uniform operands and normal old outputs: within ``gamma(K + 2, u) (|alpha| absref + |beta| |old|)`` of the
+    long-double value, K the family's bound terms (the bound tests/test_gpu_accumulate_epilogue.py derives); every float64
+    result bitwise the "axpby" route of the same case; for power-of-two pairs bitwise torch's ``alpha plain + beta old``."""
+    import torch
+
+    st = Stats(f"dg accumulate bounded seed={seed}")
+    st.cov["refused:unpredicted"] += 0
+    for group in _groups(acc_bounded_cases(seed) if cases is None else cases):
+        group = [acc_resolve(torch, ac) for ac in group]
+        case = group[0].case
+        expr, keys = case.stages()[0]
+        nrng = np.random.default_rng(case.seed)
+        host = {k: (nrng.random(_shape(expr, nm, case.E)) * 2 - 1).astype(expr.arg_to_dtype[nm]) for nm, k in sorted(keys.items())}
+        dev = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
+        dt = group[0].out_dtype()
+        shape = tuple(case.E if isinstance(d, f.SizeParam) else int(d) for d in expr.shape)
+        old_host = {name: nrng.standard_normal(shape).astype(dt) for name in expr.output_names}
+        olds = {name: torch.from_numpy(v).cuda() for name, v in old_host.items()}
+        nb = ref_.bound_terms(expr.get_subscripts(), _extent(expr, case.E), 3)
+        bounds = {name: ref_.bounded_reference(expr.get_subscripts(), [host[keys[a.name]] for a in row])
+                  for name, row in zip(expr.output_names, expr.args)}
+        u = ref_.U32 if case.dtype == "float32" else ref_.U64
+        plain_ok: Dict[str, bool] = {}
+        plains: Dict[str, Any] = {}
+        for ac in group:
+            label = _acc_label("bounded", ac)
+            outs = acc_run(torch, st, ac, dev, olds, label, plain_ok)
+            if outs is None:
+                continue
+            bk = acc_buckets(ac)
+            st.cov.update(bk)
+            alpha, beta = ac.factors()
+            for name in expr.output_names:
+                r, ar = bounds[name]
+                o = old_host[name].astype(np.longdouble)
+                want = np.longdouble(alpha) * r + np.longdouble(beta) * o
+                absw = abs(np.longdouble(alpha)) * ar + abs(np.longdouble(beta)) * np.abs(o)
+                ratio = ref_.bound_ratio(outs[name].cpu().numpy(), want, absw, nb + 2, u)
+                for b_ in bk:
+                    st.worst[b_] = max(st.worst.get(b_, 0.0), ratio)
+                if ratio > 1:
+                    st.fail(f"{label}: output {name}: |got - ref| = {ratio:.3g} x the bound  REPRO {ac.repro()}")
+            route = predicted_route(ac)
+            if case.dtype == "float64" and route != "axpby":
+                other = AccCase(case, ac.alpha, ac.beta, "axpby", ac.transform, ac.old_shift)
+                fb = acc_run(torch, st, other, dev, olds, label + " (axpby)", plain_ok)
+                if fb is not None:
+                    st.exact_runs += 1
+                    bad = sum(int((outs[n].view(torch.int64) != fb[n].view(torch.int64)).sum()) for n in expr.output_names)
+                    if bad:
+                        st.fail(f"{label}: {bad} entries differ bitwise from the \"axpby\" route  REPRO {ac.repro()}")
+                    else:
+                        st.exact_equal += 1
+                        st.cov["equal:axpby-route"] += 1
+            if ac.pow2() and _plain_accepted(torch, case, dev, ac.transform, plain_ok):
+                if ac.transform not in plains:
+                    _, pod = _out_buffers(torch, case)
+                    launch(torch, case, dev, {"prepared": True} if ac.transform == "prepared" else ac.transform, pod)
+                    plains[ac.transform] = pod[0]
+                st.exact_runs += 1
+                bad = 0
+                for n in expr.output_names:
+                    two_pass = alpha * plains[ac.transform][n] + beta * olds[n] if beta != 0 else alpha * plains[ac.transform][n]
+                    bad += ref_.differing_entries(outs[n], two_pass)
+                if bad:
+                    st.fail(f"{label}: {bad} entries differ from torch's alpha plain + beta old  REPRO {ac.repro()}")
+                else:
+                    st.exact_equal += 1
+                    st.cov["equal:torch-two-pass"] += 1
+    return st
+
+
+# ---- non-finite values
+
+ACC_PLANT_ROLES = ("field", "geometry", "operator", "old")
+ACC_PLANT_VALUES = (math.nan, math.inf, -math.inf)
+
+
+def acc_plants(seed: int) -> List[Tuple[AccCase, str, float]]:
+    """``(case, role, value)``: every role x value with beta = 0 and with beta != 0, and with alpha = 0, on the three
+    accumulating kernels (the sizes behind a tile, below one and of several tiles) and on the "axpby" route."""
+    rng = random.Random(seed + 43)
+    S = lambda: rng.randrange(1 << 30)   # noqa: E731
+    o1, o2, o3, o4 = TET_ORDERS
+    bases = [(_c("fm:fe:ifj", o4, 4, "rij", "float64", 163, S()), "kernel"), (_c("grad", o3, 1, "rij", "float64", 99, S()), "epilogue"),
+             (_c("div", o4, 1, "rji", "float64", 163, S()), "epilogue"), (_c("fm", o2, 5, "rij", "float64", 7, S()), "kernel"),
+             (_c("grad", o1, 1, "rji", "float64", 35, S()), "epilogue"), (_c("div", o2, 1, "rij", "float64", 7, S()), "epilogue"),
+             (_c("grad", o4, 1, "rij", "float64", 163, S()), "axpby"), (_c("fm", o3, 2, "rij", "float32", 65, S()), "axpby"),
+             (_c("divcomp", o3, 1, "rij", "float64", 33, S()), None)]
+    reads, blind = ((1.0, 1.0), (0.0, 1.0), (2.0, -0.5), (0.3, -1.7)), ((0.5, 0.0), (0.0, 0.0))
+    out = []
+    k = 0
+    for case, route in bases:
+        for role in ACC_PLANT_ROLES:
+            for value in ACC_PLANT_VALUES:
+                for alpha, beta in (reads[k % 4], blind[k % 2]):
+                    out.append((AccCase(case, alpha, beta, route), role, value))
+                k += 1
+    return out
+
+
+def acc_plant_buckets(ac: AccCase, role: str, value: float) -> List[str]:
+    return [f"planted:{role}:{value}:" + ("beta=0" if ac.beta == 0 else "beta!=0"), f"planted-route:{predicted_route(ac)}",
+            f"planted:{role}:alpha=0" if ac.alpha == 0 else f"planted:{role}:alpha!=0"]
+
+
+ACC_PLANT_MINIMUMS = {**{f"planted:{r}:{v}:{b}": 2 for r in ACC_PLANT_ROLES for v in ACC_PLANT_VALUES for b in ("beta=0", "beta!=0")},
+                      **{f"planted:{r}:alpha=0": 4 for r in ACC_PLANT_ROLES},
+                      "planted-route:kernel": 40, "planted-route:epilogue": 80, "planted-route:axpby": 60}
+
+
+def _plant_site(case: DGCase, role: str, rng: random.Random):
+    """``(key, index)`` of a planted input entry of the first row; for "old" the output name and an index."""
+    expr, keys = case.stages()[0]
+    row = expr.args[rng.randrange(len(expr.args))]
+    elems = sorted({0, min(case.E - 1, 15), case.E // 2, case.E - 1})
+    if role == "old":
+        shape = [case.E if isinstance(d, f.SizeParam) else int(d) for d in expr.shape]
+        idx = [rng.randrange(s) for s in shape]
+        idx[_e_axis(expr, None)] = rng.choice(elems)
+        return expr.output_names[expr.args.index(row)], tuple(idx)
+    for a in row:
+        ax = _e_axis(expr, a.name)
+        r = "operator" if ax is None else ("field" if a is row[-1] else "geometry")
+        if r == role:
+            idx = [rng.randrange(s) for s in _shape(expr, a.name, case.E)]
+            if ax is not None:
+                idx[ax] = rng.choice(elems)
+            return keys[a.name], tuple(idx)
+    return None
+
+
+def acc_check_plant(ac: AccCase, role: str, value: float, got, clean, dep) -> int:
+    """Violations of the rule of a planted value: exactly *dep* is non-finite -- NaN for a planted NaN, and NaN for any
+    value planted in an input when alpha is 0 (``0 * Inf`` is NaN: all three routes multiply) -- and every other entry
+    is bitwise the clean accumulating launch."""
+    return ref_.nonfinite_violations(got, clean, dep, math.nan if ac.alpha == 0 and role != "old" else value)
+
+
+def run_accumulate_nonfinite(seed: int, plants: Optional[Sequence[Tuple[AccCase, str, float]]] = None) -> Stats:
+    """One NaN / +Inf / -Inf in a field, a geometry factor, an operator entry or an old output of an accumulating launch.
+    beta != 0: exactly the dependency set of the einsum is non-finite (a plant in an old output: that single entry), the
+    rest bitwise the clean accumulating launch.  beta = 0: the old outputs are all NaN / +-Inf poison and do not show.
+    alpha = 0: a non-finite E_k still gives NaN, on every route (the contract)."""
+    import torch
+
+    st = Stats(f"dg accumulate nonfinite seed={seed}")
+    st.cov["refused:unpredicted"] += 0
+    rng = random.Random(seed + 47)
+    todo = acc_plants(seed) if plants is None else plants
+    data: Dict[DGCase, Any] = {}
+    for ac, role, value in todo:
+        case = ac.case
+        expr, keys = case.stages()[0]
+        if case not in data:
+            data.clear()
+            dev, _, _, t, sig = _acc_data(torch, case, st)
+            olds = {name: torch.from_numpy(x).cuda() for name, (_, x) in zip(expr.output_names, acc_old(case, sig, t, 0, ac.out_dtype()))}
+            data[case] = (dev, olds, {})
+        dev, olds, plain_ok = data[case]
+        label = _acc_label(f"nonfinite {value} in {role}", ac)
+        clean = acc_run(torch, st, ac, dev, olds, label + " (clean)", plain_ok)
+        site = _plant_site(case, role, rng)
+        if clean is None or site is None:
+            continue
+        key, idx = site
+        start = {n: o.clone() for n, o in olds.items()}
+        if ac.beta == 0:      # not read: poison everywhere
+            for o in start.values():
+                o.fill_(math.nan)
+                o.view(-1)[1::2] = math.inf
+                o.view(-1)[2::4] = -math.inf
+        if role == "old":
+            start[key][idx] = value
+            deps = {n: torch.zeros_like(o, dtype=torch.bool) for n, o in olds.items()}
+            if ac.beta != 0:
+                deps[key][idx] = True
+            got = acc_run(torch, st, ac, dev, start, label, plain_ok)
+        else:
+            keep = dev[key][idx].clone()
+            dev[key][idx] = value
+            deps = _dependency(torch, case, key, idx)[0]
+            got = acc_run(torch, st, ac, dev, start, label, plain_ok)
+            dev[key][idx] = keep
+        if got is None:
+            continue
+        st.cov.update(acc_plant_buckets(ac, role, value))
+        st.exact_runs += 1
+        bad = sum(acc_check_plant(ac, role, value, got[n], clean[n], deps[n]) for n in expr.output_names)
+        if bad:
+            st.fail(f"{label}: {bad} entries break the dependency rule at {key}{list(idx)}  REPRO {ac.repro()}")
+        else:
+            st.exact_equal += 1
+    return st
+
+
+# ---- placement
+
+ACC_PLACE_E = 163     # 2 x 80 + 3: full tiles and a remainder at every order
+
+
+def acc_placement_runs(seed: int, part: str) -> List[List[PlacedRun]]:
+    """Accumulating runs of the placement pass, one list per (case, factors), "aligned" in front.  The full set of
+    PLACEMENTS under "kernel" (face-mass) and "epilogue" (grad, div) at every order p = 1..4, E = 163 (full tiles and a
+    remainder) and, at two orders each, E = 17 (below one tile); "aligned" and "all" under "axpby".  *part* "exact":
+    power-of-two pairs with beta != 0, bitwise the reference; "signed": a general pair, bitwise the aligned launch."""
+    rng = random.Random(seed + 53)
+    S = lambda: rng.randrange(1 << 30)   # noqa: E731
+    data = "signed" if part == "signed" else "exact"
+    pow2 = [p for p in ACC_PAIRS if is_pow2(p[0]) and is_pow2(p[1]) and p[1] != 0 and p[0] != 0] + [(0.5, 0.0)]
+    out = []
+    k = 0
+
+    def add(case, route, transform, full):
+        nonlocal k
+        alpha, beta = ACC_GENERAL[k % 2] if part == "signed" else pow2[k % len(pow2)]
+        k += 1
+        acc = (alpha, beta, route, k % 2 * 3)
+        out.append([PlacedRun(case, data, transform, name, shifts, (), acc) for name, shifts in placements_of(case, full)])
+
+    for pi, order in enumerate(TET_ORDERS):
+        for E in (ACC_PLACE_E, 17) if pi % 2 else (ACC_PLACE_E,):
+            add(_c(ACC_FM_KINDS[(3 * pi + E) % 8], order, (3, 2, 4, 5)[pi], "rij", "float64", E, S()), "kernel", "auto", True)
+            add(_c("grad", order, 1, ("rij", "rji")[pi % 2], "float64", E, S()), "epilogue", "mfma" if pi == 2 else "auto", True)
+            add(_c("div", order, 1, ("rji", "rij")[pi % 2], "float64", E, S()), "epilogue", "auto", True)
+    o1, o2, o3, o4, o5, t7, t13 = ORDERS3
+    for case, t in ((_c("grad", o4, 1, "rij", "float64", 65, S()), "auto"), (_c("fm", o3, 9, "rij", "float64", 65, S()), "auto"),
+                    (_c("fm", o2, 2, "rij", "float32", 64, S()), "auto"), (_c("divcomp", o3, 1, "rij", "float64", 17, S()), "tiled"),
+                    (_c("mass", o5, 2, "ij", "float64", 65, S()), "auto"), (_c("grad", o3, 1, "rij", "mixed", 64, S()), "auto"),
+                    (_c("div", o2, 1, "rij", "float32", 1003, S()), "auto")):
+        add(case, "axpby", t, False)
+    return out
+
+
+def acc_placement_buckets(run: PlacedRun) -> List[str]:
+    route = run.acc[2]
+    ac = _acc_of(run)
+    b = ["place:" + run.placement, f"accplace-route:{predicted_route(ac)}", f"dtype:{run.case.dtype}"]
+    fam = ac.family()
+    if route in ("kernel", "epilogue") and run.placement in ("only:field", "only:output") and run.case.E >= ACC_PLACE_E:
+        b.append(f"accplace:{fam}:p{TET_ORDERS.index((run.case.Np, run.case.Nfp)) + 1}:{run.placement}")
+    return b
+
+
+def _acc_of(run: PlacedRun) -> AccCase:
+    alpha, beta, route, old_shift = run.acc
+    return AccCase(run.case, float(alpha), float(beta), route, run.transform, int(old_shift))
+
+
+def acc_placement_coverage(seed: int, part: str) -> Counter:
+    cnt: Counter = Counter()
+    for runs in acc_placement_runs(seed, part):
+        for run in runs:
+            cnt.update(acc_placement_buckets(run))
+    return cnt
+
+
+#: minimum runs per bucket of the accumulating placement runs, either part: ``only:field`` (the output aligned) and
+#: ``only:output`` (the fields aligned) for face-mass, grad and div at every order, by name
+ACC_PLACEMENT_MINIMUMS = {
+    **{f"accplace:{fam}:p{p}:{pl}": 1 for fam in ("fm", "grad", "div") for p in (1, 2, 3, 4) for pl in ("only:field", "only:output")},
+    **{"place:" + p: 18 for p in PLACEMENTS if "last" not in p}, "place:only:last-field": 6, "place:only:last-output": 6,
+    "place:aligned": 25, "place:all": 25, "accplace-route:kernel": 50, "accplace-route:epilogue": 80, "accplace-route:axpby": 14,
+}
+
+
+def _acc_placed_case(torch, st: Stats, runs: Sequence[PlacedRun]) -> None:
+    """All runs of one accumulating case: inputs embedded between NaN bands once per shift, outputs between sentinel
+    bands holding the old values; exact data bitwise the reference, signed float64 data bitwise the aligned launch."""
+    ac = _acc_of(runs[0])
+    case, data = ac.case, runs[0].data
+    expr, keys = case.stages()[0]
+    dt = ac.out_dtype()
+    refs = None
+    if data == "exact":
+        assert ac.pow2() and case.E <= HOST_REF_MAX_E
+        dev, _, sums, t, sig = _acc_data(torch, case, st)
+        old_host = acc_old(case, sig, t, ac.old_shift, dt)
+        alpha, beta = ac.factors()
+        refs = [{name: torch.from_numpy(combine_pow2(sums[name], t, alpha, beta, old_host[k][0], t + ac.old_shift, dt)).cuda()
+                 for k, name in enumerate(expr.output_names)}]
+        olds = {name: torch.from_numpy(old_host[k][1]).cuda() for k, name in enumerate(expr.output_names)}
+    else:
+        nrng = np.random.default_rng(case.seed)
+        dev = {k: torch.from_numpy((nrng.random(_shape(expr, nm, case.E)) * 2 - 1).astype(expr.arg_to_dtype[nm])).cuda()
+               for nm, k in sorted(keys.items())}
+        shape = tuple(case.E if isinstance(d, f.SizeParam) else int(d) for d in expr.shape)
+        olds = {name: torch.from_numpy(nrng.standard_normal(shape).astype(dt)).cuda() for name in expr.output_names}
+    ins_slots, out_slots = slots_of(case)
+    cache: Dict[Tuple[str, int], Tuple[Embedded, Any]] = {}
+    aligned = None
+    want_route = predicted_route(ac)
+    for run in runs:
+        shifts = dict(run.shifts)
+        ins = {}
+        for key, _, idt, shape in ins_slots:
+            at = (key, shifts.get(key, 0))
+            if at not in cache:
+                emb = embed(torch, shape, getattr(torch, idt.name), at[1], "in", dev[key])
+                cache[at] = (emb, emb.snapshot())
+            ins[key] = cache[at]
+        outs: Dict[str, Embedded] = {}
+        for slot, _, name, odt, shape in out_slots:
+            outs[name] = embed(torch, shape, getattr(torch, odt.name), shifts.get(slot, 0), "out")
+            outs[name].view.copy_(olds[name])
+        label = f"placement {run.placement} {data} " + _acc_label("", ac)
+        try:
+            route = acc_launch(ac, {k: e.view for k, (e, _) in ins.items()}, {n: e.view for n, e in outs.items()})
+        except (NotImplementedError, f.InvalidParameterError) as exc:
+            st.cov["refused:unpredicted"] += 1
+            st.fail(f"{label}: refused ({exc})  REPRO {run.repro()}")
+            continue
+        if route != want_route:
+            st.fail(f"{label}: took the route {route!r}, the host predicts {want_route!r}  REPRO {run.repro()}")
+            continue
+        st.cov.update(acc_placement_buckets(run))
+        check_inputs(st, label, run, ins)
+        base = aligned if (data == "signed" and case.dtype == "float64" and run.placement != "aligned") else None
+        check_outputs(st, label, run, [outs], refs, base)
+        if run.placement == "aligned":
+            aligned = [{n: _int_copy(torch, e) for n, e in outs.items()}]
+
+
+def run_accumulate_placement(seed: int, part: str = "all") -> Stats:
+    """The accumulating runs of the placement pass: *part* "exact", "signed" or "all"."""
+    import torch
+
+    st = Stats(f"dg accumulate placement {part} seed={seed}")
+    st.cov["leak:nan-entries"] += 0
+    st.cov["refused:unpredicted"] += 0
+    for p in ("exact", "signed") if part == "all" else (part,):
+        for runs in acc_placement_runs(seed, p):
+            _acc_placed_case(torch, st, runs)
+    return st
+
+
+def run_accumulate(seed: int) -> List[Stats]:
+    return [run_accumulate_exact(seed), run_accumulate_bounded(seed), run_accumulate_nonfinite(seed),
+            run_accumulate_placement(seed)]
+
+
+def repro_accumulate(text: str) -> Stats:
+    """Replay one ``REPRO`` line of the accumulating pass on exact and on signed data (a placement line: its aligned
+    launch first)."""
+    import torch
+
+    d = json.loads(text)
+    if "placement" in d:
+        run = PlacedRun.from_repro(text)
+        st = Stats("repro")
+        st.cov["leak:nan-entries"] += 0
+        first = [PlacedRun(run.case, run.data, run.transform, "aligned", (), run.knobs, run.acc)] if run.placement != "aligned" else []
+        _acc_placed_case(torch, st, first + [run])
+        return st
+    ac = AccCase.from_repro(text)
+    st = run_accumulate_exact(0, [ac])
+    if ac.case.scale == "normal" and predicted_route(ac) is not None:
+        st2 = run_accumulate_bounded(0, [ac])
+        st.failures += st2.failures
+        st.exact_runs += st2.exact_runs
+        st.exact_equal += st2.exact_equal
+        st.cov.update(st2.cov)
+    return st
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--placement":
         st = run_placement(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+        print(st.report())
+        sys.exit(1 if st.failures else 0)
+    if len(sys.argv) > 1 and sys.argv[1] == "--accumulate":
+        results = run_accumulate(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+        for s in results:
+            print(s.report())
+        sys.exit(1 if sum(s.failures for s in results) else 0)
+    if len(sys.argv) > 2 and sys.argv[1] == "--repro" and "accumulate" in json.loads(sys.argv[2]):
+        st = repro_accumulate(sys.argv[2])
         print(st.report())
         sys.exit(1 if st.failures else 0)
     if len(sys.argv) > 2 and sys.argv[1] == "--repro" and "placement" in json.loads(sys.argv[2]):
