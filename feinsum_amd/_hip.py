@@ -26,26 +26,8 @@ VARIANT_AUTO, VARIANT_GENERIC, VARIANT_MFMA, VARIANT_TILED, VARIANT_MFMA_SPLIT =
 VARIANTS = {"auto": VARIANT_AUTO, "generic": VARIANT_GENERIC, "mfma": VARIANT_MFMA, "tiled": VARIANT_TILED,
             "mfma_split": VARIANT_MFMA_SPLIT}
 
-#: every symbol declared in include/feinsum_hip.h (checked by the CPU test-suite)
-EXPORTED_SYMBOLS = (
-    "fe_version", "fe_last_error", "fe_device_count", "fe_device_info",
-    "fe_grad3d_f64", "fe_div3d_f64", "fe_grad3d_f64_ex", "fe_div3d_f64_ex", "fe_divcomp3d_f64",
-    "fe_grad3d_batched_f64", "fe_div3d_batched_f64", "fe_gradplanes3d_f64", "fe_matapply_f64",
-    "fe_grad_f64", "fe_div_f64",
-    "fe_graddiv3d_f64", "fe_waveop3d_f64",
-    "fe_facemass_f64",
-    "fe_flops_per_element", "fe_time_launches", "fe_einsum_generic", "fe_einsum_contract", "fe_einsum_contract_groups", "fe_einsum_reduce_plan", "fe_einsum_reduce",
-    "fe_kernel_resources",
-    "fe_prepare_operator", "fe_grad3d_prepared_f64", "fe_div3d_prepared_f64", "fe_facemass_prepared_f64",
-    "fe_graddiv3d_prepared_f64", "fe_waveop3d_prepared_f64", "fe_divcomp_f64", "fe_release_prepared",
-    "fe_split_alloc", "fe_split_free", "fe_split_info", "fe_split_stats", "fe_split_reserve", "fe_split_trim", "fe_launch_f32", "fe_set_tail_rounds", "fe_set_tail_min_rounds",
-    "fe_set_cu_limit", "fe_set_phase_priority_p5", "fe_set_div_interleave", "fe_set_div_quarter_tail", "fe_set_grad_quarter_tail", "fe_set_grad_staggered_start", "fe_last_launch_info", "fe_stream_retired", "fe_capture_id", "fe_graph_retired", "fe_tail_stats", "fe_tail_check", "fe_tail_plant", "fe_set_temporal_loads_mib", "fe_set_write_through_mib",
-    "fe_geomadj_f64", "fe_facemass_adj_f64", "fe_opgrad_plan", "fe_opgrad_f64", "fe_facemass_opgrad_f64",
-    "fe_facemass_acc_f64", "fe_axpby", "fe_grad3d_acc_f64", "fe_div3d_acc_f64",
-)
 FAMILY_F32 = 0x100    # FE_FAMILY_F32
-
-_c_double_p = C.c_void_p   # device pointers travel as plain integers
+FAMILY_ACC = 0x200    # FE_FAMILY_ACC
 
 
 class ArgPack(C.Structure):
@@ -61,6 +43,7 @@ class ArgPack(C.Structure):
         ("j3", C.POINTER(C.c_void_p)),
         ("ndim", C.c_int32),
         ("prepared", C.c_void_p),
+        ("alpha", C.c_double), ("beta", C.c_double),
     ]
 
 
@@ -87,6 +70,88 @@ class EinsumDesc(C.Structure):
         ("op_out_stride", (C.c_int64 * FE_MAX_EINSUM_INDICES) * FE_MAX_EINSUM_OPERANDS),
         ("op_sum_stride", (C.c_int64 * FE_MAX_EINSUM_INDICES) * FE_MAX_EINSUM_OPERANDS),
     ]
+
+
+# The C types of include/feinsum_hip.h.  Every pointer to data travels as an address (device pointers are plain integers;
+# host out-parameters go through ``byref``), every table of pointers as ``void**``.
+_int, _i32, _i64, _size, _f64, _str = C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_double, C.c_char_p
+_p, _pp = C.c_void_p, C.POINTER(C.c_void_p)
+
+#: ``name: (restype, argtypes)`` of every function declared in include/feinsum_hip.h, in its order (tests/test_abi.py
+#: parses the header and compares)
+SIGNATURES = {
+    "fe_version": (_int, []),
+    "fe_last_error": (_str, []),
+    "fe_device_count": (_int, []),
+    "fe_device_info": (_int, [_int, _str, _size, _p, _p]),
+    "fe_grad3d_f64": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _p]),
+    "fe_grad3d_f64_ex": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _p]),
+    "fe_div3d_f64_ex": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _p]),
+    "fe_divcomp3d_f64": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _p]),
+    "fe_divcomp_f64": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p]),
+    "fe_div3d_f64": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _p]),
+    "fe_grad3d_batched_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
+    "fe_div3d_batched_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
+    "fe_grad_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_div_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_gradplanes3d_f64": (_int, [_pp, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
+    "fe_matapply_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
+    "fe_graddiv3d_f64": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
+    "fe_waveop3d_f64": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_facemass_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_facemass_acc_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _p]),
+    "fe_grad3d_acc_f64": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _f64, _f64, _p]),
+    "fe_div3d_acc_f64": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _f64, _f64, _p]),
+    "fe_axpby": (_int, [_p, _p, _i64, _f64, _f64, _i32, _p]),
+    "fe_prepare_operator": (_int, [_i32, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "fe_release_prepared": (_int, [_p]),
+    "fe_grad3d_prepared_f64": (_int, [_p, _p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
+    "fe_div3d_prepared_f64": (_int, [_p, _p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
+    "fe_facemass_prepared_f64": (_int, [_p, _p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_graddiv3d_prepared_f64": (_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
+    "fe_waveop3d_prepared_f64": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32,
+                                     _i32, _p]),
+    "fe_kernel_resources": (_int, [_str, _size]),
+    "fe_split_alloc": (_int, [_pp, _size, _i32]),
+    "fe_split_free": (_int, [_p]),
+    "fe_split_info": (_int, [_p, _str, _size]),
+    "fe_split_stats": (_int, [_str, _size]),
+    "fe_split_reserve": (_int, [_size]),
+    "fe_split_trim": (_int, []),
+    "fe_flops_per_element": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "fe_launch": (_int, [_i32, C.POINTER(ArgPack), _p]),
+    "fe_launch_f32": (_int, [_i32, C.POINTER(ArgPack), _p]),
+    "fe_set_tail_rounds": (_int, [_i32]),
+    "fe_set_tail_min_rounds": (_int, [_i32]),
+    "fe_stream_retired": (_int, [_p]),
+    "fe_tail_check": (_int, [_i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "fe_capture_id": (_int, [_p, C.POINTER(C.c_uint64)]),
+    "fe_graph_retired": (_int, [C.c_uint64]),
+    "fe_tail_stats": (_int, [C.POINTER(_i64), _i32]),
+    "fe_tail_plant": (_int, [_p, C.c_uint32]),
+    "fe_set_temporal_loads_mib": (_int, [_i32]),
+    "fe_set_write_through_mib": (_int, [_i32]),
+    "fe_last_launch_info": (_int, [C.POINTER(_i64), _i32]),
+    "fe_set_div_interleave": (_i64, [_i64]),
+    "fe_set_div_quarter_tail": (_int, [_i32]),
+    "fe_set_grad_quarter_tail": (_int, [_i32]),
+    "fe_set_grad_staggered_start": (_int, [_i32]),
+    "fe_set_phase_priority_p5": (_int, [_i32]),
+    "fe_set_cu_limit": (_int, [_i32]),
+    "fe_time_launches": (_int, [_i32, C.POINTER(ArgPack), _i32, _p, C.POINTER(C.c_float)]),
+    "fe_einsum_generic": (_int, [C.POINTER(EinsumDesc), _pp, _p, _p]),
+    "fe_einsum_contract": (_int, [C.POINTER(EinsumDesc), _pp, _p, _p]),
+    "fe_einsum_contract_groups": (_int, [C.POINTER(EinsumDesc), C.POINTER(_i32), C.POINTER(_i32)]),
+    "fe_einsum_reduce_plan": (_int, [C.POINTER(EinsumDesc), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_size)]),
+    "fe_einsum_reduce": (_int, [C.POINTER(EinsumDesc), _pp, _p, _p, _size, _p]),
+    "fe_geomadj_f64": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _p]),
+    "fe_facemass_adj_f64": (_int, [_p, _p, _pp, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_opgrad_plan": (_int, [_i64, _i32, C.POINTER(_i64), C.POINTER(_size)]),
+    "fe_opgrad_f64": (_int, [_p, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _p, _size,
+                          _p]),
+    "fe_facemass_opgrad_f64": (_int, [_p, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _size, _p]),
+}
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
 def library_path() -> Path:
@@ -121,165 +186,9 @@ def load_library() -> C.CDLL:
     except OSError as exc:
         raise HipLibraryError(f"cannot load {path}: {exc}") from exc
 
-    lib.fe_version.restype = C.c_int
-    lib.fe_version.argtypes = []
-    lib.fe_last_error.restype = C.c_char_p
-    lib.fe_last_error.argtypes = []
-    lib.fe_device_count.restype = C.c_int
-    lib.fe_device_count.argtypes = []
-    lib.fe_device_info.restype = C.c_int
-    lib.fe_device_info.argtypes = [C.c_int, C.c_char_p, C.c_size_t,
-                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    for name in ("fe_grad3d_f64", "fe_div3d_f64"):
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                       C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
-    for name in ("fe_grad3d_f64_ex", "fe_div3d_f64_ex", "fe_divcomp3d_f64"):
-        fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                       C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    for name in ("fe_grad3d_batched_f64", "fe_div3d_batched_f64"):
-        fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                       C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    for name in ("fe_grad_f64", "fe_div_f64"):
-        fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                       C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_matapply_f64.restype = C.c_int
-    lib.fe_matapply_f64.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                    C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_gradplanes3d_f64.restype = C.c_int
-    lib.fe_gradplanes3d_f64.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p),
-                                        C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_int32,
-                                        C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_graddiv3d_f64.restype = C.c_int
-    lib.fe_graddiv3d_f64.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_waveop3d_f64.restype = C.c_int
-    lib.fe_waveop3d_f64.argtypes = [C.c_void_p] * 8 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                                       C.c_int64] + [C.c_int32] * 6 + [C.c_void_p]
-    lib.fe_facemass_f64.restype = C.c_int
-    lib.fe_facemass_f64.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
-                                    C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_int32,
-                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_divcomp_f64.restype = C.c_int
-    lib.fe_divcomp_f64.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_release_prepared.restype = C.c_int
-    lib.fe_release_prepared.argtypes = [C.c_void_p]
-    lib.fe_split_alloc.restype = C.c_int
-    lib.fe_split_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_int32]
-    lib.fe_split_free.restype = C.c_int
-    lib.fe_split_free.argtypes = [C.c_void_p]
-    lib.fe_split_info.restype = C.c_int
-    lib.fe_split_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    lib.fe_split_stats.restype = C.c_int
-    lib.fe_split_stats.argtypes = [C.c_char_p, C.c_size_t]
-    lib.fe_split_reserve.restype = C.c_int
-    lib.fe_split_reserve.argtypes = [C.c_size_t]
-    lib.fe_split_trim.restype = C.c_int
-    lib.fe_split_trim.argtypes = []
-    lib.fe_set_tail_rounds.restype = C.c_int
-    lib.fe_set_tail_rounds.argtypes = [C.c_int32]
-    lib.fe_set_tail_min_rounds.restype = C.c_int
-    lib.fe_set_tail_min_rounds.argtypes = [C.c_int32]
-    lib.fe_set_temporal_loads_mib.restype = C.c_int
-    lib.fe_set_temporal_loads_mib.argtypes = [C.c_int32]
-    lib.fe_set_write_through_mib.restype = C.c_int
-    lib.fe_set_write_through_mib.argtypes = [C.c_int32]
-    lib.fe_set_cu_limit.restype = C.c_int
-    lib.fe_set_cu_limit.argtypes = [C.c_int32]
-    lib.fe_last_launch_info.restype = C.c_int
-    lib.fe_last_launch_info.argtypes = [C.POINTER(C.c_int64), C.c_int32]
-    lib.fe_set_phase_priority_p5.restype = C.c_int
-    lib.fe_set_phase_priority_p5.argtypes = [C.c_int32]
-    lib.fe_set_div_quarter_tail.restype = C.c_int
-    lib.fe_set_div_quarter_tail.argtypes = [C.c_int32]
-    lib.fe_set_grad_quarter_tail.restype = C.c_int
-    lib.fe_set_grad_quarter_tail.argtypes = [C.c_int32]
-    lib.fe_set_grad_staggered_start.restype = C.c_int
-    lib.fe_set_grad_staggered_start.argtypes = [C.c_int32]
-    lib.fe_set_div_interleave.restype = C.c_int64
-    lib.fe_set_div_interleave.argtypes = [C.c_int64]
-    lib.fe_stream_retired.restype = C.c_int
-    lib.fe_stream_retired.argtypes = [C.c_void_p]
-    lib.fe_tail_plant.restype = C.c_int
-    lib.fe_tail_plant.argtypes = [C.c_void_p, C.c_uint32]
-    lib.fe_capture_id.restype = C.c_int
-    lib.fe_capture_id.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.fe_graph_retired.restype = C.c_int
-    lib.fe_graph_retired.argtypes = [C.c_uint64]
-    lib.fe_tail_stats.restype = C.c_int
-    lib.fe_tail_stats.argtypes = [C.POINTER(C.c_int64), C.c_int32]
-    lib.fe_tail_check.restype = C.c_int
-    lib.fe_tail_check.argtypes = [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                  C.POINTER(C.c_int32)]
-    lib.fe_launch_f32.restype = C.c_int
-    lib.fe_launch_f32.argtypes = [C.c_int32, C.POINTER(ArgPack), C.c_void_p]
-    lib.fe_prepare_operator.restype = C.c_int
-    lib.fe_prepare_operator.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_void_p]
-    for name in ("fe_grad3d_prepared_f64", "fe_div3d_prepared_f64"):
-        fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                       C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_facemass_prepared_f64.restype = C.c_int
-    lib.fe_facemass_prepared_f64.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
-                                             C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_int32,
-                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_graddiv3d_prepared_f64.restype = C.c_int
-    lib.fe_graddiv3d_prepared_f64.argtypes = [C.c_void_p] * 7 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
-    lib.fe_waveop3d_prepared_f64.restype = C.c_int
-    lib.fe_waveop3d_prepared_f64.argtypes = ([C.c_void_p] * 10 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64]
-                                             + [C.c_int32] * 6 + [C.c_void_p])
-    lib.fe_kernel_resources.restype = C.c_int
-    lib.fe_kernel_resources.argtypes = [C.c_char_p, C.c_size_t]
-    lib.fe_flops_per_element.restype = C.c_int64
-    lib.fe_flops_per_element.argtypes = [C.c_int32] * 5
-    lib.fe_time_launches.restype = C.c_int
-    lib.fe_time_launches.argtypes = [C.c_int32, C.POINTER(ArgPack), C.c_int32, C.c_void_p,
-                                     C.POINTER(C.c_float)]
-    lib.fe_einsum_generic.restype = C.c_int
-    lib.fe_einsum_generic.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_void_p), C.c_void_p,
-                                      C.c_void_p]
-    lib.fe_einsum_contract.restype = C.c_int
-    lib.fe_einsum_contract.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_void_p), C.c_void_p,
-                                       C.c_void_p]
-    lib.fe_einsum_contract_groups.restype = C.c_int
-    lib.fe_einsum_contract_groups.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.fe_einsum_reduce_plan.restype = C.c_int
-    lib.fe_einsum_reduce_plan.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
-                                          C.POINTER(C.c_size_t)]
-    lib.fe_einsum_reduce.restype = C.c_int
-    lib.fe_einsum_reduce.argtypes = [C.POINTER(EinsumDesc), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_size_t,
-                                     C.c_void_p]
-    lib.fe_geomadj_f64.restype = C.c_int
-    lib.fe_geomadj_f64.argtypes = [C.c_void_p] * 4 + [C.c_int64] + [C.c_int32] * 4 + [C.c_int64] * 3 + [C.c_void_p]
-    lib.fe_facemass_adj_f64.restype = C.c_int
-    lib.fe_facemass_adj_f64.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                        C.POINTER(C.c_void_p), C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p]
-    lib.fe_opgrad_plan.restype = C.c_int
-    lib.fe_opgrad_plan.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
-    lib.fe_opgrad_f64.restype = C.c_int
-    lib.fe_opgrad_f64.argtypes = ([C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64]
-                                  + [C.c_int32] * 4 + [C.c_int64] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p])
-    lib.fe_facemass_opgrad_f64.restype = C.c_int
-    lib.fe_facemass_opgrad_f64.argtypes = ([C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64]
-                                           + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p])
-    lib.fe_facemass_acc_f64.restype = C.c_int
-    lib.fe_facemass_acc_f64.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64,
-                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
-                                        C.c_void_p]
-    for fn in (lib.fe_grad3d_acc_f64, lib.fe_div3d_acc_f64):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p]
-    lib.fe_axpby.restype = C.c_int
-    lib.fe_axpby.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_void_p]
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

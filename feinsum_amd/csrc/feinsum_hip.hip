@@ -3073,7 +3073,22 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
     return FE_OK;
 }
 
-static int launch_family(int32_t family, const fe_argpack* a, void* stream) {
+int fe_launch(int32_t family, const fe_argpack* a, void* stream) {
+    if (!a) return fail(FE_EINVAL, "fe_launch: null argument pack");
+    if (family & FE_FAMILY_ACC) {   // out <- alpha * E + beta * out
+        const int32_t base = family & ~FE_FAMILY_ACC;
+        if (base == FE_FAMILY_FACEMASS)
+            return fe_facemass_acc_f64(a->J, a->D, a->v, a->outs, a->E, a->Np, a->nf, a->Nfp, a->b, a->layout_flags, a->alpha,
+                                       a->beta, stream);
+        if (base != FE_FAMILY_GRAD && base != FE_FAMILY_DIV)
+            return fail(FE_EUNSUPPORTED, "fe_launch: family 0x%x has no accumulating kernel (float64 face-mass, grad, div)", base);
+        if (!a->v || !a->outs) return fail(FE_EINVAL, "fe_launch: accumulating grad / div take their fields from v / outs");
+        for (int k = 0; k < a->b; ++k)   // one accumulating launch per field
+            if (int rc = (base == FE_FAMILY_GRAD ? fe_grad3d_acc_f64 : fe_div3d_acc_f64)(
+                    a->J, a->D, a->v[k], a->outs[k], a->E, a->Np, a->layout_flags, a->alpha, a->beta, stream))
+                return rc;
+        return FE_OK;
+    }
     if (family & FE_FAMILY_F32) return fe_launch_f32(family & ~FE_FAMILY_F32, a, stream);
     switch (family) {
         case FE_FAMILY_GRAD:
@@ -3122,7 +3137,7 @@ int fe_time_launches(int32_t family, const fe_argpack* args, int32_t n_launches,
     int rc = FE_OK;
     hipError_t e = hipEventRecord(t0, s);
     for (int i = 0; i < n_launches && rc == FE_OK && e == hipSuccess; ++i)
-        rc = launch_family(family, args, stream);
+        rc = fe_launch(family, args, stream);
     if (e == hipSuccess) e = hipEventRecord(t1, s);
     if (e == hipSuccess) e = hipEventSynchronize(t1);
     if (e == hipSuccess && rc == FE_OK) e = hipEventElapsedTime(ms_out, t0, t1);

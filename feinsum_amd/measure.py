@@ -65,7 +65,7 @@ from feinsum_amd.diagnostics import (HipLibraryError, InvalidParameterError,
 from feinsum_amd.einsum import INT_CLASSES, BatchedEinsum, SizeParam
 from feinsum_amd.adjoint import AdjointLaunch
 from feinsum_amd.family import (FAMILY_DIV, FAMILY_DIVCOMP, FAMILY_FACEMASS, FAMILY_GRAD,
-                                FAMILY_GRADPLANES, FAMILY_MATAPPLY, OP_J_ES, KernelPlan,
+                                FAMILY_GRADPLANES, OP_J_ES, KernelPlan,
                                 match_adjoint_family, match_family, match_operator_adjoint)
 
 logger = logging.getLogger(__name__)
@@ -271,54 +271,59 @@ def _long_length(einsum: BatchedEinsum, arg_dict: Mapping[str, Any]) -> Dict[str
     return values
 
 
+def _family_groups(plan: KernelPlan, einsum: BatchedEinsum) -> list:
+    """The rows of each launch of a family plan, as ``range`` objects: consecutive rows that share J and the operator
+    become one multi-field launch; div components go row by row."""
+    role = plan.roles
+    op_role = "D" if "D" in role else "R"
+    key = lambda row: (row[role["J"]].name if "J" in role else None, row[role[op_role]].name)   # noqa: E731
+    starts = [k for k, row in enumerate(einsum.args)
+              if k == 0 or plan.family == FAMILY_DIVCOMP or key(row) != key(einsum.args[k - 1])]
+    return [range(k, k2) for k, k2 in zip(starts, starts[1:] + [len(einsum.args)])]
+
+
 class _FamilyLaunch:
     """A family plan bound to concrete device arrays: launch / time."""
 
     def __init__(self, plan: KernelPlan, einsum: BatchedEinsum, arg_dict: Mapping[str, Any],
                  outs: Sequence[Any], variant: Any, scale: Optional[Tuple[float, float]] = None) -> None:
         self.plan, self.variant = plan, _hip.variant_code(variant)
-        # (alpha, beta) of a launch that accumulates inside its kernel -- face-mass (fe_facemass_acc_f64), grad and div of
-        # tetrahedra (fe_grad3d_acc_f64 / fe_div3d_acc_f64, one launch per field) -- else None
+        # (alpha, beta) of a launch that accumulates inside its kernel -- face-mass, grad and div of tetrahedra
+        # (FE_FAMILY_ACC: grad and div take one launch per field) -- else None
         self.scale = scale
         role = plan.roles
         rows = einsum.args
-        first = rows[0]
         long_role = "J" if "J" in role else "u"       # 'ij,ej->ei' has no geometry factor
         long_axis = einsum.in_idx_sets[role[long_role]].index(plan.long_index)
-        self.E = int(arg_dict[first[role[long_role]].name].shape[long_axis])
+        self.E = int(arg_dict[rows[0][role[long_role]].name].shape[long_axis])
         self._keep = (arg_dict, outs)
         self._prepared: Dict[Any, Any] = {}   # (operator pointer, flags) -> prepared device buffer
         p = plan.params
-        self.f32 = bool(p.get("f32"))         # all-float32 einsum: fe_launch_f32, whatever the variant
-        op_role = "D" if plan.family in (FAMILY_GRAD, FAMILY_DIV, FAMILY_DIVCOMP, FAMILY_MATAPPLY) else "R"
+        self.f32 = bool(p.get("f32"))         # all-float32 einsum: FE_FAMILY_F32, whatever the variant
         self.groups = []   # list of ArgPack (one per launch)
-        in_role = "u" if op_role == "D" else "v"
         self.group_family = plan.family
-        if plan.family == FAMILY_DIVCOMP and not self.f32 and self._bind_planes(einsum, arg_dict, outs):
-            return
-        # consecutive rows sharing J and the operator become one multi-field launch
-        k = 0
-        while k < len(rows):
-            jname = lambda row: row[role["J"]].name if "J" in role else None   # noqa: E731
-            jn, rn = jname(rows[k]), rows[k][role[op_role]].name
-            k2 = k + 1
-            while (plan.family != FAMILY_DIVCOMP and k2 < len(rows)
-                   and jname(rows[k2]) == jn and rows[k2][role[op_role]].name == rn):
-                k2 += 1
-            vptrs = [arg_dict[rows[m][role[in_role]].name].data_ptr() for m in range(k, k2)]
-            optrs = [outs[m].data_ptr() for m in range(k, k2)]
-            pack = _hip.ArgPack()
-            pack.J = arg_dict[jn].data_ptr() if jn is not None else None
-            pack.D = arg_dict[rn].data_ptr()
-            pack.u, pack.out = vptrs[0], optrs[0]
-            va, oa = _hip._ptr_array(vptrs), _hip._ptr_array(optrs)
-            self._keep += (va, oa)
-            pack.v, pack.outs = va, oa
-            pack.E, pack.Np = self.E, p["Np"]
-            pack.nf, pack.Nfp, pack.ndim = p.get("nf", 0), p.get("Nfp", 0), p.get("ndim", 3)
-            pack.b, pack.layout_flags, pack.variant = k2 - k, plan.layout_flags, self.variant
-            self.groups.append(pack)
-            k = k2
+        if not (plan.family == FAMILY_DIVCOMP and not self.f32 and self._bind_planes(einsum, arg_dict, outs)):
+            op_role, in_role = ("D", "u") if "D" in role else ("R", "v")
+            for group in _family_groups(plan, einsum):
+                first = rows[group[0]]
+                vptrs = [arg_dict[rows[m][role[in_role]].name].data_ptr() for m in group]
+                optrs = [outs[m].data_ptr() for m in group]
+                pack = _hip.ArgPack()
+                pack.J = arg_dict[first[role["J"]].name].data_ptr() if "J" in role else None
+                pack.D = arg_dict[first[role[op_role]].name].data_ptr()
+                pack.u, pack.out = vptrs[0], optrs[0]
+                va, oa = _hip._ptr_array(vptrs), _hip._ptr_array(optrs)
+                self._keep += (va, oa)
+                pack.v, pack.outs = va, oa
+                pack.E, pack.Np = self.E, p["Np"]
+                pack.nf, pack.Nfp, pack.ndim = p.get("nf", 0), p.get("Nfp", 0), p.get("ndim", 3)
+                pack.b, pack.layout_flags, pack.variant = len(group), plan.layout_flags, self.variant
+                self.groups.append(pack)
+        #: what fe_launch is told to run: the family of the packs and how their arrays are read and written
+        self.family_code = (self.group_family | (_hip.FAMILY_F32 if self.f32 else 0)
+                            | (_hip.FAMILY_ACC if scale is not None else 0))
+        for pack in self.groups:
+            pack.alpha, pack.beta = scale if scale is not None else (1.0, 0.0)
 
     def __del__(self) -> None:
         # the library keeps a record per prepared buffer (address -> shape, source operator): drop it before the buffer
@@ -402,47 +407,12 @@ class _FamilyLaunch:
     def launch(self, stream_ptr: int) -> None:
         lib = _hip.load_library()
         for pack in self.groups:
-            if self.scale is not None and self.plan.family in (FAMILY_GRAD, FAMILY_DIV):
-                entry = lib.fe_grad3d_acc_f64 if self.plan.family == FAMILY_GRAD else lib.fe_div3d_acc_f64
-                for k in range(pack.b):     # one accumulating launch per field
-                    _hip.check(entry(pack.J, pack.D, pack.v[k], pack.outs[k], pack.E, pack.Np, pack.layout_flags,
-                                     self.scale[0], self.scale[1], stream_ptr))
-            elif self.scale is not None:
-                _hip.check(lib.fe_facemass_acc_f64(pack.J, pack.D, pack.v, pack.outs, pack.E, pack.Np, pack.nf, pack.Nfp,
-                                                   pack.b, pack.layout_flags, self.scale[0], self.scale[1], stream_ptr))
-            elif self.f32:
-                _hip.check(lib.fe_launch_f32(self.plan.family, C_byref(pack), stream_ptr))
-            elif self.group_family == FAMILY_GRADPLANES:
-                _hip.check(lib.fe_gradplanes3d_f64(pack.j3, pack.D, pack.v, pack.outs, pack.E, pack.Np,
-                                                   pack.b, pack.layout_flags, pack.variant, stream_ptr))
-            elif self.plan.family == FAMILY_GRAD and pack.prepared:
-                _hip.check(lib.fe_grad3d_prepared_f64(pack.J, pack.D, pack.prepared, pack.v, pack.outs, pack.E,
-                                                      pack.Np, pack.b, pack.layout_flags, pack.variant, stream_ptr))
-            elif self.plan.family == FAMILY_GRAD:
-                _hip.check(lib.fe_grad_f64(pack.J, pack.D, pack.v, pack.outs, pack.E, pack.ndim, pack.Np,
-                                           pack.b, pack.layout_flags, pack.variant, stream_ptr))
-            elif self.plan.family == FAMILY_DIV and pack.prepared:
-                _hip.check(lib.fe_div3d_prepared_f64(pack.J, pack.D, pack.prepared, pack.v, pack.outs, pack.E,
-                                                     pack.Np, pack.b, pack.layout_flags, pack.variant, stream_ptr))
-            elif self.plan.family == FAMILY_DIV:
-                _hip.check(lib.fe_div_f64(pack.J, pack.D, pack.v, pack.outs, pack.E, pack.ndim, pack.Np,
-                                          pack.b, pack.layout_flags, pack.variant, stream_ptr))
-            elif self.plan.family == FAMILY_MATAPPLY:
-                _hip.check(lib.fe_matapply_f64(pack.J, pack.D, pack.v, pack.outs, pack.E, pack.Np, pack.b,
-                                               pack.layout_flags, pack.variant, stream_ptr))
-            elif self.plan.family == FAMILY_DIVCOMP:
-                _hip.check(lib.fe_divcomp_f64(pack.J, pack.D, pack.u, pack.out, pack.E, pack.ndim, pack.Np,
-                                              pack.layout_flags, pack.variant, stream_ptr))
-            else:
-                _hip.check(lib.fe_facemass_prepared_f64(pack.J, pack.D, pack.prepared, pack.v, pack.outs, pack.E,
-                                                        pack.Np, pack.nf, pack.Nfp, pack.b, pack.layout_flags,
-                                                        pack.variant, stream_ptr))
+            _hip.check(lib.fe_launch(self.family_code, C_byref(pack), stream_ptr))
 
     def time_batch(self, n: int, stream_ptr: int) -> float:
         """Seconds for *n* launches of the whole batched einsum (HIP events)."""
         if len(self.groups) == 1 and self.scale is None:
-            family = self.group_family | (_hip.FAMILY_F32 if self.f32 else 0)
-            return _hip.time_launches(family, self.groups[0], n, stream_ptr) * 1e-3
+            return _hip.time_launches(self.family_code, self.groups[0], n, stream_ptr) * 1e-3
         import torch
 
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -583,21 +553,6 @@ def _check_scale(alpha: Any, beta: Any) -> Tuple[float, float]:
     return alpha, beta
 
 
-def _family_group_sizes(plan: KernelPlan, einsum: BatchedEinsum) -> Tuple[int, ...]:
-    """Fields per launch of a family plan: consecutive rows that share J and the operator (as ``_FamilyLaunch`` groups
-    them)."""
-    role, rows = plan.roles, einsum.args
-    op_role = "D" if "D" in role else "R"
-    key = lambda row: (row[role["J"]].name if "J" in role else None, row[role[op_role]].name)   # noqa: E731
-    sizes: list = []
-    for k, row in enumerate(rows):
-        if k and key(row) == key(rows[k - 1]) and plan.family != FAMILY_DIVCOMP:
-            sizes[-1] += 1
-        else:
-            sizes.append(1)
-    return tuple(sizes)
-
-
 def accumulate_route(einsum: BatchedEinsum, transform: Any = None) -> str:
     """
     Which way an accumulating evaluation of *einsum* (``evaluate(..., alpha=, beta=)`` other than (1, 0)) takes under
@@ -620,7 +575,7 @@ def accumulate_route(einsum: BatchedEinsum, transform: Any = None) -> str:
     plan = match_family(einsum) if variant in (None, "auto", "mfma", 0, 2) else None
     fused = (plan is not None and plan.family == FAMILY_FACEMASS and not plan.params.get("f32")
              and plan.params.get("nf") == 4 and (plan.params.get("Np"), plan.params.get("Nfp")) in _ACC_FACEMASS_SHAPES
-             and min(_family_group_sizes(plan, einsum)) >= 2)
+             and min(len(g) for g in _family_groups(plan, einsum)) >= 2)
     if forced == "epilogue":
         if (plan is not None and plan.family in (FAMILY_GRAD, FAMILY_DIV) and not plan.params.get("f32")
                 and plan.params.get("ndim", 3) == 3 and plan.params.get("Np") in _ACC_EPILOGUE_NP):

@@ -67,7 +67,7 @@ extern "C" {
                                  * 1 % slower otherwise; results are those of FE_VARIANT_MFMA to the last bit or two.  Other entry points
                                  * answer FE_EUNSUPPORTED. */
 
-/* families, for fe_time_launches / fe_flops_per_element */
+/* families, for fe_launch / fe_time_launches / fe_flops_per_element */
 #define FE_FAMILY_GRAD     1
 #define FE_FAMILY_DIV      2
 #define FE_FAMILY_GRADDIV  3
@@ -75,7 +75,9 @@ extern "C" {
 #define FE_FAMILY_DIVCOMP  5
 #define FE_FAMILY_GRADPLANES 6
 #define FE_FAMILY_MATAPPLY 7
-#define FE_FAMILY_F32      0x100 /* or-ed into a family for fe_time_launches: the float32 launch (fe_launch_f32) */
+#define FE_FAMILY_F32      0x100 /* or-ed into a family for fe_launch / fe_time_launches: the float32 launch (fe_launch_f32) */
+#define FE_FAMILY_ACC      0x200 /* or-ed into a family for fe_launch / fe_time_launches: out <- alpha * E + beta * out
+                                  * (face-mass, grad, div; float64 only) */
 
 /* face-mass operand layouts (bit flags) */
 #define FE_FM_J_EF   0  /* J[E][nf]      (test_loopy_utils.py:41)            */
@@ -385,8 +387,8 @@ int fe_split_trim(void);
 int64_t fe_flops_per_element(int32_t family, int32_t Np, int32_t nf,
                              int32_t Nfp, int32_t b);
 
-/* Argument pack for fe_time_launches (one struct for every family; unused
- * fields are ignored). */
+/* Argument pack for fe_launch, fe_launch_f32 and fe_time_launches (one struct for
+ * every family; unused fields are ignored). */
 typedef struct fe_argpack {
     const double* J;
     const double* D;          /* D (grad/div) or R/L (face-mass)              */
@@ -401,7 +403,22 @@ typedef struct fe_argpack {
     const double* const* j3;  /* FE_FAMILY_GRADPLANES: 3 ptrs; v = u (b), outs = planes (3 b) */
     int32_t ndim;             /* grad / div: 0 or 3 = tetrahedra, 2 = triangles (v / outs, any b) */
     const void* prepared;     /* the operator D (or R) in prepared form, or NULL (fe_prepare_operator) */
+    double alpha, beta;       /* FE_FAMILY_ACC only: out <- alpha * E + beta * out */
 } fe_argpack;
+
+/* One launch of `family` (FE_FAMILY_*) on the arrays of `args`: the one dispatcher behind every bound DG launch and
+ * behind fe_time_launches.  Every case is a call of the named entry point above with the pack's fields, so checks,
+ * messages and results are that entry point's:
+ *   GRAD / DIV    ndim == 2: fe_grad_f64 / fe_div_f64 on v / outs; else fe_grad3d_prepared_f64 / fe_div3d_prepared_f64,
+ *                 on v / outs for b > 1, on the single pair u / out otherwise
+ *   GRADPLANES    fe_gradplanes3d_f64 (j3, v, outs)       MATAPPLY  fe_matapply_f64 (v, outs)
+ *   GRADDIV       fe_graddiv3d_prepared_f64               DIVCOMP   fe_divcomp_f64 (u, out; ndim 2, else 3)
+ *   FACEMASS      fe_facemass_prepared_f64 (v, outs)
+ * family | FE_FAMILY_F32 is fe_launch_f32.  family | FE_FAMILY_ACC accumulates with the pack's alpha and beta (ignored
+ * without the bit): FACEMASS is fe_facemass_acc_f64 on v / outs; GRAD and DIV are fe_grad3d_acc_f64 / fe_div3d_acc_f64
+ * once per field k < b on v[k], outs[k], stopping at the first error; any other family, and FE_FAMILY_ACC together with
+ * FE_FAMILY_F32, is FE_EUNSUPPORTED.  A null pack and an unknown family are FE_EINVAL. */
+int fe_launch(int32_t family, const fe_argpack* args, void* stream);
 
 /* float32 operands (the reference validates float32 einsums at 1e-6 and carries float32 peaks:
  * src/feinsum/measure.py:178-192, src/feinsum/data/device_info.py:5-26).  One entry point for the families

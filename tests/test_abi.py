@@ -28,6 +28,107 @@ def test_library_exports_every_declared_symbol():
     assert set(declared) == set(_hip.EXPORTED_SYMBOLS)
 
 
+#: the ctypes type of every C type the header spells (a spelling that is not here fails the tests below)
+C_TYPES = {
+    "char*": ctypes.c_char_p, "const char*": ctypes.c_char_p,
+    "const double*": ctypes.c_void_p, "double*": ctypes.c_void_p, "const void*": ctypes.c_void_p, "void*": ctypes.c_void_p,
+    "const double* const*": ctypes.POINTER(ctypes.c_void_p), "double* const*": ctypes.POINTER(ctypes.c_void_p),
+    "const void* const*": ctypes.POINTER(ctypes.c_void_p), "void**": ctypes.POINTER(ctypes.c_void_p),
+    "const fe_argpack*": ctypes.POINTER(_hip.ArgPack), "const fe_einsum_desc*": ctypes.POINTER(_hip.EinsumDesc),
+    "double": ctypes.c_double, "float*": ctypes.POINTER(ctypes.c_float),
+    "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+    "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64,
+    "int32_t*": ctypes.POINTER(ctypes.c_int32), "int64_t*": ctypes.POINTER(ctypes.c_int64),
+    "size_t*": ctypes.POINTER(ctypes.c_size_t), "uint64_t*": ctypes.POINTER(ctypes.c_uint64),
+}
+
+
+def _header_code():
+    """The header without comments; ``(code without preprocessor lines, {macro: integer value})``."""
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "feinsum_hip.h").read_text(), flags=re.S)
+    macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"^#define\s+(FE_\w+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))\s*$", text, flags=re.M)}
+    return re.sub(r"^\s*#.*$", "", text, flags=re.M), macros
+
+
+def _split_decl(decl):
+    """``"const double* const* u"`` -> ``("const double* const*", "u")``: the last word is the name."""
+    m = re.fullmatch(r"(.*?)(\w+)((?:\[\w+\])*)", " ".join(decl.split()))
+    assert m and m.group(1).strip(), decl
+    return re.sub(r"\s*\*", "*", m.group(1).strip()), m.group(2), re.findall(r"\[(\w+)\]", m.group(3))
+
+
+def _ctype(spelling):
+    assert spelling in C_TYPES, f"include/feinsum_hip.h spells a C type this test has no ctypes type for: {spelling!r}"
+    return C_TYPES[spelling]
+
+
+def _prototypes():
+    """``{name: (restype, [argtypes])}`` of every ``ret name(args);`` of the header."""
+    code, _ = _header_code()
+    code = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", code, flags=re.S)
+    protos = {}
+    for decl in (d.strip() for d in code.replace('extern "C" {', "").split(";")):
+        if "(" not in decl:
+            continue
+        m = re.fullmatch(r"(.*?)\b(fe_\w+)\s*\((.*)\)", decl, flags=re.S)
+        assert m, f"not of the form `ret name(args)`: {decl!r}"
+        ret = re.sub(r"\s*\*", "*", " ".join(m.group(1).split()))
+        args = [a.strip() for a in m.group(3).split(",")]
+        args = [] if args in (["void"], [""]) else args
+        assert m.group(2) not in protos
+        protos[m.group(2)] = (_ctype(ret), [_ctype(_split_decl(a)[0]) for a in args])
+    return protos
+
+
+def _struct_fields(name):
+    """``[(field, ctypes type)]`` of ``typedef struct name { ... } name;`` in declaration order."""
+    code, macros = _header_code()
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), code, flags=re.S).group(1)
+    fields = []
+    for decl in (d.strip() for d in body.split(";")):
+        if not decl:
+            continue
+        first, *more = [x.strip() for x in decl.split(",")]     # `int32_t Np, nf, Nfp;` declares three of one type
+        spelling, fname, dims = _split_decl(first)
+        for fname, dims in [(fname, dims)] + [_split_decl(spelling + " " + x)[1:] for x in more]:
+            ctype = _ctype(spelling)
+            for d in reversed(dims):                                  # a[X][Y] is an array of X arrays of Y
+                ctype = ctype * (macros[d] if d in macros else int(d))
+            fields.append((fname, ctype))
+    return fields
+
+
+def test_signature_table_matches_the_header():
+    """restype and argtypes of every function, derived from the header's prototypes through C_TYPES, are what
+    ``_hip.SIGNATURES`` gives ctypes: a wrong width or a missing argument there would be silent undefined behaviour."""
+    protos = _prototypes()
+    assert set(protos) == set(_declared_symbols()) == set(_hip.SIGNATURES)
+    assert list(protos) == list(_hip.SIGNATURES)          # the table keeps the header's order
+    for name, (restype, argtypes) in protos.items():
+        assert _hip.SIGNATURES[name][0] is restype, name
+        assert list(_hip.SIGNATURES[name][1]) == argtypes, name
+    lib = _hip.load_library()
+    for name, (restype, argtypes) in protos.items():      # ... and load_library applied it
+        assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == argtypes, name
+    assert _hip.EXPORTED_SYMBOLS == tuple(_hip.SIGNATURES)
+
+
+def test_struct_mirrors_match_the_header():
+    for cname, mirror in (("fe_argpack", _hip.ArgPack), ("fe_einsum_desc", _hip.EinsumDesc)):
+        assert [(n, t) for n, t in mirror._fields_] == _struct_fields(cname), cname
+    _, macros = _header_code()
+    assert (_hip.FAMILY_F32, _hip.FAMILY_ACC) == (macros["FE_FAMILY_F32"], macros["FE_FAMILY_ACC"])
+    assert (_hip.FE_MAX_EINSUM_OPERANDS, _hip.FE_MAX_EINSUM_INDICES) == (macros["FE_MAX_EINSUM_OPERANDS"],
+                                                                         macros["FE_MAX_EINSUM_INDICES"])
+    # alpha and beta were appended: no earlier offset moved
+    assert (_hip.ArgPack.prepared.offset, _hip.ArgPack.alpha.offset, ctypes.sizeof(_hip.ArgPack)) == (112, 120, 136)
+
+
+def test_an_unmapped_c_type_fails():
+    with pytest.raises(AssertionError, match="no ctypes type"):
+        _ctype("long double*")
+
+
 def test_version_and_flop_counters():
     lib = _hip.load_library()
     assert lib.fe_version() == 1000
