@@ -28,6 +28,7 @@ VARIANTS = {"auto": VARIANT_AUTO, "generic": VARIANT_GENERIC, "mfma": VARIANT_MF
 
 FAMILY_F32 = 0x100    # FE_FAMILY_F32
 FAMILY_ACC = 0x200    # FE_FAMILY_ACC
+FAMILY_FIELDS_F32 = 0x400    # FE_FAMILY_FIELDS_F32: float32 fields in float64 div / face-mass
 
 
 class ArgPack(C.Structure):
@@ -120,6 +121,9 @@ SIGNATURES = {
     "fe_split_trim": (_int, []),
     "fe_flops_per_element": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "fe_launch": (_int, [_i32, C.POINTER(ArgPack), _p]),
+    "fe_grad3d_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _p]),
+    "fe_div3d_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _p]),
+    "fe_facemass_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
     "fe_launch_f32": (_int, [_i32, C.POINTER(ArgPack), _p]),
     "fe_set_tail_rounds": (_int, [_i32]),
     "fe_set_tail_min_rounds": (_int, [_i32]),
@@ -634,6 +638,8 @@ def last_launch_info() -> dict:
     d["interleaved"] = bool(d["kind"] & 4)
     d["quarter_tail"] = bool(d["kind"] & 8)
     d["staggered_start"] = bool(d["kind"] & 16)
+    d["mixed_fields"] = bool(d["kind"] & 32)             # fe_grad3d_mixed_f64 / fe_div3d_mixed_f64 / fe_facemass_mixed_f64
+    d["plain_field_loads"] = bool(d["kind"] & 64)        # ... with the fields through registers instead of LDS-DMA
     d["kind"] = "B build interleaved" if d["kind"] & 4 else "default"
     return d
 

@@ -35,6 +35,7 @@
 #include "fe_div_f32.h"
 #include "fe_facemass_f32.h"
 #include "fe_tiled.h"
+#include "fe_mixed.h"
 
 namespace {
 
@@ -1226,6 +1227,60 @@ int launch_f32_facemass(const fe_argpack* a, const double* const* vin, double* c
             return rc;
     }
     FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+// ---- float32 fields in float64 grad, div and face-mass (fe_mixed.h).  A launch below one wave tile still runs one block: its
+// remainder code covers every element.  `plain`: the launch's field loads go through registers (a field plane that does not
+// start on an 8-byte boundary: fe_mixed.h).  grad and div take the same arguments: one launcher, one launch per field.
+template <typename G, auto KD, auto KP>
+int launch_mixed_fields(const double* J, const double* D, const float* const* v, double* const* outs, int b, int64_t E, int opT,
+                     bool plain, const char* what, const char* what_plain, hipStream_t s) {
+    const int64_t nTiles = E / G::TEL;
+    const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
+    const Walk walk = walk_static(nTiles > 0 ? nTiles : 1);
+    for (int k = 0; k < b; ++k) {
+        const float* u = v[k];
+        double* out = outs[k];
+        auto args = [&](const Launch&) {
+            return call(opT, fe::kLaunchMixedFields | (plain ? fe::kLaunchPlainFieldLoads : 0), J, D, u, out, E, nTiles, opT);
+        };
+        if (int rc = plain ? mfma_launch<KP>(s, walk, geo, what_plain, args) : mfma_launch<KD>(s, walk, geo, what, args)) return rc;
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+template <typename G, auto KD, auto KP>
+int launch_mixed_facemass(const double* J, const double* R, const float* const* v, double* const* outs, int b, int64_t E, int jl,
+                          int rl, bool plain, const char* what, const char* what_plain, hipStream_t s) {
+    const int64_t nTiles = E / G::TEL;
+    const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
+    const Walk walk = walk_static(nTiles > 0 ? nTiles : 1);
+    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // groups of up to kMaxFields fields share J and the fragments
+        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
+        const fe::FieldPtrs P = field_group(reinterpret_cast<const double* const*>(v) + k0, outs + k0, nb);
+        auto args = [&](const Launch&) {
+            return call(0, fe::kLaunchMixedFields | (plain ? fe::kLaunchPlainFieldLoads : 0), J, R, P, nb, E, nTiles, jl, rl);
+        };
+        if (int rc = plain ? mfma_launch<KP>(s, walk, geo, what_plain, args) : mfma_launch<KD>(s, walk, geo, what, args)) return rc;
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+// the argument checks the mixed entry points share: float32 fields 4-byte aligned, everything else 8-byte, before any device work
+int check_mixed(const char* who, const void* J, const void* op, const float* const* v, double* const* outs, int64_t E, int32_t Np,
+                int32_t b) {
+    if (E < 0) return fail(FE_EINVAL, "%s: E must be >= 0 (got %lld)", who, (long long)E);
+    if (Np <= 0 || b <= 0) return fail(FE_EINVAL, "%s: Np and b must be positive (got %d, %d)", who, Np, b);
+    if (!v || !outs) return fail(FE_EINVAL, "%s: null pointer table", who);
+    if ((reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(op)) & 7u)
+        return fail(FE_EINVAL, "%s: J and the operator must be 8-byte aligned (float64 arrays)", who);
+    for (int k = 0; k < b; ++k) {
+        if (reinterpret_cast<uintptr_t>(v[k]) & 3u) return fail(FE_EINVAL, "%s: field %d must be 4-byte aligned (a float32 array)", who, k);
+        if (reinterpret_cast<uintptr_t>(outs[k]) & 7u) return fail(FE_EINVAL, "%s: output %d must be 8-byte aligned (a float64 array)", who, k);
+    }
     return FE_OK;
 }
 
@@ -3073,8 +3128,125 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
     return FE_OK;
 }
 
+// float32 fields, float64 J / operator / outputs (fe_mixed.h)
+int fe_div3d_mixed_f64(const double* J, const double* D, const void* const* fields, double* const* outs, int64_t E, int32_t Np,
+                       int32_t b, int32_t layout_flags, void* stream) {
+    forget_last_launch();
+    const float* const* v = reinterpret_cast<const float* const*>(fields);
+    const char* who = "div, float32 fields";
+    if (int rc = check_mixed(who, J, D, v, outs, E, Np, b)) return rc;
+    if (layout_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, layout_flags);
+    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
+        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
+    if (E == 0) return FE_OK;
+    if (!J || !D) return fail(FE_EINVAL, "%s: null device pointer", who);
+    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    bool plain = false;   // a plane x E Np floats behind a field's start that is not on an 8-byte boundary: no LDS-DMA for the fields
+    for (int k = 0; k < b; ++k) {
+        if (!v[k] || !outs[k]) return fail(FE_EINVAL, "%s: null field pointer %d", who, k);
+        for (int x = 0; x < 3; ++x) plain = plain || ((reinterpret_cast<uintptr_t>(v[k]) + (uintptr_t)x * (uintptr_t)E * Np * 4u) & 7u) != 0;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int opT = (layout_flags & FE_OP_TRANSPOSED) ? 1 : 0;
+#define FE_MIXED_DIV(NP, M)                                                                                                   \
+    launch_mixed_fields<fe::DivMixedGeomT<NP, M>, fe::div3d_mixed_kernel<NP, M, false>, fe::div3d_mixed_kernel<NP, M, true>>( \
+        J, D, v, outs, b, E, opT, plain, "div float32 fields Np=" #NP " M=" #M, "div float32 fields Np=" #NP " M=" #M ", plain loads", s)
+    switch (Np) {   // the (Np, M) geometries of fe_div3d_f64
+        case 35: return FE_MIXED_DIV(35, 1);
+        case 20: return FE_MIXED_DIV(20, 1);
+        case 10: return FE_MIXED_DIV(10, 3);
+        default: return FE_MIXED_DIV(4, 5);
+    }
+#undef FE_MIXED_DIV
+}
+
+int fe_grad3d_mixed_f64(const double* J, const double* D, const void* const* fields, double* const* outs, int64_t E, int32_t Np,
+                        int32_t b, int32_t layout_flags, void* stream) {
+    forget_last_launch();
+    const float* const* v = reinterpret_cast<const float* const*>(fields);
+    const char* who = "grad, float32 fields";
+    if (int rc = check_mixed(who, J, D, v, outs, E, Np, b)) return rc;
+    if (layout_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, layout_flags);
+    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
+        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
+    if (E == 0) return FE_OK;
+    if (!J || !D) return fail(FE_EINVAL, "%s: null device pointer", who);
+    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    bool plain = false;   // a field that does not start on an 8-byte boundary: no LDS-DMA for the fields
+    for (int k = 0; k < b; ++k) {
+        if (!v[k] || !outs[k]) return fail(FE_EINVAL, "%s: null field pointer %d", who, k);
+        plain = plain || (reinterpret_cast<uintptr_t>(v[k]) & 7u) != 0;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int opT = (layout_flags & FE_OP_TRANSPOSED) ? 1 : 0;
+#define FE_MIXED_GRAD(NP, M)                                                                                                     \
+    launch_mixed_fields<fe::GradMixedGeomT<M, NP>, fe::grad3d_mixed_kernel<M, NP, false>, fe::grad3d_mixed_kernel<M, NP, true>>( \
+        J, D, v, outs, b, E, opT, plain, "grad float32 fields Np=" #NP " M=" #M, "grad float32 fields Np=" #NP " M=" #M ", plain loads", s)
+    switch (Np) {   // the (Np, M) geometries of fe_grad3d_f64
+        case 35: return FE_MIXED_GRAD(35, 1);
+        case 20: return FE_MIXED_GRAD(20, 2);
+        case 10: return FE_MIXED_GRAD(10, 3);
+        default: return FE_MIXED_GRAD(4, 5);
+    }
+#undef FE_MIXED_GRAD
+}
+
+int fe_facemass_mixed_f64(const double* J, const double* R, const void* const* fields, double* const* outs, int64_t E, int32_t Np,
+                          int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream) {
+    forget_last_launch();
+    const float* const* v = reinterpret_cast<const float* const*>(fields);
+    const char* who = "face-mass, float32 fields";
+    if (int rc = check_mixed(who, J, R, v, outs, E, Np, b)) return rc;
+    if (nf <= 0 || Nfp <= 0) return fail(FE_EINVAL, "%s: nf and Nfp must be positive (got %d, %d)", who, nf, Nfp);
+    if (layout_flags & ~7) return fail(FE_EINVAL, "%s: bad layout flags %d", who, layout_flags);
+    if (!(nf == 4 && ((Np == 35 && Nfp == 15) || (Np == 20 && Nfp == 10) || (Np == 10 && Nfp == 6) || (Np == 4 && Nfp == 3))))
+        return fail(FE_EUNSUPPORTED, "%s: (nf, Np, Nfp) = (%d, %d, %d) has no kernel (tetrahedra p = 1..4)", who, nf, Np, Nfp);
+    if (E == 0) return FE_OK;
+    if (!J || !R) return fail(FE_EINVAL, "%s: null device pointer", who);
+    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    bool plain = false;   // a face slab f E Nfp floats behind a field's start that is not on an 8-byte boundary
+    for (int k = 0; k < b; ++k) {
+        if (!v[k] || !outs[k]) return fail(FE_EINVAL, "%s: null field pointer %d", who, k);
+        for (int f = 0; f < 4; ++f) plain = plain || ((reinterpret_cast<uintptr_t>(v[k]) + (uintptr_t)f * (uintptr_t)E * Nfp * 4u) & 7u) != 0;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int jl = (layout_flags & FE_FM_J_FE) ? 1 : 0;
+    const int rl = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((layout_flags & FE_FM_R_T) ? 2 : 0);
+#define FE_MIXED_FM(NP, NFP, M)                                                                                     \
+    launch_mixed_facemass<fe::FmMixedGeomT<NP, NFP, M>, fe::facemass_mixed_kernel<NP, NFP, M, false>,               \
+                          fe::facemass_mixed_kernel<NP, NFP, M, true>>(J, R, v, outs, b, E, jl, rl, plain,          \
+                                                                       "face-mass float32 fields Np=" #NP " M=" #M, \
+                                                                       "face-mass float32 fields Np=" #NP " M=" #M ", plain loads", s)
+    switch (Np) {   // the (Np, Nfp, M) geometries of fe_facemass_f64
+        case 35: return FE_MIXED_FM(35, 15, 1);
+        case 20: return FE_MIXED_FM(20, 10, 1);
+        case 10: return FE_MIXED_FM(10, 6, 2);
+        default: return FE_MIXED_FM(4, 3, 4);
+    }
+#undef FE_MIXED_FM
+}
+
 int fe_launch(int32_t family, const fe_argpack* a, void* stream) {
     if (!a) return fail(FE_EINVAL, "fe_launch: null argument pack");
+    if (family & FE_FAMILY_FIELDS_F32) {   // float32 fields, everything else float64: the pack's field pointers are nominal
+        const int32_t base = family & ~FE_FAMILY_FIELDS_F32;
+        if (base != FE_FAMILY_GRAD && base != FE_FAMILY_DIV && base != FE_FAMILY_FACEMASS)
+            return fail(FE_EUNSUPPORTED, "fe_launch: family 0x%x has no kernel for float32 fields (float64 grad, div and face-mass "
+                        "of tetrahedra; not together with FE_FAMILY_F32 or FE_FAMILY_ACC)", base);
+        const int b = a->b > 0 ? a->b : 1;
+        const void* one_in[1] = {a->u};
+        double* one_out[1] = {a->out};
+        const void* const* v = reinterpret_cast<const void* const*>(a->v);
+        double* const* outs = a->outs;
+        if (!v || !outs) {
+            if (b != 1) return fail(FE_EINVAL, "fe_launch: b = %d needs the v / outs pointer arrays", b);
+            v = one_in;
+            outs = one_out;
+        }
+        if (base == FE_FAMILY_GRAD) return fe_grad3d_mixed_f64(a->J, a->D, v, outs, a->E, a->Np, b, a->layout_flags, stream);
+        if (base == FE_FAMILY_DIV) return fe_div3d_mixed_f64(a->J, a->D, v, outs, a->E, a->Np, b, a->layout_flags, stream);
+        return fe_facemass_mixed_f64(a->J, a->D, v, outs, a->E, a->Np, a->nf, a->Nfp, b, a->layout_flags, stream);
+    }
     if (family & FE_FAMILY_ACC) {   // out <- alpha * E + beta * out
         const int32_t base = family & ~FE_FAMILY_ACC;
         if (base == FE_FAMILY_FACEMASS)

@@ -147,6 +147,53 @@ def match_family(einsum: BatchedEinsum) -> Optional[KernelPlan]:
 
 
 # --------------------------------------------------------------------------
+# float32 fields in the float64 families: grad, div and face-mass of tetrahedra p = 1..4 whose fields
+# are float32 while every J and every operator is float64.  Kept apart from match_family on purpose -- "auto" keeps its
+# route for these einsums; only transform="mixed_family" reaches the kernels of csrc/fe_mixed.h.
+# --------------------------------------------------------------------------
+
+#: (Np, Nfp) of the tetrahedral orders p = 1..4 (nf = 4): the shapes fe_mixed.h is compiled for
+MIXED_TET_SHAPES = ((4, 3), (10, 6), (20, 10), (35, 15))
+MIXED_FAMILY_RULE = ("grad 'xre,rij,ej->xei', div 'xre,rij,xej->ei' (operator 'rij' or 'rji') or face-mass 'ef,fij,fej->ei' (its "
+                     "eight J / R layouts) of tetrahedra p = 1..4 (Np = 4, 10, 20, 35; nf = 4, Nfp = 3, 6, 10, 15), every "
+                     "field of every row float32, every J and every operator float64")
+
+
+def match_mixed_family(einsum: BatchedEinsum) -> Optional[KernelPlan]:
+    """The :class:`KernelPlan` (``params["fields_f32"] = 1``) of a DG einsum with float32 fields in float64 geometry
+    factors and operators -- :data:`MIXED_FAMILY_RULE` -- else ``None``."""
+    f32, f64 = np.dtype("float32"), np.dtype("float64")
+    for family, flags, subscripts, roles in _TEMPLATES:
+        if family not in (FAMILY_GRAD, FAMILY_DIV, FAMILY_FACEMASS):
+            continue
+        m = _match_template(einsum, subscripts)
+        if m is None:
+            continue
+        perm, mapping = m
+        dim = lambda t: einsum.index_to_dim_length[mapping[t]]  # noqa: E731
+        if any(isinstance(dim(t), SizeParam) for t in mapping if t != "e"):
+            continue
+        role = {name: perm[k] for k, name in enumerate(roles)}
+        field ="u" if "u" in role else "v"
+        if not all(np.dtype(row[role[field]].dtype) == f32 and
+                   all(np.dtype(row[p].dtype) == f64 for name, p in role.items() if name != field)
+                   for row in einsum.args):
+            continue
+        if family == FAMILY_FACEMASS:
+            if int(dim("f")) != 4 or (int(dim("i")), int(dim("j"))) not in MIXED_TET_SHAPES:
+                continue
+            params = {"Np": int(dim("i")), "nf": 4, "Nfp": int(dim("j"))}
+        else:
+            if (int(dim("x")), int(dim("r"))) != (3, 3) or int(dim("i")) != int(dim("j")) \
+                    or int(dim("i")) not in [np_ for np_, _ in MIXED_TET_SHAPES]:
+                continue
+            params = {"Np": int(dim("i")), "ndim": 3}
+        params["fields_f32"] = 1
+        return KernelPlan(family, flags, role, mapping["e"], params)
+    return None
+
+
+# --------------------------------------------------------------------------
 # adjoint-only shapes (DESIGN.md section 3l): the einsums that the gradients of the DG families need and that no forward
 # family kernel covers.  Kept apart from match_family on purpose -- "auto" on a user-built einsum of one of these shapes
 # keeps its kernel; only the autograd path and the "adjoint" transform reach these kernels.

@@ -27,7 +27,9 @@ Argument conventions kept from the reference:
                space summed into a small output as a split reduction over the whole chip,
                ``feinsum_amd.reduction``; ``"adjoint"``: the adjoint kernels of the DG families, for the einsums
                ``family.match_adjoint_family`` recognises only; ``"operator_adjoint"``: the
-               operator-gradient kernels, for the einsums ``family.match_operator_adjoint`` recognises only); in a dict, ``"prepared": True`` lets a
+               operator-gradient kernels, for the einsums ``family.match_operator_adjoint`` recognises only;
+               ``"mixed_family"``: grad, div and face-mass with float32 fields in float64 geometry factors and
+               operators, for the einsums ``family.match_mixed_family`` recognises only); in a dict, ``"prepared": True`` lets a
                bound launch (``timeit``) use a prepared copy of its operator
                matrices; ``"placement"`` (or ``$FEINSUM_PLACEMENT``): ``timeit``
                allocates one array per operand as the reference does; with the
@@ -66,7 +68,8 @@ from feinsum_amd.einsum import INT_CLASSES, BatchedEinsum, SizeParam
 from feinsum_amd.adjoint import AdjointLaunch
 from feinsum_amd.family import (FAMILY_DIV, FAMILY_DIVCOMP, FAMILY_FACEMASS, FAMILY_GRAD,
                                 FAMILY_GRADPLANES, OP_J_ES, KernelPlan,
-                                match_adjoint_family, match_family, match_operator_adjoint)
+                                MIXED_FAMILY_RULE, match_adjoint_family, match_family, match_mixed_family,
+                                match_operator_adjoint)
 
 logger = logging.getLogger(__name__)
 
@@ -300,6 +303,7 @@ class _FamilyLaunch:
         self._prepared: Dict[Any, Any] = {}   # (operator pointer, flags) -> prepared device buffer
         p = plan.params
         self.f32 = bool(p.get("f32"))         # all-float32 einsum: FE_FAMILY_F32, whatever the variant
+        self.fields_f32 = bool(p.get("fields_f32"))   # float32 fields only (match_mixed_family): FE_FAMILY_FIELDS_F32
         self.groups = []   # list of ArgPack (one per launch)
         self.group_family = plan.family
         if not (plan.family == FAMILY_DIVCOMP and not self.f32 and self._bind_planes(einsum, arg_dict, outs)):
@@ -321,6 +325,7 @@ class _FamilyLaunch:
                 self.groups.append(pack)
         #: what fe_launch is told to run: the family of the packs and how their arrays are read and written
         self.family_code = (self.group_family | (_hip.FAMILY_F32 if self.f32 else 0)
+                            | (_hip.FAMILY_FIELDS_F32 if self.fields_f32 else 0)
                             | (_hip.FAMILY_ACC if scale is not None else 0))
         for pack in self.groups:
             pack.alpha, pack.beta = scale if scale is not None else (1.0, 0.0)
@@ -343,7 +348,7 @@ class _FamilyLaunch:
         current stream: call it with the stream of *stream_ptr* current (``_bind`` does)."""
         import torch
 
-        if self.f32 or self.variant not in (_hip.VARIANT_AUTO, _hip.VARIANT_MFMA, _hip.VARIANT_MFMA_SPLIT) or self.group_family == FAMILY_GRADPLANES \
+        if self.f32 or self.fields_f32 or self.variant not in (_hip.VARIANT_AUTO, _hip.VARIANT_MFMA, _hip.VARIANT_MFMA_SPLIT) or self.group_family == FAMILY_GRADPLANES \
                 or self.plan.family not in (FAMILY_GRAD, FAMILY_DIV, FAMILY_FACEMASS):
             return 0
         done = 0
@@ -502,9 +507,16 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     plain kernel of their own).  The reduction rule is checked before the contraction rule.  ``"adjoint"`` (that transform only: an
     einsum that ``family.match_adjoint_family`` recognises, else ``NotImplementedError``) runs the adjoint kernels, and
     ``"operator_adjoint"`` (that transform only: ``family.match_operator_adjoint``, else ``NotImplementedError``) the
-    operator-gradient kernels.
+    operator-gradient kernels.  ``"mixed_family"`` (that transform only: ``family.match_mixed_family``, else
+    ``NotImplementedError`` naming the rule) runs the DG kernels for float32 fields.
     """
     variant = _variant_from_transform(transform)
+    if variant == "mixed_family":
+        if match_mixed_family(einsum) is None:
+            raise NotImplementedError(
+                f"transform 'mixed_family': einsum '{einsum.get_subscripts()}' x {einsum.b} is not {MIXED_FAMILY_RULE}"
+                " (feinsum_amd.family.match_mixed_family)")
+        return "mixed_family"
     if variant == "adjoint":
         if match_adjoint_family(einsum) is None:
             raise NotImplementedError(
@@ -665,6 +677,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     elif kind == "operator_adjoint":
         with torch.cuda.device(q.torch_device):
             bound = AdjointLaunch(match_operator_adjoint(einsum), einsum, arg_dict, outs, stream=q.stream)
+    elif kind == "mixed_family":     # (accumulation: the "axpby" route -- accumulate_route knows no other for it)
+        bound = _FamilyLaunch(match_mixed_family(einsum), einsum, arg_dict, outs, None)
     elif kind == "family":
         bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform),
                               scale=(alpha, beta) if route in ("kernel", "epilogue") else None)

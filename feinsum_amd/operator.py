@@ -67,7 +67,8 @@ class _WaveOpLaunch:
 
 
 def _single_plain_group(b: Any, family: int) -> bool:
-    return (isinstance(b, _FamilyLaunch) and b.plan.family == family and len(b.groups) == 1
+    # (a stage bound under "mixed_family" -- float32 fields -- stays a launch of its own: the fused kernels read float64)
+    return (isinstance(b, _FamilyLaunch) and not getattr(b, "fields_f32", False) and b.plan.family == family and len(b.groups) == 1
             and (family == FAMILY_FACEMASS
                  or (b.groups[0].b == 1 and b.plan.layout_flags == 0 and b.groups[0].ndim == 3)))
 
@@ -146,7 +147,7 @@ class BoundOperator:
             if hasattr(b, "entry_point"):
                 names.append(b.entry_point)
             elif isinstance(b, _FamilyLaunch):
-                names += ["fe_gradplanes" if b.group_family == 6 else f"fe_{b.plan.name}"] * len(b.groups)
+                names += ["fe_gradplanes" if b.group_family == 6 else f"fe_{b.plan.name}" + ("_mixed" if getattr(b, "fields_f32", False) else "")] * len(b.groups)
             else:
                 names += ["fe_einsum_generic"] * len(b.launches)
         return tuple(names)

@@ -78,6 +78,8 @@ extern "C" {
 #define FE_FAMILY_F32      0x100 /* or-ed into a family for fe_launch / fe_time_launches: the float32 launch (fe_launch_f32) */
 #define FE_FAMILY_ACC      0x200 /* or-ed into a family for fe_launch / fe_time_launches: out <- alpha * E + beta * out
                                   * (face-mass, grad, div; float64 only) */
+#define FE_FAMILY_FIELDS_F32 0x400 /* or-ed into FE_FAMILY_GRAD / DIV / FACEMASS: float32 fields, everything else float64
+                                    * (fe_grad3d_mixed_f64 / fe_div3d_mixed_f64 / fe_facemass_mixed_f64) */
 
 /* face-mass operand layouts (bit flags) */
 #define FE_FM_J_EF   0  /* J[E][nf]      (test_loopy_utils.py:41)            */
@@ -417,8 +419,30 @@ typedef struct fe_argpack {
  * family | FE_FAMILY_F32 is fe_launch_f32.  family | FE_FAMILY_ACC accumulates with the pack's alpha and beta (ignored
  * without the bit): FACEMASS is fe_facemass_acc_f64 on v / outs; GRAD and DIV are fe_grad3d_acc_f64 / fe_div3d_acc_f64
  * once per field k < b on v[k], outs[k], stopping at the first error; any other family, and FE_FAMILY_ACC together with
- * FE_FAMILY_F32, is FE_EUNSUPPORTED.  A null pack and an unknown family are FE_EINVAL. */
+ * FE_FAMILY_F32, is FE_EUNSUPPORTED.  family | FE_FAMILY_FIELDS_F32: fe_grad3d_mixed_f64 / fe_div3d_mixed_f64 /
+ * fe_facemass_mixed_f64 (below).
+ * A null pack and an unknown family are FE_EINVAL. */
 int fe_launch(int32_t family, const fe_argpack* args, void* stream);
+
+/* Float32 FIELDS in float64 grad, div and face-mass (feinsum_amd/csrc/fe_mixed.h): v[k] are float32 arrays (grad: u_k[E][Np],
+ * div: u_k[3][E][Np], face-mass: v_k[nf][E][Nfp]), J, the operator and the outputs float64, layouts and `layout_flags` as
+ * fe_grad3d_f64_ex / fe_div3d_f64_ex / fe_facemass_f64.  A field value is widened as it is read (exact); every product and sum is float64 on the matrix cores, in
+ * the order of the float64 kernels, and nothing is narrowed.  Results do not depend on where the arrays lie.
+ * Tetrahedra p = 1..4 (Np = 4, 10, 20, 35; face-mass nf = 4, Nfp = 3, 6, 10, 15), any b >= 1, any E; anything else is
+ * FE_EUNSUPPORTED.  A field pointer must be 4-byte, every other pointer 8-byte aligned (FE_EINVAL before any device work).
+ * The fields of a launch come by 16-byte LDS-DMA when every field (div: every plane x E Np; face-mass: every face slab
+ * f E Nfp) starts on an 8-byte boundary, and through 4-byte register loads otherwise (fe_last_launch_info `kind` bits 32: float32 fields,
+ * 64: the register-load form).  Asynchronous on `stream`; E = 0 launches nothing.  (The table `v` is spelled
+ * `const void* const*`: its entries are `const float*`.)
+ * fe_launch(FE_FAMILY_GRAD / FE_FAMILY_DIV / FE_FAMILY_FACEMASS | FE_FAMILY_FIELDS_F32, ...) call these with
+ * the pack's field pointers (u / out when v / outs are null and b <= 1) read as float; the bit on any other family, or
+ * together with FE_FAMILY_F32 or FE_FAMILY_ACC, is FE_EUNSUPPORTED. */
+int fe_grad3d_mixed_f64(const double* J, const double* D, const void* const* v, double* const* outs,
+                        int64_t E, int32_t Np, int32_t b, int32_t layout_flags, void* stream);
+int fe_div3d_mixed_f64(const double* J, const double* D, const void* const* v, double* const* outs,
+                       int64_t E, int32_t Np, int32_t b, int32_t layout_flags, void* stream);
+int fe_facemass_mixed_f64(const double* J, const double* R, const void* const* v, double* const* outs,
+                          int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream);
 
 /* float32 operands (the reference validates float32 einsums at 1e-6 and carries float32 peaks:
  * src/feinsum/measure.py:178-192, src/feinsum/data/device_info.py:5-26).  One entry point for the families
