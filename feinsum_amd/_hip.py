@@ -124,6 +124,9 @@ SIGNATURES = {
     "fe_grad3d_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _p]),
     "fe_div3d_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _p]),
     "fe_facemass_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_grad3d_strided_f64": (_int, [_p, _i64, _p, _pp, _pp, _i64, _i64, _i32, _i32, _i32, _p]),
+    "fe_div3d_strided_f64": (_int, [_p, _i64, _p, _pp, _i64, _pp, _i64, _i32, _i32, _i32, _p]),
+    "fe_facemass_strided_f64": (_int, [_p, _i64, _p, _pp, _i64, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
     "fe_launch_f32": (_int, [_i32, C.POINTER(ArgPack), _p]),
     "fe_set_tail_rounds": (_int, [_i32]),
     "fe_set_tail_min_rounds": (_int, [_i32]),
@@ -330,6 +333,33 @@ def grad3d_acc(J: int, D: int, u: int, out: int, E: int, Np: int, alpha: float, 
     """``out <- alpha * grad(u) + beta * out`` inside the matrix-core kernel (fe_grad3d_acc_f64).  NotImplementedError: the
     order has no accumulating kernel (tetrahedra p = 1..4)."""
     check(load_library().fe_grad3d_acc_f64(J, D, u, out, E, Np, op_flags, float(alpha), float(beta), stream))
+
+
+def grad3d_strided(J: int, ldJ: int, D: int, u: Sequence[int], out: Sequence[int], ldOut: int, E: int, Np: int,
+                   op_flags: int = 0, stream: int = 0) -> None:
+    """grad on an element slice of larger arrays (fe_grad3d_strided_f64): ``E`` elements, the rows of J ``ldJ`` and the
+    output planes ``ldOut * Np`` doubles apart.  Every pointer addresses element 0 of the slice."""
+    if len(u) != len(out):
+        raise InvalidParameterError("grad: need as many outputs as fields")
+    check(load_library().fe_grad3d_strided_f64(J, ldJ, D, _ptr_array(u), _ptr_array(out), ldOut, E, Np, len(u), op_flags, stream))
+
+
+def div3d_strided(J: int, ldJ: int, D: int, u: Sequence[int], ldIn: int, out: Sequence[int], E: int, Np: int,
+                  op_flags: int = 0, stream: int = 0) -> None:
+    """div on an element slice (fe_div3d_strided_f64): the planes of every field ``ldIn * Np`` doubles apart."""
+    if len(u) != len(out):
+        raise InvalidParameterError("div: need as many outputs as fields")
+    check(load_library().fe_div3d_strided_f64(J, ldJ, D, _ptr_array(u), ldIn, _ptr_array(out), E, Np, len(u), op_flags, stream))
+
+
+def facemass_strided(J: int, ldJ: int, R: int, v: Sequence[int], ldIn: int, out: Sequence[int], E: int, Np: int, nf: int,
+                     Nfp: int, layout_flags: int = 0, stream: int = 0) -> None:
+    """face-mass on an element slice (fe_facemass_strided_f64): the face slabs of every field ``ldIn * Nfp`` doubles apart,
+    the rows of a J stored ``fe`` ``ldJ``.  NotImplementedError: one field, or a shape without a matrix-core kernel."""
+    if len(v) != len(out):
+        raise InvalidParameterError("face-mass: need as many outputs as fields")
+    check(load_library().fe_facemass_strided_f64(J, ldJ, R, _ptr_array(v), ldIn, _ptr_array(out), E, Np, nf, Nfp, len(v),
+                                                 layout_flags, stream))
 
 
 def div3d_acc(J: int, D: int, u: int, out: int, E: int, Np: int, alpha: float, beta: float, op_flags: int = 0,
@@ -640,6 +670,7 @@ def last_launch_info() -> dict:
     d["staggered_start"] = bool(d["kind"] & 16)
     d["mixed_fields"] = bool(d["kind"] & 32)             # fe_grad3d_mixed_f64 / fe_div3d_mixed_f64 / fe_facemass_mixed_f64
     d["plain_field_loads"] = bool(d["kind"] & 64)        # ... with the fields through registers instead of LDS-DMA
+    d["element_slice"] = bool(d["kind"] & 128)           # fe_grad3d_strided_f64 / fe_div3d_strided_f64 / fe_facemass_strided_f64
     d["kind"] = "B build interleaved" if d["kind"] & 4 else "default"
     return d
 

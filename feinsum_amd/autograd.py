@@ -262,5 +262,11 @@ def evaluate_differentiable(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[st
     missing = [n for n in names if n not in arg_dict]
     if missing:
         raise InvalidParameterError(f"missing input arrays: {missing}")
+    # (element slices, measure.ELEMENT_SLICE_RULE: the adjoint kernels take whole arrays only -- refused up front, before the
+    #  forward pass could accept them)
+    strided = [n for n in names if hasattr(arg_dict[n], "is_contiguous") and not arg_dict[n].is_contiguous()]
+    if strided:
+        raise InvalidParameterError(f"evaluate_differentiable: argument '{strided[0]}' must be C-contiguous (the adjoint kernels "
+                                    "do not take element slices; differentiate .contiguous() copies)")
     outs = _FN.apply(_Spec(einsum, names, q, transform, schedule, operator_gradients), *[arg_dict[n] for n in names])
     return MappingProxyType(dict(zip(einsum.output_names, outs)))

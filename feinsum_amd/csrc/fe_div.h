@@ -51,6 +51,43 @@
 
 namespace fe {
 
+// element slices (kLd, div3d_mfma_body): entry (e, i) as div3d_item (fe_generic.h) computes it -- the same products in the same
+// order -- with row k of J at J + k ldJ and plane x of the field at u + x ldIn Np.  A function of its own, so that the plain one
+// and every kernel it is inlined into stay as they are.
+__device__ __forceinline__ void div3d_item_ld(const double* __restrict__ J, const double* __restrict__ D,
+                                              const double* __restrict__ u, double* __restrict__ out, int64_t ldJ,
+                                              int64_t ldIn, int Np, int64_t e, int i, int opT) {
+    double jac[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) jac[k] = J[(int64_t)k * ldJ + e];
+    const double* u0 = u + ((int64_t)0 * ldIn + e) * Np;
+    const double* u1 = u + ((int64_t)1 * ldIn + e) * Np;
+    const double* u2 = u + ((int64_t)2 * ldIn + e) * Np;
+    const int si = opT ? 1 : Np, sj = opT ? Np : 1;   // opT: D stored as [r][j][i]
+    const double* d0 = D + (int64_t)0 * Np * Np + (int64_t)i * si;
+    const double* d1 = D + (int64_t)1 * Np * Np + (int64_t)i * si;
+    const double* d2 = D + (int64_t)2 * Np * Np + (int64_t)i * si;
+    double acc = 0.0;
+#pragma unroll 5
+    for (int j = 0; j < Np; ++j) {
+        const double a = u0[j], b = u1[j], c = u2[j];
+        const double ju0 = jac[0] * a + jac[3] * b + jac[6] * c;
+        const double ju1 = jac[1] * a + jac[4] * b + jac[7] * c;
+        const double ju2 = jac[2] * a + jac[5] * b + jac[8] * c;
+        acc += d0[j * sj] * ju0 + d1[j * sj] * ju1 + d2[j * sj] * ju2;
+    }
+    out[e * Np + i] = acc;
+}
+
+// fewer elements than a wave tile of an element slice (fe_div3d_strided_f64)
+__global__ __launch_bounds__(256) void div3d_generic_ld_kernel(
+    const double* __restrict__ J, const double* __restrict__ D, const double* __restrict__ u,
+    double* __restrict__ out, int64_t E, int64_t ldJ, int64_t ldIn, int Np, int opT) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= E * Np) return;
+    div3d_item_ld(J, D, u, out, ldJ, ldIn, Np, idx / Np, (int)(idx % Np), opT);
+}
+
 #ifdef FE_EXPERIMENTS
 // Diagnostic build only: per wave of the eight-wave p = 5 kernels {shader cycles waiting for the tile, in the MFMA
 // phase, in the epilogue; tiles done; HW_ID; 100 MHz stamps of loop start and end}.
@@ -133,12 +170,14 @@ struct DivGeom {
 // own wait in front of their first use (it does not see the LDS-DMA prefetch and waits for that too, as in fe_facemass.h).
 // With beta == 0 nothing is read: one scalar branch per unit.  The remainder code accumulates alike.
 template <int NP, int M, int kDbg = 0, int MODE = 0, int ND = 3, bool ALDS = false, bool W8 = false, bool kPrep = false,
-          bool kDyn = false, bool kIlv = false, bool kAcc = false>
+          bool kDyn = false, bool kIlv = false, bool kAcc = false, bool kLd = false>
 __device__ __forceinline__ void div3d_mfma_body(
     const double* __restrict__ J, const double* __restrict__ D, const void* __restrict__ prep, const FieldPtrs& P,
     int nb, int64_t E, int64_t nTiles, int op_flags, int jes, const unsigned bid, const unsigned nblk,
     const GradFields* __restrict__ Q = nullptr, unsigned* __restrict__ tail = nullptr, int64_t t_static = 0,
-    const double alpha = 1.0, const double beta = 0.0) {
+    const double alpha = 1.0, const double beta = 0.0, const int64_t ldJ = 0, const int64_t ldIn = 0) {
+    static_assert(!kLd || (MODE == 0 && ND == 3 && !ALDS && !W8 && !kPrep && !kIlv && !kAcc && kDbg == 0),
+                  "element slices: plain div of tetrahedra, register fragments, B fragments up front");
     static_assert(!kAcc || (MODE == 0 && ND == 3 && !ALDS && !W8 && !kPrep && !kDyn && !kIlv && kDbg == 0),
                   "accumulating launches: plain div of tetrahedra, register fragments, static walk, B fragments up front");
     static_assert(!kPrep || (!ALDS && MODE == 0 && ND == 3), "prepared operators: plain div of tetrahedra");
@@ -182,7 +221,8 @@ __device__ __forceinline__ void div3d_mfma_body(
             for (int k = 0; k < nb; ++k) {
                 const double* uk = field_in(P, k);
                 double* ok = field_out(P, k);
-                if (MODE == 0 && ND == 3) div3d_item<kAcc>(J, Dsrc, uk, ok, E, NP, e, i, opT, alpha, beta);
+                if constexpr (kLd) div3d_item_ld(J, Dsrc, uk, ok, ldJ, ldIn, NP, e, i, opT);
+                else if (MODE == 0 && ND == 3) div3d_item<kAcc>(J, Dsrc, uk, ok, E, NP, e, i, opT, alpha, beta);
                 else if (MODE == 0) div_nd_item(J, Dsrc, uk, ok, E, NP, ND, e, i, opT);
                 else if (MODE == 4) grad_nd_item(J, Dsrc, uk, ok, E, NP, ND, e, i, opT);
                 else if (MODE == 5) {
@@ -240,7 +280,9 @@ __device__ __forceinline__ void div3d_mfma_body(
         if (tload) {   // (fe_common.h, kOpLoadsTemporal: one scalar branch for the whole unit)
 #pragma unroll
             for (int x = 0; x < (x_one_plane ? 1 : G::NPLANES); ++x) {   // (x_one_plane, experiments build: timing, wrong results)
-                const char* up = ub + (int64_t)x * E * (NP * 8);
+                const char* up;   // (kLd: see grad3d_mfma_body)
+                if constexpr (kLd) up = ub + (int64_t)x * ldIn * (NP * 8);
+                else up = ub + (int64_t)x * E * (NP * 8);
 #pragma unroll
                 for (int c = 0; c < G::P_INSTR; ++c)
                     if ((c + 1) * 64 <= G::P_CHUNKS || c * 64 + lane < G::P_CHUNKS)
@@ -249,7 +291,9 @@ __device__ __forceinline__ void div3d_mfma_body(
         } else {
 #pragma unroll
             for (int x = 0; x < G::NPLANES; ++x) {
-                const char* up = ub + (int64_t)x * E * (NP * 8);
+                const char* up;   // (kLd: see grad3d_mfma_body)
+                if constexpr (kLd) up = ub + (int64_t)x * ldIn * (NP * 8);
+                else up = ub + (int64_t)x * E * (NP * 8);
 #pragma unroll
                 for (int c = 0; c < G::P_INSTR; ++c)
                     if ((c + 1) * 64 <= G::P_CHUNKS || c * 64 + lane < G::P_CHUNKS)
@@ -269,7 +313,8 @@ __device__ __forceinline__ void div3d_mfma_body(
                 src = reinterpret_cast<const char*>((x == 0 ? Q->j[0] : x == 1 ? Q->j[1] : Q->j[2]) + (int64_t)r * E + e0) +
                       col * 16;
             } else {
-                src = (MODE == 1 && jes) ? jb + e0 * (8 * (ND - 1)) + q * 16 : jb + ((int64_t)row * E) * 8 + col * 16;
+                if constexpr (kLd) src = jb + ((int64_t)row * ldJ) * 8 + col * 16;
+                else src = (MODE == 1 && jes) ? jb + e0 * (8 * (ND - 1)) + q * 16 : jb + ((int64_t)row * E) * 8 + col * 16;
             }
             if ((c + 1) * 64 <= G::J_CHUNKS || q < G::J_CHUNKS) glds16(src, lds_j + c * 1024);
         }
@@ -1371,6 +1416,25 @@ __global__ __launch_bounds__(256, 2) void div3d_mfma_acc_kernel(
     double beta) {
     div3d_mfma_body<NP, M, 0, 0, 3, false, false, false, false, false, true>(J, D, nullptr, P, 1, E, nTiles, opT, 0, blockIdx.x,
                                                                              gridDim.x, nullptr, nullptr, 0, alpha, beta);
+}
+
+// div on an element slice of larger arrays (fe_div3d_strided_f64; div3d_mfma_body, kLd): E elements, the rows of J ldJ and the
+// planes of every field ldIn Np doubles apart; any number of fields, static walk, all B fragments up front
+template <int NP, int M>
+__global__ __launch_bounds__(256, 2) void div3d_mfma_strided_kernel(
+    const double* __restrict__ J, const double* __restrict__ D, FieldPtrs P, int nb, int64_t E, int64_t ldJ, int64_t ldIn,
+    int64_t nTiles, int opT) {
+    div3d_mfma_body<NP, M, 0, 0, 3, false, false, false, false, false, false, true>(J, D, nullptr, P, nb, E, nTiles, opT, 0, blockIdx.x,
+                                                                                     gridDim.x, nullptr, nullptr, 0, 1.0, 0.0, ldJ, ldIn);
+}
+
+// ... with a dynamic walk (fe_common.h); the number of fields is a run-time argument
+template <int NP, int M>
+__global__ __launch_bounds__(256, 2) FE_TAIL_KERNEL_ATTR void div3d_mfma_strided_tail_kernel(
+    const double* __restrict__ J, const double* __restrict__ D, FieldPtrs P, int nb, int64_t E, int64_t ldJ, int64_t ldIn,
+    int64_t nTiles, int opT, unsigned* __restrict__ tail, int64_t t_static) {
+    div3d_mfma_body<NP, M, 0, 0, 3, false, false, false, true, false, false, true>(J, D, nullptr, P, nb, E, nTiles, opT, 0, blockIdx.x,
+                                                                                    gridDim.x, nullptr, tail, t_static, 1.0, 0.0, ldJ, ldIn);
 }
 
 // the plain single-field div with a dynamic walk (see fe_common.h)

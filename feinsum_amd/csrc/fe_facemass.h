@@ -65,11 +65,12 @@ struct FmGeom {
 };
 
 // UNIT_LOADS x 16-byte LDS-DMA for the field slabs (+ J_INSTR for J at a tile start).
-template <int NP, int NFP, int M, bool kWithJ, int NF = kFmNf, bool ALDS = false, bool W8 = false>
+// kLd (element slices, facemass_mfma_body): E is the slab distance ldIn, and the rows of J stored [nf][..] are ldJ apart
+template <int NP, int NFP, int M, bool kWithJ, int NF = kFmNf, bool ALDS = false, bool W8 = false, bool kLd = false>
 __device__ __forceinline__ void fm_issue_unit_loads(const double* __restrict__ J,
                                                     const double* __restrict__ vk, int64_t E,
                                                     int64_t tile, int lane, unsigned lds_v,
-                                                    unsigned lds_j, int jfe) {
+                                                    unsigned lds_j, int jfe, int64_t ldJ = 0) {
     using G = FmGeom<NP, NFP, M, NF, ALDS, W8>;
     const int64_t e0 = tile * G::TEL;
     const char* vb = reinterpret_cast<const char*>(vk) + e0 * (NFP * 8) + lane * 16;
@@ -99,8 +100,10 @@ __device__ __forceinline__ void fm_issue_unit_loads(const double* __restrict__ J
         for (int c = 0; c < G::J_INSTR; ++c) {
             const int q = c * 64 + lane;                       // 16-byte chunk of the J tile
             const int row = q / (G::TEL / 2), col = q - row * (G::TEL / 2);   // "fe": 4 rows of TEL doubles
-            const char* src = jfe ? jb + ((int64_t)row * E + e0) * 8 + col * 16
-                                  : jb + e0 * (NF * 8) + q * 16;
+            const char* src;   // (kLd: see grad3d_mfma_body)
+            if constexpr (kLd) src = jfe ? jb + ((int64_t)row * ldJ + e0) * 8 + col * 16 : jb + e0 * (NF * 8) + q * 16;
+            else src = jfe ? jb + ((int64_t)row * E + e0) * 8 + col * 16
+                           : jb + e0 * (NF * 8) + q * 16;
             if ((c + 1) * 64 <= G::J_CHUNKS || q < G::J_CHUNKS) glds16(src, lds_j + c * 1024);
         }
     }
@@ -121,11 +124,18 @@ __device__ __forceinline__ void fm_issue_unit_loads(const double* __restrict__ J
 // counted wait at the top of a unit counts them (ACC_LOADS) among the operations younger than the unit's own loads.  With
 // beta == 0 nothing is read: one scalar branch per unit.  The remainder code accumulates alike.
 template <int NP, int NFP, int M, int NB, int NF = kFmNf, bool ALDS = false, bool W8 = false, bool kPrep = false,
-          bool kDyn = false, bool kAcc = false>
+          bool kDyn = false, bool kAcc = false, bool kLd = false>
 __device__ __forceinline__ void facemass_mfma_body(
     const double* __restrict__ J, const double* __restrict__ R, const void* __restrict__ prep, const FieldPtrs& P,
     int64_t E, int64_t nTiles, int jfe_flags, int rlayout, const unsigned bid, const unsigned nblk,
-    unsigned* __restrict__ tail = nullptr, int64_t t_static = 0, const double alpha = 1.0, const double beta = 0.0) {
+    unsigned* __restrict__ tail = nullptr, int64_t t_static = 0, const double alpha = 1.0, const double beta = 0.0,
+    const int64_t ldJ = 0, const int64_t ldIn = 0) {
+    static_assert(!kLd || (!ALDS && !W8 && !kPrep && !kAcc), "element slices: register fragments, the plain operator");
+    // (kLd: the slabs are ldIn and the rows of J stored [nf][..] ldJ apart.  FM_ISSUE keeps the call the other instantiations always
+    //  made behind its `else`, unchanged: see grad3d_mfma_body)
+#define FM_ISSUE(WITHJ, VK, TILE, LDSV, LDSJ)                                                                                  \
+    if constexpr (kLd) fm_issue_unit_loads<NP, NFP, M, WITHJ, NF, ALDS, W8, true>(J, VK, ldIn, TILE, lane, LDSV, LDSJ, jfe_flags, ldJ); \
+    else fm_issue_unit_loads<NP, NFP, M, WITHJ, NF, ALDS, W8>(J, VK, E, TILE, lane, LDSV, LDSJ, jfe_flags)
     const int jfe = jfe_flags & 1;   // J stored [nf][E]; bit kOpLoadsTemporal: the field slabs by plain loads (fe_common.h)
     static_assert(!kPrep || !ALDS, "prepared operators: fragments in registers");
     static_assert(!kAcc || (!ALDS && !W8 && !kPrep && !kDyn), "accumulating launches: register fragments, static walk");
@@ -162,7 +172,8 @@ __device__ __forceinline__ void facemass_mfma_body(
         const int rI = rlayout == 0 ? NFP : rlayout == 1 ? NF * NFP : 1;
         const int rJ = rlayout == 0 || rlayout == 1 ? 1 : rlayout == 2 ? NP : NF * NP;
         remainder_items(nTiles * G::TEL, E, NP, bid, nblk, [&](int64_t e, int i) {
-            facemass_item<NB, kAcc>(J, Rsrc, P, E, NP, NF, NFP, jEs, jFs, rF, rI, rJ, e, i, alpha, beta);
+            if constexpr (kLd) facemass_item<NB>(J, Rsrc, P, ldIn, NP, NF, NFP, jEs, jfe ? ldJ : (int64_t)1, rF, rI, rJ, e, i);
+            else facemass_item<NB, kAcc>(J, Rsrc, P, E, NP, NF, NFP, jEs, jFs, rF, rI, rJ, e, i, alpha, beta);
         });
     };
     bool first_requested = false;   // (units 0 and 1 of this wave's first tile: see the staged prologue)
@@ -184,8 +195,8 @@ __device__ __forceinline__ void facemass_mfma_body(
             const int64_t first_ = (int64_t)bid * G::WAVES + wave;
             if (wave * (int)sizeof(WaveLds) >= G::OP_D * 8 && first_ < nTiles) {
                 const unsigned lv = lds_addr_uniform(L->v[0]), lj = lds_addr_uniform(L->j);
-                fm_issue_unit_loads<NP, NFP, M, true, NF, ALDS, W8>(J, P.v[0], E, first_, lane, lv, lj, jfe_flags);
-                fm_issue_unit_loads<NP, NFP, M, false, NF, ALDS, W8>(J, P.v[1], E, first_, lane, lv + G::UNIT_D * 8, lj, jfe_flags);
+                FM_ISSUE(true, P.v[0], first_, lv, lj);
+                FM_ISSUE(false, P.v[1], first_, lv + G::UNIT_D * 8, lj);
                 first_requested = true;
             }
         }
@@ -246,7 +257,7 @@ __device__ __forceinline__ void facemass_mfma_body(
     if constexpr (W8) {
         // ---- eight waves per block: wait the unit -> B to registers -> MFMAs -> o through the slab
         //      buffer -> stores -> request the next unit
-        fm_issue_unit_loads<NP, NFP, M, true, NF, ALDS, W8>(J, P.v[0], E, first, lane, lds_v0, lds_j, jfe_flags);
+        FM_ISSUE(true, P.v[0], first, lds_v0, lds_j);
         double jv8[G::KS];
         // dynamic walk (fe_common.h): the ticket for the next tile is asked for with unit 0 (behind the vmcnt(0) at its top)
         // and read behind the last unit's stores, where the next tile's first unit is requested
@@ -319,7 +330,7 @@ __device__ __forceinline__ void facemass_mfma_body(
                 wave_lds_fence();
                 // ---- the next unit: the next field of this tile, or field 0 (and J) of the next tile
                 if (k + 1 < NB) {
-                    fm_issue_unit_loads<NP, NFP, M, false, NF, ALDS, W8>(J, P.v[(k + 1) % NB], E, tile, lane, lds_v0, lds_j, jfe_flags);
+                    FM_ISSUE(false, P.v[(k + 1) % NB], tile, lds_v0, lds_j);
                 } else {
                     if constexpr (kDyn) {
                         if (asked8) {   // younger than the request by now: this unit's stores (every unit starts with vmcnt(0))
@@ -331,7 +342,7 @@ __device__ __forceinline__ void facemass_mfma_body(
                             }
                         }
                     }
-                    if (nt < tEnd) fm_issue_unit_loads<NP, NFP, M, true, NF, ALDS, W8>(J, P.v[0], E, nt, lane, lds_v0, lds_j, jfe_flags);
+                    if (nt < tEnd) FM_ISSUE(true, P.v[0], nt, lds_v0, lds_j);
                 }
             }
             tile = nt;
@@ -351,8 +362,8 @@ __device__ __forceinline__ void facemass_mfma_body(
 
     // prologue: units 0 and 1 of the first tile (unless requested in front of the fragment build)
     if (!first_requested) {
-        fm_issue_unit_loads<NP, NFP, M, true, NF, ALDS, W8>(J, P.v[0], E, first, lane, lds_v0, lds_j, jfe_flags);
-        fm_issue_unit_loads<NP, NFP, M, false, NF, ALDS, W8>(J, P.v[1], E, first, lane, lds_v0 + G::UNIT_D * 8, lds_j, jfe_flags);
+        FM_ISSUE(true, P.v[0], first, lds_v0, lds_j);
+        FM_ISSUE(false, P.v[1], first, lds_v0 + G::UNIT_D * 8, lds_j);
     }
     if constexpr (kPrep) prepared_fragments_landed();
 
@@ -452,11 +463,9 @@ __device__ __forceinline__ void facemass_mfma_body(
                 const int64_t tile2 = (k + 2 < NB) ? tile : nt;
                 if (tile2 < tEnd) {
                     if (k2 == 0)
-                        fm_issue_unit_loads<NP, NFP, M, true, NF, ALDS, W8>(J, P.v[k2], E, tile2, lane,
-                                                              lds_v0 + slot * (G::UNIT_D * 8), lds_j, jfe_flags);
+                        FM_ISSUE(true, P.v[k2], tile2, lds_v0 + slot * (G::UNIT_D * 8), lds_j);
                     else
-                        fm_issue_unit_loads<NP, NFP, M, false, NF, ALDS, W8>(J, P.v[k2], E, tile2, lane,
-                                                               lds_v0 + slot * (G::UNIT_D * 8), lds_j, jfe_flags);
+                        FM_ISSUE(false, P.v[k2], tile2, lds_v0 + slot * (G::UNIT_D * 8), lds_j);
                 }
             }
 
@@ -525,6 +534,8 @@ __device__ __forceinline__ void facemass_mfma_body(
     }
 }
 
+#undef FM_ISSUE
+
 // eight-wave blocks with the fragments in LDS (p = 5) with a dynamic walk
 template <int NP, int NFP, int NB>
 __global__ __launch_bounds__(512, 1) FE_TAIL_KERNEL_ATTR void facemass_w8_tail_kernel(
@@ -550,6 +561,35 @@ __global__ __launch_bounds__(256, 2) void facemass_mfma_acc_kernel(
     double alpha, double beta) {
     facemass_mfma_body<NP, NFP, M, NB, kFmNf, false, false, false, false, true>(J, R, nullptr, P, E, nTiles, jfe, rlayout,
                                                                                 blockIdx.x, gridDim.x, nullptr, 0, alpha, beta);
+}
+
+// fewer elements than a wave tile of an element slice (fe_facemass_strided_f64): entry by entry, as facemass_generic_kernel
+template <int NB>
+__global__ __launch_bounds__(256) void facemass_generic_ld_kernel(
+    const double* __restrict__ J, const double* __restrict__ R, FieldPtrs P, int64_t E, int64_t ldIn, int Np, int nf, int Nfp,
+    int64_t jEs, int64_t jFs, int rF, int rI, int rJ) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= E * Np) return;
+    facemass_item<NB>(J, R, P, ldIn, Np, nf, Nfp, jEs, jFs, rF, rI, rJ, idx / Np, (int)(idx % Np));
+}
+
+// face-mass on an element slice of larger arrays (fe_facemass_strided_f64; facemass_mfma_body, kLd): E elements, the rows of J
+// stored [nf][..] ldJ and the face slabs of every field ldIn Nfp doubles apart; tetrahedra p = 1..4, 2..4 fields, static walk
+template <int NP, int NFP, int M, int NB>
+__global__ __launch_bounds__(256, 2) void facemass_mfma_strided_kernel(
+    const double* __restrict__ J, const double* __restrict__ R, FieldPtrs P, int64_t E, int64_t ldJ, int64_t ldIn, int64_t nTiles,
+    int jfe, int rlayout) {
+    facemass_mfma_body<NP, NFP, M, NB, kFmNf, false, false, false, false, false, true>(J, R, nullptr, P, E, nTiles, jfe, rlayout,
+                                                                                       blockIdx.x, gridDim.x, nullptr, 0, 1.0, 0.0, ldJ, ldIn);
+}
+
+// ... with a dynamic walk (fe_common.h): three or four fields
+template <int NP, int NFP, int M, int NB>
+__global__ __launch_bounds__(256, 2) FE_TAIL_KERNEL_ATTR void facemass_mfma_strided_tail_kernel(
+    const double* __restrict__ J, const double* __restrict__ R, FieldPtrs P, int64_t E, int64_t ldJ, int64_t ldIn, int64_t nTiles,
+    int jfe, int rlayout, unsigned* __restrict__ tail, int64_t t_static) {
+    facemass_mfma_body<NP, NFP, M, NB, kFmNf, false, false, false, true, false, true>(J, R, nullptr, P, E, nTiles, jfe, rlayout,
+                                                                                      blockIdx.x, gridDim.x, tail, t_static, 1.0, 0.0, ldJ, ldIn);
 }
 
 template <int NP, int NFP, int M, int NB, int NF = kFmNf, bool ALDS = false, bool W8 = false, bool kPrep = false>

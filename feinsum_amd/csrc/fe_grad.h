@@ -134,6 +134,39 @@ __device__ __forceinline__ void grad3d_item(const double* __restrict__ J, const 
             J[(int64_t)(x * 3 + 2) * E + e] * t2;
 }
 
+// element slices (kLd, grad3d_mfma_body): row x*3+r of J starts at J + (x*3+r) ldJ, plane x of the output at out + x ldOut Np.
+// A function of its own, so that the plain one and every kernel it is inlined into stay as they are; the same products in the same order.
+__device__ __forceinline__ void grad3d_item_ld(const double* __restrict__ J, const double* __restrict__ D,
+                                               const double* __restrict__ u, double* __restrict__ out, int64_t ldJ,
+                                               int64_t ldOut, int Np, int64_t e, int i, int opT) {
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+    const double* ue = u + e * Np;
+    const int si = opT ? 1 : Np, sj = opT ? Np : 1;
+    const double* d0 = D + (int64_t)0 * Np * Np + (int64_t)i * si;
+    const double* d1 = D + (int64_t)1 * Np * Np + (int64_t)i * si;
+    const double* d2 = D + (int64_t)2 * Np * Np + (int64_t)i * si;
+#pragma unroll 5
+    for (int j = 0; j < Np; ++j) {
+        const double uj = ue[j];
+        t0 += d0[j * sj] * uj;
+        t1 += d1[j * sj] * uj;
+        t2 += d2[j * sj] * uj;
+    }
+    for (int x = 0; x < 3; ++x)
+        out[((int64_t)x * ldOut + e) * Np + i] =
+            J[(int64_t)(x * 3 + 0) * ldJ + e] * t0 + J[(int64_t)(x * 3 + 1) * ldJ + e] * t1 +
+            J[(int64_t)(x * 3 + 2) * ldJ + e] * t2;
+}
+
+// fewer elements than a wave tile of an element slice (fe_grad3d_strided_f64)
+__global__ __launch_bounds__(256) void grad3d_generic_ld_kernel(
+    const double* __restrict__ J, const double* __restrict__ D, const double* __restrict__ u,
+    double* __restrict__ out, int64_t E, int64_t ldJ, int64_t ldOut, int Np, int opT) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= E * Np) return;
+    grad3d_item_ld(J, D, u, out, ldJ, ldOut, Np, idx / Np, (int)(idx % Np), opT);
+}
+
 // the accumulating form: out[x,e,i] = alpha * (that sum) + beta * out[x,e,i]; beta == 0 does not read the output
 // (axpby_combine, fe_common.h).  A function of its own, so that the plain one and every kernel it is inlined into stay as they are.
 __device__ __forceinline__ void grad3d_item_acc(const double* __restrict__ J, const double* __restrict__ D,
@@ -298,12 +331,16 @@ __device__ __forceinline__ void grad_load_old(const double* op, int lane, v2d (&
 // L(unit + 1) | [O S](plane 0) [O S](plane 1) [O S](plane 2), all of it younger than L(unit + 1): the counted waits at the top of
 // the next unit count the ACC_LOADS old-value loads beside the stores, under the wave-uniform beta != 0 branch.  With beta == 0
 // nothing is read.  The remainder code accumulates alike.
-template <int NP, int M, int kDbg = 0, bool kPlain = true, bool kPrep = false, bool kDyn = false, bool kAcc = false>
+template <int NP, int M, int kDbg = 0, bool kPlain = true, bool kPrep = false, bool kDyn = false, bool kAcc = false, bool kLd = false>
 __device__ __forceinline__ void grad3d_mfma_body(
     const GradFields& P, const double* __restrict__ D, const void* __restrict__ prep, int nb, int nx_, int64_t E,
     int64_t nTiles, int op_flags, const unsigned bid, const unsigned nblk, unsigned* __restrict__ tail = nullptr,
-    int64_t t_static = 0, const double alpha = 1.0, const double beta = 0.0) {
+    int64_t t_static = 0, const double alpha = 1.0, const double beta = 0.0, const int64_t ldJ = 0, const int64_t ldOut = 0) {
     static_assert(!kDyn || (kPlain && !kPrep), "dynamic walk: plain launches of one field");
+    static_assert(!kLd || (kPlain && !kPrep && !kAcc && kDbg == 0), "element slices: plain grad, the plain operator");
+    // (kLd: the plane distances are ldJ / ldOut instead of E.  Every statement that forms such an address stands twice, under
+    //  `if constexpr (kLd)` and, unchanged, behind its `else`: the other instantiations then compile the text they always had --
+    //  nothing new is captured by a lambda or computed -- and keep their device code)
     static_assert(!kAcc || (kPlain && !kPrep && !kDyn && kDbg == 0), "accumulating launches: plain grad, static walk, the plain operator");
     constexpr bool kAccAhead = kAcc && NP != 35;
     const bool acc_reads = kAcc && beta != 0.0;   // wave-uniform (a kernel argument)
@@ -317,7 +354,7 @@ __device__ __forceinline__ void grad3d_mfma_body(
 #ifdef FE_EXPERIMENTS
     const unsigned long long t_entry = (kDbg & 32) ? __builtin_amdgcn_s_memrealtime() : 0;
 #endif
-    if constexpr (kPlain && !kPrep && !kDyn && M == 1 && !kAcc) {   // (fe_common.h: every second CU of an XCD starts half a tile period late)
+    if constexpr (kPlain && !kPrep && !kDyn && M == 1 && !kAcc && !kLd) {   // (fe_common.h: every second CU of an XCD starts half a tile period late)
         if ((op_flags & kOpStaggeredStart) && ((bid >> 3) & 1))
             for (int i = 0; i < kStaggerSleeps; ++i) __builtin_amdgcn_s_sleep(16);
     }
@@ -352,7 +389,7 @@ __device__ __forceinline__ void grad3d_mfma_body(
     // Same products in the same order as a full tile: bitwise the same results.
     int64_t q_e0 = -1;            // first element of this wave's quarter tile, or -1
     int64_t t_full = nTiles;      // tiles walked as full tiles
-    if constexpr (kPlain && !kPrep && M == 1 && !kAcc) {
+    if constexpr (kPlain && !kPrep && M == 1 && !kAcc && !kLd) {
         if ((op_flags & kOpQuarterTail) && nb == 1 && !(kDyn && tail != nullptr)) {
             const int64_t r = nTiles % stride;
             if (r > 0 && 4 * r <= stride && nTiles > stride) {   // (what is possible; the launcher sets the flag by its own, narrower rule)
@@ -378,7 +415,8 @@ __device__ __forceinline__ void grad3d_mfma_body(
     auto issue_first_units = [&]() -> int {   // returns the number of vector-memory ops that may stay in flight
         if (!(tile < tEnd) || x_no_loads) return 0;
         grad_issue_u<NP, M, kNT>(P.u[0], phys(tile), lane, lds_addr_uniform(L->u[0]), tload);
-        grad_issue_j<NP, M, kPlain>(P, E, phys(tile), lane, lds_addr_uniform(L->j[0]));
+        if constexpr (kLd) grad_issue_j<NP, M, kPlain>(P, ldJ, phys(tile), lane, lds_addr_uniform(L->j[0]));
+        else grad_issue_j<NP, M, kPlain>(P, E, phys(tile), lane, lds_addr_uniform(L->j[0]));
         if (nb > 1) {
             grad_issue_u<NP, M, kNT>(P.u[1], phys(tile), lane, lds_addr_uniform(L->u[1]), tload);
             pre = true;
@@ -397,7 +435,8 @@ __device__ __forceinline__ void grad3d_mfma_body(
             for (int k = 0; k < nb; ++k) {
                 const double* uk = grad_field_u(P, k);
                 if (kPlain) {
-                    if constexpr (kAcc) grad3d_item_acc(P.j[0], Dsrc, uk, grad_plane_out(P, k, 0), E, NP, e, i, opT, alpha, beta);
+                    if constexpr (kLd) grad3d_item_ld(P.j[0], Dsrc, uk, grad_plane_out(P, k, 0), ldJ, ldOut, NP, e, i, opT);
+                    else if constexpr (kAcc) grad3d_item_acc(P.j[0], Dsrc, uk, grad_plane_out(P, k, 0), E, NP, e, i, opT, alpha, beta);
                     else grad3d_item(P.j[0], Dsrc, uk, grad_plane_out(P, k, 0), E, NP, e, i, opT);
                 } else {
                     double* const o[3] = {grad_plane_out(P, k, 0), grad_plane_out(P, k, 1), grad_plane_out(P, k, 2)};
@@ -418,8 +457,10 @@ __device__ __forceinline__ void grad3d_mfma_body(
         FE_TILE_STAMP(x_stamps, smem + G::LDS_BYTES, wave, lane, dbg_it, 0);   // this unit's loads have landed
         double* out_x[3];
         out_x[0] = grad_plane_out(P, fk, 0);
-        out_x[1] = kPlain ? out_x[0] + E * NP : grad_plane_out(P, fk, 1);
-        out_x[2] = kPlain ? out_x[0] + 2 * E * NP : grad_plane_out(P, fk, 2);
+        if constexpr (kLd) out_x[1] = out_x[0] + ldOut * NP;
+        else out_x[1] = kPlain ? out_x[0] + E * NP : grad_plane_out(P, fk, 1);
+        if constexpr (kLd) out_x[2] = out_x[0] + 2 * ldOut * NP;
+        else out_x[2] = kPlain ? out_x[0] + 2 * E * NP : grad_plane_out(P, fk, 2);
         int obuf = 0;
         const int64_t e0 = phys(tile_) * G::TEL;
         // kAcc: the old values of plane q = 3 m + x of the unit, in old.v[q & 1] (see the head of this function)
@@ -610,7 +651,8 @@ __device__ __forceinline__ void grad3d_mfma_body(
             }
             if (!pre) {
                 grad_issue_u<NP, M, kNT>(P.u[0], nxt, lane, lds_addr_uniform(L->u[buf ^ 1]), tload);
-                grad_issue_j<NP, M, kPlain>(P, E, nxt, lane, lds_addr_uniform(L->j[buf ^ 1]));
+                if constexpr (kLd) grad_issue_j<NP, M, kPlain>(P, ldJ, nxt, lane, lds_addr_uniform(L->j[buf ^ 1]));
+                else grad_issue_j<NP, M, kPlain>(P, E, nxt, lane, lds_addr_uniform(L->j[buf ^ 1]));
             }
         }
         // wait L(cur): younger are S(previous), the ticket / report, L(next)
@@ -680,7 +722,10 @@ __device__ __forceinline__ void grad3d_mfma_body(
         } else if (nt < tEnd) {
             if (!pre) grad_issue_u<NP, M, kNT>(grad_field_u(P, nk), phys(nt), lane, lds_addr_uniform(L->u[ub ^ 1]), tload);
             if (next_new_tile) {
-                if (!pre) grad_issue_j<NP, M, kPlain>(P, E, phys(nt), lane, lds_addr_uniform(L->j[jbuf ^ 1]));
+                if (!pre) {
+                    if constexpr (kLd) grad_issue_j<NP, M, kPlain>(P, ldJ, phys(nt), lane, lds_addr_uniform(L->j[jbuf ^ 1]));
+                    else grad_issue_j<NP, M, kPlain>(P, E, phys(nt), lane, lds_addr_uniform(L->j[jbuf ^ 1]));
+                }
                 if (x_no_stores || first) wait_vmcnt<G::LOADS>();
                 else if (kAcc && acc_reads) wait_vmcnt<G::LOADS + G::STORES + G::ACC_LOADS>();   // + the previous unit's old-value loads
                 else wait_vmcnt_planes<G::LOADS, G::PLANE_STORES>(nx);
@@ -889,7 +934,7 @@ __device__ __forceinline__ void grad3d_mfma_body(
         static_top();
         static_bottom(std::false_type{});
     }
-    if constexpr (kPlain && !kPrep && M == 1 && !kAcc) {
+    if constexpr (kPlain && !kPrep && M == 1 && !kAcc && !kLd) {
         if (q_e0 >= 0) {
             wait_vmcnt<G::STORES>();                         // younger than the quarter tile's loads: the last full tile's stores
             const double* ut = L->u[ub];
@@ -962,6 +1007,24 @@ __global__ __launch_bounds__(256, 2) void grad3d_mfma_acc_kernel(
     GradFields P, const double* __restrict__ D, int64_t E, int64_t nTiles, int opT, double alpha, double beta) {
     grad3d_mfma_body<NP, M, 0, true, false, false, true>(P, D, nullptr, 1, 3, E, nTiles, opT, blockIdx.x, gridDim.x, nullptr, 0,
                                                          alpha, beta);
+}
+
+// grad on an element slice of larger arrays (fe_grad3d_strided_f64; grad3d_mfma_body, kLd): E elements, the rows of J ldJ and the
+// output planes ldOut Np doubles apart; any number of fields, full tiles (no quarter tiles, no staggered start); static walk
+template <int NP, int M>
+__global__ __launch_bounds__(256, 2) void grad3d_mfma_strided_kernel(
+    GradFields P, const double* __restrict__ D, int nb, int64_t E, int64_t ldJ, int64_t ldOut, int64_t nTiles, int opT) {
+    grad3d_mfma_body<NP, M, 0, true, false, false, false, true>(P, D, nullptr, nb, 3, E, nTiles, opT, blockIdx.x, gridDim.x, nullptr, 0,
+                                                                1.0, 0.0, ldJ, ldOut);
+}
+
+// ... with a dynamic walk (fe_common.h); the number of fields is a run-time argument
+template <int NP, int M>
+__global__ __launch_bounds__(256, 2) FE_TAIL_KERNEL_ATTR void grad3d_mfma_strided_tail_kernel(
+    GradFields P, const double* __restrict__ D, int nb, int64_t E, int64_t ldJ, int64_t ldOut, int64_t nTiles, int opT,
+    unsigned* __restrict__ tail, int64_t t_static) {
+    grad3d_mfma_body<NP, M, 0, true, false, true, false, true>(P, D, nullptr, nb, 3, E, nTiles, opT, blockIdx.x, gridDim.x, tail, t_static,
+                                                               1.0, 0.0, ldJ, ldOut);
 }
 
 // the plain single-field launch with a dynamic tail (see fe_common.h)

@@ -986,6 +986,78 @@ int launch_div_acc(const double* J, const double* D, const fe::FieldPtrs& P, int
         [&](const Launch&) { return call(f, 0, J, D, P, E, nTiles, f, alpha, beta); });
 }
 
+// The launches on element slices (fe_grad3d_strided_f64, fe_div3d_strided_f64, fe_facemass_strided_f64; kLd in fe_grad.h,
+// fe_div.h, fe_facemass.h): E is the launch's element count -- tiles, grid, the footprint rules of the cache hints -- and the
+// plane distances of the arrays are arguments of their own.  The plain operator, full tiles; no write-through, quarter
+// tiles, staggered start, interleaved build or split walk (the kernels compile those forms out).  Walks as the contiguous
+// launchers: behind two static rounds the tiles come by tickets (grad, div; face-mass of three or more fields).
+template <int NP, int M>
+int launch_grad_strided(const fe::GradFields& P, const double* D, int nb, int64_t E, int64_t ldJ, int64_t ldOut, int opT,
+                        hipStream_t s, bool* launched) {
+    using G = fe::GradGeom<NP, M>;
+    const int64_t nTiles = E / G::TEL;   // full wave tiles; the launch covers the elements behind the last one too
+    *launched = nTiles > 0;
+    if (nTiles == 0) return FE_OK;
+    const int f = (opT ? 1 : 0) | temporal_flag((9 + (int64_t)nb * NP) * E * 8);
+    char what[96], tail_what[96];
+    snprintf(what, sizeof(what), "grad Np=%d M=%d, element slice", NP, M);
+    snprintf(tail_what, sizeof(tail_what), "grad Np=%d M=%d, element slice, dynamic walk", NP, M);
+    // behind two static rounds the tiles come by tickets, as in launch_grad (fe_common.h: dynamic walk)
+    return mfma_launch<fe::grad3d_mfma_strided_kernel<NP, M>, fe::grad3d_mfma_strided_tail_kernel<NP, M>>(
+        s, walk_tickets(nTiles), {G::WAVES, 256, G::LDS_BYTES, 2, 8 / G::WAVES}, what,
+        [&](const Launch&) { return call(f, 128, P, D, nb, E, ldJ, ldOut, nTiles, f); }, tail_what,
+        [&](const Launch& L) { return call(f, 128, P, D, nb, E, ldJ, ldOut, nTiles, f, L.tail, L.t_static[0]); });
+}
+
+template <int NP, int M>
+int launch_div_strided(const double* J, const double* D, const fe::FieldPtrs& P, int nb, int64_t E, int64_t ldJ, int64_t ldIn,
+                       int opT, hipStream_t s, bool* launched) {
+    using G = fe::DivGeom<NP, M>;
+    const int64_t nTiles = E / G::TEL;
+    *launched = nTiles > 0;
+    if (nTiles == 0) return FE_OK;
+    const int f = (opT ? 1 : 0) | temporal_flag((9 + 3 * (int64_t)nb * NP) * E * 8, kTemporalFloorDiv, kTemporalCapDivMib);
+    char what[96], tail_what[96];
+    snprintf(what, sizeof(what), "div Np=%d M=%d, element slice", NP, M);
+    snprintf(tail_what, sizeof(tail_what), "div Np=%d M=%d, element slice, dynamic walk", NP, M);
+    return mfma_launch<fe::div3d_mfma_strided_kernel<NP, M>, fe::div3d_mfma_strided_tail_kernel<NP, M>>(
+        s, walk_tickets(nTiles), {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, 8 / G::WAVES}, what,
+        [&](const Launch&) { return call(f, 128, J, D, P, nb, E, ldJ, ldIn, nTiles, f); }, tail_what,
+        [&](const Launch& L) { return call(f, 128, J, D, P, nb, E, ldJ, ldIn, nTiles, f, L.tail, L.t_static[0]); });
+}
+
+template <int NP, int NFP, int M, int NB>
+int launch_fm_strided_nb(const double* J, const double* R, const fe::FieldPtrs& P, int64_t E, int64_t ldJ, int64_t ldIn,
+                         int64_t nTiles, int jfe, int rifj, hipStream_t s) {
+    using G = fe::FmGeom<NP, NFP, M>;
+    jfe = (jfe ? 1 : 0) | temporal_flag((fe::kFmNf + (int64_t)NB * fe::kFmNf * NFP) * E * 8, kTemporalFloorFaceMass, kTemporalCapFaceMassMib);
+    char what[96], tail_what[96];
+    snprintf(what, sizeof(what), "face-mass Np=%d Nfp=%d M=%d b=%d, element slice", NP, NFP, M, NB);
+    const Geometry geo = {G::WAVES, G::THREADS, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
+    auto args = [&](const Launch&) { return call(jfe, 128, J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj); };
+    if constexpr (NB >= 3) {   // three or more fields: the dynamic walk, as in launch_fm_nb
+        snprintf(tail_what, sizeof(tail_what), "face-mass Np=%d M=%d b=%d, element slice, dynamic walk", NP, M, NB);
+        return mfma_launch<fe::facemass_mfma_strided_kernel<NP, NFP, M, NB>, fe::facemass_mfma_strided_tail_kernel<NP, NFP, M, NB>>(
+            s, walk_tickets(nTiles, true, NP == 35 && NB == 4), geo, what, args, tail_what,
+            [&](const Launch& L) { return call(jfe, 128, J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj, L.tail, L.t_static[0]); });
+    } else {
+        (void)tail_what;
+        return mfma_launch<fe::facemass_mfma_strided_kernel<NP, NFP, M, NB>>(s, walk_static(nTiles), geo, what, args);
+    }
+}
+
+template <int NP, int NFP, int M>
+int launch_fm_strided(const double* J, const double* R, const fe::FieldPtrs& P, int nb, int64_t E, int64_t ldJ, int64_t ldIn,
+                      int64_t nTiles, int jfe, int rifj, hipStream_t s) {
+    switch (nb) {
+        case 2: return launch_fm_strided_nb<NP, NFP, M, 2>(J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj, s);
+        case 3: return launch_fm_strided_nb<NP, NFP, M, 3>(J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj, s);
+        case 4: return launch_fm_strided_nb<NP, NFP, M, 4>(J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj, s);
+        default: break;
+    }
+    return fail(FE_EINVAL, "face-mass on an element slice: internal field grouping error (nb=%d)", nb);
+}
+
 // 'xre,rij,ej->xei' operands as grad-type planes: j[x] = J[x], out[k][x] = out_k[x]
 fe::GradFields grad_fields(const double* J, const double* const* u, double* const* out, int nb, int64_t E,
                            int Np) {
@@ -2352,6 +2424,157 @@ int fe_div3d_acc_f64(const double* J, const double* D, const double* u, double* 
     if (!launched) {
         hipLaunchKernelGGL(fe::div3d_generic_acc_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, u, out, E, Np,
                            (int64_t)0, opT, alpha, beta);
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+// ---- element slices of larger arrays: E elements, plane distances (leading dimensions) of their own.
+// the argument checks the three entry points share; everything here comes before any device work
+static int check_strided(const char* who, const void* J, const void* A, const void* const* in, const void* const* out, int64_t E,
+                         int32_t b, int64_t ldJ, bool ldJ_used, int64_t ldIn, bool ldIn_used, int64_t ldOut, bool ldOut_used) {
+    if (E < 0) return fail(FE_EINVAL, "%s: E must be >= 0 (got %lld)", who, (long long)E);
+    if (b < 1) return fail(FE_EINVAL, "%s: b=%d, need at least one field", who, b);
+    if (!in || !out) return fail(FE_EINVAL, "%s: null pointer table", who);
+    if ((ldJ_used && ldJ < E) || (ldIn_used && ldIn < E) || (ldOut_used && ldOut < E))
+        return fail(FE_EINVAL, "%s: a leading dimension is smaller than E = %lld (ldJ %lld, ldIn %lld, ldOut %lld)", who, (long long)E,
+                    (long long)ldJ, (long long)ldIn, (long long)ldOut);
+    const int64_t ld_max = (int64_t)1 << 40;
+    if ((ldJ_used && ldJ >= ld_max) || (ldIn_used && ldIn >= ld_max) || (ldOut_used && ldOut >= ld_max))
+        return fail(FE_EINVAL, "%s: leading dimension too large", who);
+    uintptr_t bits = reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(A);
+    for (int k = 0; k < b; ++k) bits |= reinterpret_cast<uintptr_t>(in[k]) | reinterpret_cast<uintptr_t>(out[k]);
+    if (bits & 7u) return fail(FE_EINVAL, "%s: device pointers must be 8-byte aligned", who);
+    if (E == 0) return FE_OK;
+    if (!J || !A) return fail(FE_EINVAL, "%s: null device pointer", who);
+    for (int k = 0; k < b; ++k)
+        if (!in[k] || !out[k]) return fail(FE_EINVAL, "%s: null field pointer %d", who, k);
+    return FE_OK;
+}
+
+int fe_grad3d_strided_f64(const double* J, int64_t ldJ, const double* D, const double* const* u, double* const* out, int64_t ldOut,
+                          int64_t E, int32_t Np, int32_t b, int32_t op_flags, void* stream) {
+    forget_last_launch();
+    const char* who = "grad on an element slice";
+    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
+        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
+    if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, op_flags);
+    if (int rc = check_strided(who, J, D, reinterpret_cast<const void* const*>(u), reinterpret_cast<const void* const*>(out), E, b,
+                               ldJ, true, 0, false, ldOut, true))
+        return rc;
+    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    if (E == 0) return FE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
+    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // kMaxFields fields per launch
+        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
+        fe::GradFields P = {};
+        for (int x = 0; x < 3; ++x) P.j[x] = J + (int64_t)x * 3 * ldJ;
+        for (int k = 0; k < nb; ++k) {
+            P.u[k] = u[k0 + k];
+            for (int x = 0; x < 3; ++x) P.out[k][x] = out[k0 + k] + (int64_t)x * ldOut * Np;
+        }
+        bool launched = false;
+        int rc = FE_OK;
+        switch (Np) {   // the (Np, M) geometries of fe_grad3d_f64
+            case 35: rc = launch_grad_strided<35, 1>(P, D, nb, E, ldJ, ldOut, opT, s, &launched); break;
+            case 20: rc = launch_grad_strided<20, 2>(P, D, nb, E, ldJ, ldOut, opT, s, &launched); break;
+            case 10: rc = launch_grad_strided<10, 3>(P, D, nb, E, ldJ, ldOut, opT, s, &launched); break;
+            default: rc = launch_grad_strided<4, 5>(P, D, nb, E, ldJ, ldOut, opT, s, &launched); break;
+        }
+        if (rc != FE_OK) return rc;
+        if (!launched)   // fewer elements than a wave tile: one thread per entry
+            for (int k = 0; k < nb; ++k)
+                hipLaunchKernelGGL(fe::grad3d_generic_ld_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, P.u[k], P.out[k][0], E,
+                                   ldJ, ldOut, Np, opT);
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+int fe_div3d_strided_f64(const double* J, int64_t ldJ, const double* D, const double* const* u, int64_t ldIn, double* const* out,
+                         int64_t E, int32_t Np, int32_t b, int32_t op_flags, void* stream) {
+    forget_last_launch();
+    const char* who = "div on an element slice";
+    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
+        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
+    if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, op_flags);
+    if (int rc = check_strided(who, J, D, reinterpret_cast<const void* const*>(u), reinterpret_cast<const void* const*>(out), E, b,
+                               ldJ, true, ldIn, true, 0, false))
+        return rc;
+    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    if (E == 0) return FE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
+    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // kMaxFields fields per launch
+        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
+        const fe::FieldPtrs P = field_group(u + k0, out + k0, nb);
+        bool launched = false;
+        int rc = FE_OK;
+        switch (Np) {   // the (Np, M) geometries of fe_div3d_f64
+            case 35: rc = launch_div_strided<35, 1>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched); break;
+            case 20: rc = launch_div_strided<20, 1>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched); break;
+            case 10: rc = launch_div_strided<10, 3>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched); break;
+            default: rc = launch_div_strided<4, 5>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched); break;
+        }
+        if (rc != FE_OK) return rc;
+        if (!launched)
+            for (int k = 0; k < nb; ++k)
+                hipLaunchKernelGGL(fe::div3d_generic_ld_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, P.v[k], P.out[k], E, ldJ,
+                                   ldIn, Np, opT);
+    }
+    FE_HIP_CHECK(hipGetLastError());
+    return FE_OK;
+}
+
+int fe_facemass_strided_f64(const double* J, int64_t ldJ, const double* R, const double* const* v, int64_t ldIn, double* const* out,
+                            int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream) {
+    forget_last_launch();
+    const char* who = "face-mass on an element slice";
+    FmChoice geo{0, 16};
+    // the compiled scope: tetrahedra p = 1..4, two or more fields (in groups of 2..4)
+    if (nf != fe::kFmNf || Np == 56 || !fm_mfma_geometry(Np, nf, Nfp, &geo) || b == 1)
+        return fail(FE_EUNSUPPORTED, "%s: (nf, Np, Nfp, b) = (%d, %d, %d, %d) has no kernel (tetrahedra p = 1..4, b >= 2)", who, nf, Np,
+                    Nfp, b);
+    if (layout_flags & ~7) return fail(FE_EINVAL, "%s: bad layout flags %d", who, layout_flags);
+    const int jfe = (layout_flags & FE_FM_J_FE) ? 1 : 0;
+    if (int rc = check_strided(who, J, R, reinterpret_cast<const void* const*>(v), reinterpret_cast<const void* const*>(out), E, b,
+                               ldJ, jfe != 0, ldIn, true, 0, false))
+        return rc;
+    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    if (E == 0) return FE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rifj = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((layout_flags & FE_FM_R_T) ? 2 : 0);
+    const int64_t jEs = jfe ? 1 : nf, jFs = jfe ? ldJ : 1;
+    const int rF = rifj == 0 ? Np * Nfp : rifj == 1 ? Nfp : rifj == 2 ? Nfp * Np : Np;
+    const int rI = rifj == 0 ? Nfp : rifj == 1 ? nf * Nfp : 1;
+    const int rJ = rifj == 0 || rifj == 1 ? 1 : rifj == 2 ? Np : nf * Np;
+    const int64_t nTiles = E / geo.tel;   // full wave tiles; the launch covers the elements behind the last one too
+    // fields go in groups of up to four per launch; never leave a group of one
+    for (int k0 = 0; k0 < b;) {
+        int nb = b - k0 < 4 ? b - k0 : 4;
+        if (b - k0 - nb == 1) nb -= 1;
+        const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
+        if (nTiles > 0) {
+            int rc = FE_OK;
+            switch (Np) {   // the (Np, Nfp, M) geometries of fe_facemass_f64
+                case 35: rc = launch_fm_strided<35, 15, 1>(J, R, P, nb, E, ldJ, ldIn, nTiles, jfe, rifj, s); break;
+                case 20: rc = launch_fm_strided<20, 10, 1>(J, R, P, nb, E, ldJ, ldIn, nTiles, jfe, rifj, s); break;
+                case 10: rc = launch_fm_strided<10, 6, 2>(J, R, P, nb, E, ldJ, ldIn, nTiles, jfe, rifj, s); break;
+                default: rc = launch_fm_strided<4, 3, 4>(J, R, P, nb, E, ldJ, ldIn, nTiles, jfe, rifj, s); break;
+            }
+            if (rc != FE_OK) return rc;
+        } else {   // fewer elements than a wave tile: one thread per entry
+            const dim3 grid(generic_grid(E, Np)), block(256);
+#define FE_FM_LD_CASE(NB)                                                                                            \
+    case NB:                                                                                                         \
+        hipLaunchKernelGGL(fe::facemass_generic_ld_kernel<NB>, grid, block, 0, s, J, R, P, E, ldIn, Np, nf, Nfp, jEs, \
+                           jFs, rF, rI, rJ);                                                                         \
+        break;
+            switch (nb) { FE_FM_LD_CASE(2) FE_FM_LD_CASE(3) FE_FM_LD_CASE(4) }
+#undef FE_FM_LD_CASE
+        }
+        k0 += nb;
     }
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;

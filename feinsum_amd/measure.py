@@ -247,7 +247,74 @@ def generate_out_arrays(cq: Any, einsum: BatchedEinsum, long_dim_length: int, *,
 # the waist: run one BatchedEinsum on device arrays
 # --------------------------------------------------------------------------
 
-def _check_tensor(name: str, t: Any, shape: Tuple[int, ...], dtype: np.dtype, q: DeviceQueue) -> None:
+#: what takes element slices (``_bind``) -- quoted by every refusal of a view
+ELEMENT_SLICE_RULE = ("element slices -- base.narrow(element axis, a, n) of a C-contiguous base -- are accepted for the inputs "
+                      "and outputs (not the operator array) of float64 grad 'xre,rij,ej->xei', div 'xre,rij,xej->ei' and "
+                      "face-mass 'ef,fij,fej->ei' (two or more fields per launch) of tetrahedra p = 1..4, under the transform "
+                      "'auto' or 'mfma', with (alpha, beta) = (1, 0)")
+
+
+def element_slice_ld(shape: Sequence[int], strides: Sequence[int], axis: int) -> Optional[int]:
+    """
+    The leading dimension of an element slice, or ``None``: *strides* (in elements) are the C-contiguous strides of
+    *shape* with the extent of *axis* replaced by some ``ld >= shape[axis]`` -- what ``base.narrow(axis, a, n)`` of a
+    contiguous ``base`` has (``ld`` is then the base's extent along *axis*).  A contiguous array gives ``shape[axis]``;
+    steps, negative strides, transposes and expanded axes give ``None``.  As in torch, the stride of an axis of extent 1
+    says nothing; an array without elements addresses nothing and gives ``shape[axis]``.  Where no axis in front of
+    *axis* has an extent above 1 the array is contiguous whatever its base was, and the result is ``shape[axis]``.
+    """
+    shape, strides = tuple(int(n) for n in shape), tuple(int(n) for n in strides)
+    if len(shape) != len(strides) or not 0 <= axis < len(shape) or any(n < 0 for n in shape):
+        return None
+    if 0 in shape:
+        return shape[axis]
+    inner = 1                                  # elements of one entry of `axis`
+    for d in range(len(shape) - 1, axis - 1, -1):
+        if shape[d] != 1 and strides[d] != inner:
+            return None
+        if d > axis:
+            inner *= shape[d]
+    ld, outer = None, 1                        # outer: extents between `axis` and d
+    for d in range(axis - 1, -1, -1):
+        if shape[d] != 1:
+            unit = inner * outer
+            if ld is None:
+                if strides[d] <= 0 or strides[d] % unit:
+                    return None
+                ld = strides[d] // unit
+                if ld < shape[axis]:
+                    return None
+            elif strides[d] != ld * unit:
+                return None
+        outer *= shape[d]
+    return shape[axis] if ld is None else ld
+
+
+def element_slice_spans(address: int, shape: Sequence[int], ld: int, axis: int, itemsize: int) -> Tuple[Tuple[int, int], ...]:
+    """The ``(address, nbytes)`` span of every contiguous piece of an element slice (:func:`element_slice_ld`): one per
+    entry of the axes in front of *axis* -- nine for a sliced J ``(3, 3, E)``, three for grad's output ``(3, E, Np)`` --
+    or ONE where the pieces touch (``ld == shape[axis]``, or nothing in front of *axis*)."""
+    shape = tuple(int(n) for n in shape)
+    inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
+    n_outer = int(np.prod(shape[:axis], dtype=np.int64))
+    piece = shape[axis] * inner * itemsize
+    if n_outer <= 1 or ld == shape[axis] or piece == 0:
+        return ((int(address), n_outer * piece),)
+    return tuple((int(address) + k * ld * inner * itemsize, piece) for k in range(n_outer))
+
+
+def _slice_axis(t: Any) -> Optional[int]:
+    """The axis along which a tensor is an element slice (0 for a contiguous one), or None."""
+    if t.is_contiguous():
+        return 0
+    shape, strides = tuple(t.shape), tuple(t.stride())
+    return next((a for a in range(len(shape)) if element_slice_ld(shape, strides, a) is not None), None)
+
+
+def _check_tensor(name: str, t: Any, shape: Tuple[int, ...], dtype: np.dtype, q: DeviceQueue,
+                  slice_axis: Optional[int] = None) -> bool:
+    """Shape, dtype, device and layout of one operand.  Returns True where *t* is not contiguous but an element slice
+    along *slice_axis* (``_bind`` then decides whether the launch takes slices); any other layout is refused."""
     import torch
 
     if not isinstance(t, torch.Tensor):
@@ -259,7 +326,11 @@ def _check_tensor(name: str, t: Any, shape: Tuple[int, ...], dtype: np.dtype, q:
     if t.dtype != getattr(torch, dtype.name):
         raise InvalidParameterError(f"argument '{name}' has dtype {t.dtype}, expected {dtype}")
     if not t.is_contiguous():
-        raise InvalidParameterError(f"argument '{name}' must be C-contiguous")
+        if slice_axis is not None and element_slice_ld(tuple(t.shape), tuple(t.stride()), slice_axis) is not None:
+            return True
+        raise InvalidParameterError(f"argument '{name}' must be C-contiguous ({ELEMENT_SLICE_RULE}; this view is not such"
+                                    " a slice of this operand)")
+    return False
 
 
 def _long_length(einsum: BatchedEinsum, arg_dict: Mapping[str, Any]) -> Dict[str, int]:
@@ -480,18 +551,30 @@ def _span(t: Any) -> Tuple[int, int]:
     return int(t.data_ptr()), int(t.numel()) * int(t.element_size())
 
 
+def _spans(t: Any) -> Tuple[Tuple[int, int], ...]:
+    """The byte ranges of a tensor ``_bind`` accepts: one for a contiguous tensor, one per contiguous piece of an element
+    slice (:func:`element_slice_spans`) -- so that two disjoint element ranges of one array do not overlap."""
+    axis = _slice_axis(t)
+    if axis is None:
+        raise InvalidParameterError("a tensor that is neither C-contiguous nor an element slice has no byte ranges here")
+    if axis == 0:                   # contiguous
+        return (_span(t),)
+    ld = element_slice_ld(tuple(t.shape), tuple(t.stride()), axis)
+    return element_slice_spans(int(t.data_ptr()), tuple(t.shape), ld, axis, int(t.element_size()))
+
+
 def _refuse_aliased_outputs(einsum: BatchedEinsum, arg_dict: Mapping[str, Any], given: Mapping[str, Any]) -> None:
     """The aliasing rule of :func:`evaluate`: no output handed in may share a byte with an input or with another
     output (the kernels read their operands while other threads already store results)."""
     names = list(given)
     for k, name in enumerate(names):
         for other in sorted(einsum.all_args):
-            if _overlap([_span(given[name])], [_span(arg_dict[other])]):
+            if _overlap(_spans(given[name]), _spans(arg_dict[other])):
                 raise InvalidParameterError(
                     f"output '{name}' shares memory with input '{other}': an evaluation may not write what it reads"
                     " (hand in an output of its own)")
         for other in names[:k]:
-            if _overlap([_span(given[name])], [_span(given[other])]):
+            if _overlap(_spans(given[name]), _spans(given[other])):
                 raise InvalidParameterError(
                     f"output '{name}' shares memory with output '{other}': every output needs memory of its own")
 
@@ -546,6 +629,110 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     if variant in (None, "auto", 0) and auto_picks_contraction(einsum, sizes):
         return "contraction"
     return "generic"
+
+
+def accepts_element_slices(einsum: BatchedEinsum, transform: Any = None, alpha: float = 1.0, beta: float = 0.0) -> bool:
+    """Does a launch of *einsum* under *transform* take element slices (``ELEMENT_SLICE_RULE``)?  From the einsum alone:
+    no arrays, no device.  The launch kind ``"family"``, a float64 GRAD / DIV / FACEMASS plan of tetrahedra p = 1..4 --
+    face-mass with every launch group of two or more fields --, the variant auto or ``"mfma"``, no accumulation."""
+    if (float(alpha), float(beta)) != (1.0, 0.0) or (isinstance(transform, Mapping) and "accumulate" in transform):
+        return False
+    variant = _variant_from_transform(transform)
+    if variant not in (None, "auto", "mfma", 0, 2):
+        return False
+    plan = match_family(einsum)      # (under these variants launch_kind is "family" exactly where a plan exists)
+    if plan is None:
+        return False
+    p = plan.params
+    if plan.family not in (FAMILY_GRAD, FAMILY_DIV, FAMILY_FACEMASS) or p.get("f32") or p.get("fields_f32"):
+        return False
+    if plan.family == FAMILY_FACEMASS:
+        return (p.get("nf") == 4 and (p.get("Np"), p.get("Nfp")) in _ACC_FACEMASS_SHAPES
+                and min(len(g) for g in _family_groups(plan, einsum)) >= 2)
+    return p.get("ndim", 3) == 3 and p.get("Np") in _ACC_EPILOGUE_NP
+
+
+def _element_axes(einsum: BatchedEinsum) -> Tuple[Dict[str, int], Optional[int]]:
+    """Where the element axis is: per argument that may be an element slice, and in the outputs.  Empty / None outside the
+    DG families; the operator array has none."""
+    plan = match_family(einsum)
+    if plan is None:
+        return {}, None
+    axes: Dict[str, int] = {}
+    for row in einsum.args:
+        for pos, arg in enumerate(row):
+            if plan.long_index in einsum.in_idx_sets[pos]:
+                axes[arg.name] = einsum.in_idx_sets[pos].index(plan.long_index)
+    out_axis = einsum.out_idx_set.index(plan.long_index) if plan.long_index in einsum.out_idx_set else None
+    return axes, out_axis
+
+
+def _strided_runs(plan: KernelPlan, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any]) -> list:
+    """The launches of a family plan on element slices: ``[(first row of the group, (ldIn, ldOut), rows)]``.  A launch has one
+    ldIn and one ldOut, so the fields of a group of ``_family_groups`` are gathered by their pair of leading dimensions, in order
+    of first appearance (fields A, B, A, B of two bases become the launches {A, A} and {B, B}; every field's result is the same
+    in any grouping).  An entry of *outs* may be None: an output that is yet to be allocated, contiguous.  Face-mass needs two
+    fields per launch: a field that is alone with its leading dimensions is refused (``InvalidParameterError``)."""
+    role, rows = plan.roles, einsum.args
+    in_role = "u" if "D" in role else "v"
+    in_axis = einsum.in_idx_sets[role[in_role]].index(plan.long_index)
+    out_axis = einsum.out_idx_set.index(plan.long_index)
+    ld_of = lambda t, axis: element_slice_ld(tuple(t.shape), tuple(t.stride()), axis)   # noqa: E731
+    runs = []
+    for group in _family_groups(plan, einsum):
+        by_ld: Dict[Tuple[int, int], list] = {}
+        for m in group:
+            field = arg_dict[rows[m][role[in_role]].name]
+            n = int(field.shape[in_axis])
+            by_ld.setdefault((ld_of(field, in_axis), n if outs[m] is None else ld_of(outs[m], out_axis)), []).append(m)
+        for lds, members in by_ld.items():
+            if plan.family == FAMILY_FACEMASS and len(members) < 2 and int(arg_dict[rows[members[0]][role[in_role]].name].shape[in_axis]) > 0:
+                raise InvalidParameterError(
+                    f"face-mass on element slices: field '{rows[members[0]][role[in_role]].name}' is alone in its launch group with its "
+                    f"leading dimensions (ldIn, ldOut) = {lds}, and one field has no matrix-core kernel: slice the fields and outputs of a "
+                    f"group out of bases of equal length, at least two of each length, or hand in C-contiguous arrays ({ELEMENT_SLICE_RULE})")
+            runs.append((group[0], lds, members))
+    return runs
+
+
+class _StridedFamilyLaunch:
+    """float64 grad, div or face-mass of tetrahedra p = 1..4 with element slices among its arrays: the named entry points
+    ``fe_grad3d_strided_f64`` / ``fe_div3d_strided_f64`` / ``fe_facemass_strided_f64``, one launch per group of
+    ``_family_groups`` and pair of leading dimensions in it (``_strided_runs``).  No prepared operators."""
+
+    def __init__(self, plan: KernelPlan, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any]) -> None:
+        self.plan = plan
+        self._keep = (arg_dict, outs)
+        role, rows, p = plan.roles, einsum.args, plan.params
+        op_role, in_role = ("D", "u") if "D" in role else ("R", "v")
+        self.entry_point = {FAMILY_GRAD: "fe_grad3d_strided_f64", FAMILY_DIV: "fe_div3d_strided_f64",
+                            FAMILY_FACEMASS: "fe_facemass_strided_f64"}[plan.family]
+        j_axis = einsum.in_idx_sets[role["J"]].index(plan.long_index)
+        self.E = int(arg_dict[rows[0][role["J"]].name].shape[j_axis])
+        self.calls = []      # (function, arguments in front of the stream)
+        self.rows = []       # the rows of every call
+        for first, (ld_in, ld_out), members in _strided_runs(plan, einsum, arg_dict, outs):
+            J, A = arg_dict[rows[first][role["J"]].name], arg_dict[rows[first][role[op_role]].name]
+            ldJ = element_slice_ld(tuple(J.shape), tuple(J.stride()), j_axis)
+            vptrs = [arg_dict[rows[m][role[in_role]].name].data_ptr() for m in members]
+            optrs = [outs[m].data_ptr() for m in members]
+            self.rows.append(tuple(members))
+            if plan.family == FAMILY_GRAD:
+                self.calls.append((_hip.grad3d_strided, (J.data_ptr(), ldJ, A.data_ptr(), vptrs, optrs, ld_out, self.E,
+                                                         p["Np"], plan.layout_flags)))
+            elif plan.family == FAMILY_DIV:
+                self.calls.append((_hip.div3d_strided, (J.data_ptr(), ldJ, A.data_ptr(), vptrs, ld_in, optrs, self.E,
+                                                        p["Np"], plan.layout_flags)))
+            else:
+                self.calls.append((_hip.facemass_strided, (J.data_ptr(), ldJ, A.data_ptr(), vptrs, ld_in, optrs, self.E,
+                                                           p["Np"], p["nf"], p["Nfp"], plan.layout_flags)))
+
+    def launch(self, stream_ptr: int) -> None:
+        for fn, args in self.calls:
+            fn(*args, stream=stream_ptr)
+
+    def time_batch(self, n: int, stream_ptr: int) -> float:
+        return _hip.time_with_events(self.launch, n, stream_ptr)
 
 
 ACCUMULATE_ROUTES = ("kernel", "axpby", "epilogue")
@@ -635,16 +822,24 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     if missing:
         raise InvalidParameterError(f"missing input arrays: {missing}")
     sizes = _long_length(einsum, arg_dict)
+    in_axes, out_axis = _element_axes(einsum)
+    sliced = []      # arguments that are element slices and not contiguous
     for name, shape in einsum.arg_to_shape.items():
         concrete = tuple(sizes[d.name] if isinstance(d, SizeParam) else int(d) for d in shape)
-        _check_tensor(name, arg_dict[name], concrete, einsum.arg_to_dtype[name], q)
+        if _check_tensor(name, arg_dict[name], concrete, einsum.arg_to_dtype[name], q, in_axes.get(name)):
+            sliced.append(name)
     out_shape = tuple(sizes[d.name] if isinstance(d, SizeParam) else int(d) for d in einsum.shape)
     given = {name: out_dict[name] for name in einsum.output_names if out_dict is not None and name in out_dict}
     for k, name in enumerate(einsum.output_names):
         if name in given:
-            _check_tensor(name, given[name], out_shape, result_dtype(einsum, k), q)
+            if _check_tensor(name, given[name], out_shape, result_dtype(einsum, k), q, out_axis):
+                sliced.append(name)
     _refuse_aliased_outputs(einsum, arg_dict, given)     # before anything is allocated, prepared or launched
     alpha, beta = _check_scale(alpha, beta)
+    if sliced:                                           # (likewise: which launches take slices, and how their fields group)
+        if not accepts_element_slices(einsum, transform, alpha, beta):
+            raise InvalidParameterError(f"argument '{sliced[0]}' must be C-contiguous for this launch: {ELEMENT_SLICE_RULE}")
+        _strided_runs(match_family(einsum), einsum, arg_dict, [given.get(name) for name in einsum.output_names])
     route = None if (alpha, beta) == (1.0, 0.0) else accumulate_route(einsum, transform)
     if beta != 0.0 and len(given) != len(einsum.output_names):
         raise InvalidParameterError(
@@ -679,6 +874,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
             bound = AdjointLaunch(match_operator_adjoint(einsum), einsum, arg_dict, outs, stream=q.stream)
     elif kind == "mixed_family":     # (accumulation: the "axpby" route -- accumulate_route knows no other for it)
         bound = _FamilyLaunch(match_mixed_family(einsum), einsum, arg_dict, outs, None)
+    elif kind == "family" and sliced:
+        bound = _StridedFamilyLaunch(match_family(einsum), einsum, arg_dict, outs)
     elif kind == "family":
         bound = _FamilyLaunch(match_family(einsum), einsum, arg_dict, outs, _variant_from_transform(transform),
                               scale=(alpha, beta) if route in ("kernel", "epilogue") else None)
@@ -692,8 +889,9 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     #: None (the outputs are overwritten), or which way the launch adds onto them: "kernel" | "axpby" | "epilogue" (accumulate_route)
     bound.accumulate = route
     # byte ranges the launch reads and writes (operator.py checks them before reordering launches)
-    bound.reads = tuple(_span(arg_dict[name]) for name in sorted(einsum.all_args)) + (tuple(_span(t) for t in outs) if beta != 0.0 else ())
-    bound.writes = tuple(_span(t) for t in outs) + (tuple(_span(t) for t in temps) if route == "axpby" else ())
+    bound.reads = (tuple(sp for name in sorted(einsum.all_args) for sp in _spans(arg_dict[name]))
+                   + (tuple(sp for t in outs for sp in _spans(t)) if beta != 0.0 else ()))
+    bound.writes = tuple(sp for t in outs for sp in _spans(t)) + (tuple(_span(t) for t in temps) if route == "axpby" else ())
     bound.output_allocations = MappingProxyType(allocated)
     bound.owned_arrays, bound.owned_stream_ptr = tuple(owned), q.stream_ptr   # (operator.py: launches on another stream mark them)
     return q, bound, outs

@@ -32,7 +32,7 @@ from typing import Any, List, Mapping, Optional, Sequence, Tuple
 from feinsum_amd import _hip
 from feinsum_amd.einsum import BatchedEinsum
 from feinsum_amd.family import FAMILY_DIV, FAMILY_FACEMASS, FAMILY_GRAD
-from feinsum_amd.measure import _bind, _FamilyLaunch, _overlap
+from feinsum_amd.measure import _bind, _FamilyLaunch, _overlap, _StridedFamilyLaunch
 
 StageT = Tuple[BatchedEinsum, Mapping[str, Any]]
 
@@ -144,7 +144,9 @@ class BoundOperator:
         """C entry point behind every enqueue, in order (one per launch group)."""
         names: List[str] = []
         for b in self.launches:
-            if hasattr(b, "entry_point"):
+            if isinstance(b, _StridedFamilyLaunch):     # a stage on element slices: never merged, one call per launch group
+                names += [b.entry_point] * len(b.calls)
+            elif hasattr(b, "entry_point"):
                 names.append(b.entry_point)
             elif isinstance(b, _FamilyLaunch):
                 names += ["fe_gradplanes" if b.group_family == 6 else f"fe_{b.plan.name}" + ("_mixed" if getattr(b, "fields_f32", False) else "")] * len(b.groups)

@@ -444,6 +444,27 @@ int fe_div3d_mixed_f64(const double* J, const double* D, const void* const* v, d
 int fe_facemass_mixed_f64(const double* J, const double* R, const void* const* v, double* const* outs,
                           int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream);
 
+/* float64 grad 'xre,rij,ej->xei', div 'xre,rij,xej->ei' and face-mass 'ef,fij,fej->ei' x b on an ELEMENT SLICE of larger
+ * arrays: E is the number of elements of the launch, and every array whose element axis is not its leading one has a
+ * leading dimension of its own, in elements, as BLAS has lda (every pointer addresses element 0 of the slice):
+ *   ldJ    row x*3 + r of J starts at J + (x*3 + r) * ldJ; face-mass with J stored [nf][..] (FE_FM_J_FE): row f at J + f * ldJ
+ *          (J stored [..][nf] is contiguous in a slice: ldJ is ignored);
+ *   ldIn   div: plane x of field k starts at u[k] + x * ldIn * Np; face-mass: slab f at v[k] + f * ldIn * Nfp;
+ *   ldOut  grad: plane x of field k starts at out[k] + x * ldOut * Np.
+ * grad's fields and the outputs of div and face-mass are contiguous in a slice.  Tetrahedra p = 1..4 (Np = 4, 10, 20, 35;
+ * face-mass nf = 4, Nfp = 3, 6, 10, 15), any b >= 1 -- face-mass b >= 2 --, any E; anything else is FE_EUNSUPPORTED.  A leading
+ * dimension smaller than E and a pointer that is not 8-byte aligned are FE_EINVAL; all of these come before any device work.
+ * The matrix-core kernels, walking as the contiguous launches do (fe_last_launch_info `kind` bit 128); with every leading dimension equal to E the
+ * results are bitwise those of fe_grad3d_batched_f64 / fe_div3d_batched_f64 / fe_facemass_f64.  Asynchronous on `stream`;
+ * E = 0 launches nothing. */
+int fe_grad3d_strided_f64(const double* J, int64_t ldJ, const double* D, const double* const* u, double* const* out,
+                          int64_t ldOut, int64_t E, int32_t Np, int32_t b, int32_t op_flags, void* stream);
+int fe_div3d_strided_f64(const double* J, int64_t ldJ, const double* D, const double* const* u, int64_t ldIn,
+                         double* const* out, int64_t E, int32_t Np, int32_t b, int32_t op_flags, void* stream);
+int fe_facemass_strided_f64(const double* J, int64_t ldJ, const double* R, const double* const* v, int64_t ldIn,
+                            double* const* out, int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
+                            int32_t layout_flags, void* stream);
+
 /* float32 operands (the reference validates float32 einsums at 1e-6 and carries float32 peaks:
  * src/feinsum/measure.py:178-192, src/feinsum/data/device_info.py:5-26).  One entry point for the families
  * FE_FAMILY_GRAD / DIV / DIVCOMP / MATAPPLY / FACEMASS: every pointer of `args` is read as float (the struct's
