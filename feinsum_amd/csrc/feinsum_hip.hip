@@ -36,6 +36,9 @@
 #include "fe_facemass_f32.h"
 #include "fe_tiled.h"
 #include "fe_mixed.h"
+#include "fe_orders.h"
+
+static_assert(FE_FM_J_FE == 1 && FE_FM_R_IFJ == 2 && FE_FM_R_T == 4, "the layout bits fe::FmLayout decodes");
 
 namespace {
 
@@ -155,17 +158,101 @@ struct PerDeviceOnce {
 #include "fe_split_alloc.h"
 namespace {
 
-int check_common(const void* J, const void* D, const void* u, const void* out, int64_t E,
-                 int32_t Np) {
-    if (E < 0) return fail(FE_EINVAL, "E must be >= 0 (got %lld)", (long long)E);
-    if (Np <= 0) return fail(FE_EINVAL, "Np must be positive (got %d)", Np);
-    if (E > 0 && (!J || !D || !u || !out)) return fail(FE_EINVAL, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(u) |
-         reinterpret_cast<uintptr_t>(out)) & 7u)
-        return fail(FE_EINVAL, "device pointers must be 8-byte aligned (float64 arrays)");
-    if (E * (int64_t)Np >= (int64_t)1 << 39)
-        return fail(FE_EINVAL, "E*Np too large (%lld)", (long long)(E * Np));
+// ---- the argument check of the DG entry points: one description of a call, one precedence ("the front end").
+//  1. structure -- E < 0, non-positive sizes, b < 1, stray flag bits, non-finite alpha / beta, a null pointer table, a leading
+//     dimension below E or too large, alignment: FE_EINVAL;
+//  2. scope -- no kernel for the shape, the field count or the variant: FE_EUNSUPPORTED;
+//  3. E == 0: kCheckDone, the caller returns FE_OK;
+//  4. null device or field pointers, E*Np too large: FE_EINVAL.
+// The entry points on element slices keep the order their tests pin: scope first (CallCheck::scope_first).
+// Everything here comes before any device work.
+constexpr int kCheckDone = 1;
+enum CheckScope { kScopeAny, kScopeTet, kScopeTetFaces };   // kernels for: any shape / tetrahedra p = 1..4 by Np / by (nf, Np, Nfp, b)
+struct CallCheck {
+    const char* who;
+    const void* J;
+    const void* op;
+    const void* const* in;    // b pointers each
+    const void* const* out;
+    int64_t E;
+    int32_t Np, b, flags, flag_mask;
+    const char* flag_name = "operator";
+    int in_align = 8;                       // 4: float32 fields
+    const double* alpha = nullptr;          // with beta: an accumulating call
+    const double* beta = nullptr;
+    int64_t ld[3] = {0, 0, 0};              // ldJ, ldIn, ldOut of a call on an element slice, where ld_used
+    bool ld_used[3] = {false, false, false};
+    bool faces = false;                     // a face-mass call: nf, Nfp
+    int32_t nf = 0, Nfp = 0;
+    CheckScope scope = kScopeAny;
+    const char* kernel = "kernel";          // what the scope message says is missing
+    int min_b = 1;
+    bool scope_first = false;               // the slice entry points: the scope comes before the structure (tests pin it)
+    int variant = FE_VARIANT_AUTO, variant_hi = FE_VARIANT_AUTO;
+};
+
+int check_scope(const CallCheck& c) {
+    const char* who = c.who;
+    if (c.variant < FE_VARIANT_AUTO || c.variant > c.variant_hi) return fail(FE_EUNSUPPORTED, "%s: unknown variant %d", who, c.variant);
+    if (c.scope == kScopeTet && !fe::is_tet_order(c.Np))
+        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no %s (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, c.Np, c.kernel);
+    // (a field count below one is malformed, not out of scope)
+    if (c.scope == kScopeTetFaces && !(c.nf == fe::kFmNf && fe::is_tet_order(c.Np, c.Nfp) && !(c.b >= 1 && c.b < c.min_b)))
+        return fail(FE_EUNSUPPORTED, "%s: (nf, Np, Nfp, b) = (%d, %d, %d, %d) has no %s (tetrahedra p = 1..4, b >= %d)", who, c.nf,
+                    c.Np, c.Nfp, c.b, c.kernel, c.min_b);
     return FE_OK;
+}
+
+int check_call(const CallCheck& c) {
+    const char* who = c.who;
+    if (c.scope_first)
+        if (int rc = check_scope(c)) return rc;
+    if (c.E < 0) return fail(FE_EINVAL, "%s: E must be >= 0 (got %lld)", who, (long long)c.E);
+    if (c.faces && (c.Np <= 0 || c.nf <= 0 || c.Nfp <= 0 || c.b <= 0))
+        return fail(FE_EINVAL, "%s: Np, nf, Nfp, b must be positive (%d %d %d %d)", who, c.Np, c.nf, c.Nfp, c.b);
+    if (c.Np <= 0) return fail(FE_EINVAL, "%s: Np must be positive (got %d)", who, c.Np);
+    if (c.b < 1) return fail(FE_EINVAL, "%s: b=%d, need at least one field", who, c.b);
+    if (c.flags & ~c.flag_mask) return fail(FE_EINVAL, "%s: bad %s flags %d", who, c.flag_name, c.flags);
+    if (c.alpha && (!std::isfinite(*c.alpha) || !std::isfinite(*c.beta)))
+        return fail(FE_EINVAL, "%s: alpha and beta must be finite (got %g, %g)", who, *c.alpha, *c.beta);
+    if (!c.in || !c.out) return fail(FE_EINVAL, "%s: null pointer table", who);
+    for (int i = 0; i < 3; ++i)
+        if (c.ld_used[i] && c.ld[i] < c.E)
+            return fail(FE_EINVAL, "%s: a leading dimension is smaller than E = %lld (ldJ %lld, ldIn %lld, ldOut %lld)", who,
+                        (long long)c.E, (long long)c.ld[0], (long long)c.ld[1], (long long)c.ld[2]);
+    for (int i = 0; i < 3; ++i)
+        if (c.ld_used[i] && c.ld[i] >= (int64_t)1 << 40)
+            return fail(FE_EINVAL, "%s: leading dimension too large (%lld)", who, (long long)c.ld[i]);
+    if ((reinterpret_cast<uintptr_t>(c.J) | reinterpret_cast<uintptr_t>(c.op)) & 7u)
+        return fail(FE_EINVAL, "%s: device pointers must be 8-byte aligned (float64 arrays: J and the operator)", who);
+    for (int k = 0; k < c.b; ++k) {
+        if (reinterpret_cast<uintptr_t>(c.in[k]) & (uintptr_t)(c.in_align - 1))
+            return fail(FE_EINVAL, c.in_align == 4 ? "%s: field %d must be 4-byte aligned (a float32 array)"
+                                                   : "%s: field %d: device pointers must be 8-byte aligned (float64 arrays)", who, k);
+        if (reinterpret_cast<uintptr_t>(c.out[k]) & 7u)
+            return fail(FE_EINVAL, "%s: output %d: device pointers must be 8-byte aligned (float64 arrays)", who, k);
+    }
+    if (!c.scope_first)
+        if (int rc = check_scope(c)) return rc;
+    if (c.E == 0) return kCheckDone;
+    if (!c.J || !c.op) return fail(FE_EINVAL, "%s: null device pointer", who);
+    for (int k = 0; k < c.b; ++k)
+        if (!c.in[k] || !c.out[k]) return fail(FE_EINVAL, "%s: null field pointer %d (a null device pointer)", who, k);
+    if (c.E * (int64_t)c.Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large (%lld)", who, (long long)(c.E * c.Np));
+    return FE_OK;
+}
+
+template <typename T>
+const void* const* ptr_table(T* const* p) { return reinterpret_cast<const void* const*>(p); }
+void use_ld(CallCheck& c, int i, int64_t ld) { c.ld[i] = ld; c.ld_used[i] = true; }
+#define FE_CHECK_CALL(c) \
+    if (int rc_ = check_call(c)) return rc_ == kCheckDone ? FE_OK : rc_
+
+// the older entry points check field by field, and an empty call goes on to their own checks of flags and variant
+int check_common(const char* who, const void* J, const void* D, const void* u, const void* out, int64_t E, int32_t Np) {
+    const CallCheck c = {who, J, D, &u, &out, E, Np, 1, 0, 0};
+    const int rc = check_call(c);
+    return rc == kCheckDone ? FE_OK : rc;
 }
 
 unsigned generic_grid(int64_t E, int Np) { return (unsigned)((E * Np + 255) / 256); }
@@ -906,20 +993,11 @@ int launch_fm_nb(const double* J, const double* R, const void* prep, const fe::F
 template <int NP, int NFP, int M, int NF = fe::kFmNf, bool ALDS = false>
 int launch_fm(const double* J, const double* R, const void* prep, const fe::FieldPtrs& P, int nb, int64_t E,
               int64_t nTiles, int jfe, int rifj, hipStream_t s) {
-    switch (nb) {
-        case 2: return launch_fm_nb<NP, NFP, M, 2, NF, ALDS>(J, R, prep, P, E, nTiles, jfe, rifj, s);
-        case 3: return launch_fm_nb<NP, NFP, M, 3, NF, ALDS>(J, R, prep, P, E, nTiles, jfe, rifj, s);
-        case 4: return launch_fm_nb<NP, NFP, M, 4, NF, ALDS>(J, R, prep, P, E, nTiles, jfe, rifj, s);
-        default: break;
-    }
+    int rc = FE_OK;
+    auto launch = [&](auto NB) { return launch_fm_nb<NP, NFP, M, decltype(NB)::value, NF, ALDS>(J, R, prep, P, E, nTiles, jfe, rifj, s); };
+    if (fe::with_field_count<2, 4>(nb, &rc, launch)) return rc;
     if constexpr (NP == 35 && NF == fe::kFmNf) {   // p = 4, the headline order: groups of up to 8 fields
-        switch (nb) {
-            case 5: return launch_fm_nb<NP, NFP, M, 5>(J, R, prep, P, E, nTiles, jfe, rifj, s);
-            case 6: return launch_fm_nb<NP, NFP, M, 6>(J, R, prep, P, E, nTiles, jfe, rifj, s);
-            case 7: return launch_fm_nb<NP, NFP, M, 7>(J, R, prep, P, E, nTiles, jfe, rifj, s);
-            case 8: return launch_fm_nb<NP, NFP, M, 8>(J, R, prep, P, E, nTiles, jfe, rifj, s);
-            default: break;
-        }
+        if (fe::with_field_count<5, 8>(nb, &rc, launch)) return rc;
     }
     return fail(FE_EINVAL, "face-mass: internal field grouping error (nb=%d)", nb);
 }
@@ -942,12 +1020,11 @@ int launch_fm_acc_nb(const double* J, const double* R, const fe::FieldPtrs& P, i
 template <int NP, int NFP, int M>
 int launch_fm_acc(const double* J, const double* R, const fe::FieldPtrs& P, int nb, int64_t E, int64_t nTiles, int jfe, int rifj,
                   double alpha, double beta, hipStream_t s) {
-    switch (nb) {
-        case 2: return launch_fm_acc_nb<NP, NFP, M, 2>(J, R, P, E, nTiles, jfe, rifj, alpha, beta, s);
-        case 3: return launch_fm_acc_nb<NP, NFP, M, 3>(J, R, P, E, nTiles, jfe, rifj, alpha, beta, s);
-        case 4: return launch_fm_acc_nb<NP, NFP, M, 4>(J, R, P, E, nTiles, jfe, rifj, alpha, beta, s);
-        default: break;
-    }
+    int rc = FE_OK;
+    if (fe::with_field_count<2, 4>(nb, &rc, [&](auto NB) {
+            return launch_fm_acc_nb<NP, NFP, M, decltype(NB)::value>(J, R, P, E, nTiles, jfe, rifj, alpha, beta, s);
+        }))
+        return rc;
     return fail(FE_EINVAL, "accumulating face-mass: internal field grouping error (nb=%d)", nb);
 }
 
@@ -1049,12 +1126,11 @@ int launch_fm_strided_nb(const double* J, const double* R, const fe::FieldPtrs& 
 template <int NP, int NFP, int M>
 int launch_fm_strided(const double* J, const double* R, const fe::FieldPtrs& P, int nb, int64_t E, int64_t ldJ, int64_t ldIn,
                       int64_t nTiles, int jfe, int rifj, hipStream_t s) {
-    switch (nb) {
-        case 2: return launch_fm_strided_nb<NP, NFP, M, 2>(J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj, s);
-        case 3: return launch_fm_strided_nb<NP, NFP, M, 3>(J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj, s);
-        case 4: return launch_fm_strided_nb<NP, NFP, M, 4>(J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj, s);
-        default: break;
-    }
+    int rc = FE_OK;
+    if (fe::with_field_count<2, 4>(nb, &rc, [&](auto NB) {
+            return launch_fm_strided_nb<NP, NFP, M, decltype(NB)::value>(J, R, P, E, ldJ, ldIn, nTiles, jfe, rifj, s);
+        }))
+        return rc;
     return fail(FE_EINVAL, "face-mass on an element slice: internal field grouping error (nb=%d)", nb);
 }
 
@@ -1074,7 +1150,7 @@ fe::GradFields grad_fields(const double* J, const double* const* u, double* cons
 // are those of a plain grad (one [3][3][E] array, [3][E][Np] outputs).
 int grad_fields_launch(const fe::GradFields& P, const double* Jfull, const double* D, const void* prep, int nb, int nx,
                        int64_t E, int Np, int opT, int variant, hipStream_t s) {
-    const bool mfma_ok = Np == 35 || Np == 20 || Np == 10 || Np == 4 || (Np == 56 && Jfull);
+    const bool mfma_ok = fe::is_tet_order(Np) || (Np == 56 && Jfull);
     fe::FieldPtrs Pt = {};
     for (int k = 0; k < nb; ++k) { Pt.v[k] = P.u[k]; Pt.out[k] = P.out[k][0]; }
     const fe::TiledArgs ta = tiled_args(FE_FAMILY_GRAD, Jfull, D, Pt, nb, E, 3, Np, 0, 0, opT, 0, 0);
@@ -1102,14 +1178,11 @@ int grad_fields_launch(const fe::GradFields& P, const double* Jfull, const doubl
 #ifdef FE_EXPERIMENTS
         if (variant >= 1000) dbg = (variant - 1000) & 255;   // experiment flags, see fe_grad.h
 #endif
-        int rc = FE_OK;
-        switch (Np) {   // wave tile = 16 M elements
-            case 35: rc = launch_grad<35, 1>(P, Jfull != nullptr, D, prep, nb, nx, E, dbg, opT, s, &e_done); break;
-            case 20: rc = launch_grad<20, 2>(P, Jfull != nullptr, D, prep, nb, nx, E, dbg, opT, s, &e_done); break;
-            case 10: rc = launch_grad<10, 3>(P, Jfull != nullptr, D, prep, nb, nx, E, dbg, opT, s, &e_done); break;
-            default: rc = launch_grad<4, 5>(P, Jfull != nullptr, D, prep, nb, nx, E, dbg, opT, s, &e_done); break;
-        }
-        if (rc != FE_OK) return rc;
+        if (int rc = fe::with_tet_order(Np, [&](auto o) {   // wave tile = 16 M elements
+                using O = decltype(o);
+                return launch_grad<O::NP, O::MG>(P, Jfull != nullptr, D, prep, nb, nx, E, dbg, opT, s, &e_done);
+            }))
+            return rc;
     }
     if (e_done < E) {
         const dim3 grid(generic_grid(E - e_done, Np)), block(256);
@@ -1206,12 +1279,12 @@ int launch_waveop(fe::WaveOpArgs a, const fe::GradFields& Pg, const fe::FieldPtr
 #endif
     *launched = a.nTilesG > 0 || a.nTilesD > 0 || a.nTilesF > 0;   // remainders included
     if (!*launched) return FE_OK;
-    switch (nb) {
-        case 2: return launch_waveop_nb<NP, NFP, MG, MD, MF, 2>(a, Pg, Pd, Pf, s);
-        case 3: return launch_waveop_nb<NP, NFP, MG, MD, MF, 3>(a, Pg, Pd, Pf, s);
-        case 4: return launch_waveop_nb<NP, NFP, MG, MD, MF, 4>(a, Pg, Pd, Pf, s);
-        default: return fail(FE_EINVAL, "waveop: internal field count error (nb=%d)", nb);
-    }
+    int rc = FE_OK;
+    if (fe::with_field_count<2, 4>(nb, &rc, [&](auto NB) {
+            return launch_waveop_nb<NP, NFP, MG, MD, MF, decltype(NB)::value>(a, Pg, Pd, Pf, s);
+        }))
+        return rc;
+    return fail(FE_EINVAL, "waveop: internal field count error (nb=%d)", nb);
 }
 
 // triangles (ND = 2): grad by components (MODE 4) and div (MODE 0) instances of the div template
@@ -1291,13 +1364,12 @@ int launch_f32_facemass(const fe_argpack* a, const double* const* vin, double* c
     const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
     const float* J = reinterpret_cast<const float*>(a->J);
     const float* R = reinterpret_cast<const float*>(a->D);
-    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {
-        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
-        const fe::FieldPtrs P = field_group(vin + k0, vout + k0, nb);
-        if (int rc = mfma_launch<K>(s, walk_static(nTiles), geo, what,
-                                    [&](const Launch&) { return call(0, 0, J, R, P, nb, a->E, nTiles, jl, rl); }))
-            return rc;
-    }
+    if (int rc = fe::for_each_field_group(b, fe::kMaxFields, false, [&](int k0, int nb) {
+            const fe::FieldPtrs P = field_group(vin + k0, vout + k0, nb);
+            return mfma_launch<K>(s, walk_static(nTiles), geo, what,
+                                  [&](const Launch&) { return call(0, 0, J, R, P, nb, a->E, nTiles, jl, rl); });
+        }))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
@@ -1329,29 +1401,50 @@ int launch_mixed_facemass(const double* J, const double* R, const float* const* 
     const int64_t nTiles = E / G::TEL;
     const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
     const Walk walk = walk_static(nTiles > 0 ? nTiles : 1);
-    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // groups of up to kMaxFields fields share J and the fragments
-        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
-        const fe::FieldPtrs P = field_group(reinterpret_cast<const double* const*>(v) + k0, outs + k0, nb);
-        auto args = [&](const Launch&) {
-            return call(0, fe::kLaunchMixedFields | (plain ? fe::kLaunchPlainFieldLoads : 0), J, R, P, nb, E, nTiles, jl, rl);
-        };
-        if (int rc = plain ? mfma_launch<KP>(s, walk, geo, what_plain, args) : mfma_launch<KD>(s, walk, geo, what, args)) return rc;
-    }
+    // groups of up to kMaxFields fields share J and the fragments
+    if (int rc = fe::for_each_field_group(b, fe::kMaxFields, false, [&](int k0, int nb) {
+            const fe::FieldPtrs P = field_group(reinterpret_cast<const double* const*>(v) + k0, outs + k0, nb);
+            auto args = [&](const Launch&) {
+                return call(0, fe::kLaunchMixedFields | (plain ? fe::kLaunchPlainFieldLoads : 0), J, R, P, nb, E, nTiles, jl, rl);
+            };
+            return plain ? mfma_launch<KP>(s, walk, geo, what_plain, args) : mfma_launch<KD>(s, walk, geo, what, args);
+        }))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
 
-// the argument checks the mixed entry points share: float32 fields 4-byte aligned, everything else 8-byte, before any device work
-int check_mixed(const char* who, const void* J, const void* op, const float* const* v, double* const* outs, int64_t E, int32_t Np,
-                int32_t b) {
-    if (E < 0) return fail(FE_EINVAL, "%s: E must be >= 0 (got %lld)", who, (long long)E);
-    if (Np <= 0 || b <= 0) return fail(FE_EINVAL, "%s: Np and b must be positive (got %d, %d)", who, Np, b);
-    if (!v || !outs) return fail(FE_EINVAL, "%s: null pointer table", who);
-    if ((reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(op)) & 7u)
-        return fail(FE_EINVAL, "%s: J and the operator must be 8-byte aligned (float64 arrays)", who);
-    for (int k = 0; k < b; ++k) {
-        if (reinterpret_cast<uintptr_t>(v[k]) & 3u) return fail(FE_EINVAL, "%s: field %d must be 4-byte aligned (a float32 array)", who, k);
-        if (reinterpret_cast<uintptr_t>(outs[k]) & 7u) return fail(FE_EINVAL, "%s: output %d must be 8-byte aligned (a float64 array)", who, k);
+// A kernel's description (fe_kernel_resources), formatted once: a `static const What` per instantiation of a call site
+struct What {
+    char text[96];
+    What(const char* fmt, ...) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(text, sizeof(text), fmt, ap);
+        va_end(ap);
+    }
+    operator const char*() const { return text; }
+};
+
+// The field tables of an argument pack (fe_launch, fe_launch_f32): the b-field form (v / outs) when given, else the single
+// pair (u / out).  `in` and `out` may point into the struct: filled in place, not copied.
+struct PackFields {
+    const void* one_in[1];
+    double* one_out[1];
+    const void* const* in;
+    double* const* out;
+    int b;
+};
+int pack_fields(const char* who, const fe_argpack* a, PackFields* f) {
+    f->b = a->b > 0 ? a->b : 1;
+    f->one_in[0] = a->u;
+    f->one_out[0] = a->out;
+    f->in = ptr_table(a->v);
+    f->out = a->outs;
+    if (!f->in || !f->out) {
+        if (f->b != 1) return fail(FE_EINVAL, "%s: b = %d needs the v / outs pointer arrays", who, f->b);
+        f->in = f->one_in;
+        f->out = f->one_out;
     }
     return FE_OK;
 }
@@ -1429,11 +1522,10 @@ inline bool fm_mfma_geometry(int Np, int nf, int Nfp, FmChoice* c) {
     }
     if (nf != fe::kFmNf) return false;
     if (Np == 56 && Nfp == 21) { *c = {4, 16}; return true; }   // p = 5: A fragments in LDS
-    if (Np == 35 && Nfp == 15) { *c = {8, 16}; return true; }
-    if (Np == 20 && Nfp == 10) { *c = {4, 16}; return true; }
-    if (Np == 10 && Nfp == 6) { *c = {4, 32}; return true; }
-    if (Np == 4 && Nfp == 3) { *c = {4, 64}; return true; }
-    return false;
+    if (!fe::is_tet_order(Np, Nfp)) return false;
+    // (p = 4, the headline order: groups of up to 8 fields)
+    *c = {Np == 35 ? 8 : 4, fe::with_tet_order(Np, [](auto o) { return 16 * decltype(o)::MF; })};
+    return true;
 }
 
 // Index groups of a two-operand einsum for fe_einsum_contract, from the descriptor's strides alone: an output index
@@ -1659,13 +1751,12 @@ int fe_prepare_operator(int32_t family, const double* op, int32_t Np, int32_t nf
         if (flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "prepare: bad operator flags %d", flags);
         const int opT = (flags & FE_OP_TRANSPOSED) ? 1 : 0;
         info.kind = kPreparedD;
-        switch (Np) {   // the (Np, M) geometries of launch_grad / launch_div
-            case 35: prepare_d<35, 1, 1>(op, prepared, opT, s); break;
-            case 20: prepare_d<20, 2, 1>(op, prepared, opT, s); break;
-            case 10: prepare_d<10, 3, 3>(op, prepared, opT, s); break;
-            case 4: prepare_d<4, 5, 5>(op, prepared, opT, s); break;
-            default: return fail(FE_EUNSUPPORTED, "prepare: grad / div operators of tetrahedra p = 1..4 only (Np=%d)", Np);
-        }
+        if (!fe::is_tet_order(Np)) return fail(FE_EUNSUPPORTED, "prepare: grad / div operators of tetrahedra p = 1..4 only (Np=%d)", Np);
+        fe::with_tet_order(Np, [&](auto o) {
+            using O = decltype(o);
+            prepare_d<O::NP, O::MG, O::MD>(op, prepared, opT, s);
+            return 0;
+        });
     } else if (family == FE_FAMILY_FACEMASS) {
         if (flags & ~(FE_FM_R_IFJ | FE_FM_R_T)) return fail(FE_EINVAL, "prepare: bad face-mass operator flags %d", flags);
         const int rlayout = ((flags & FE_FM_R_IFJ) ? 1 : 0) + ((flags & FE_FM_R_T) ? 2 : 0);
@@ -1673,11 +1764,13 @@ int fe_prepare_operator(int32_t family, const double* op, int32_t Np, int32_t nf
         info.nf = nf;
         info.Nfp = Nfp;
         if (nf != fe::kFmNf) return fail(FE_EUNSUPPORTED, "prepare: face-mass operators of tetrahedra only (nf=%d)", nf);
-        if (Np == 35 && Nfp == 15) prepare_r<35, 15, 1>(op, prepared, rlayout, s);
-        else if (Np == 20 && Nfp == 10) prepare_r<20, 10, 1>(op, prepared, rlayout, s);
-        else if (Np == 10 && Nfp == 6) prepare_r<10, 6, 2>(op, prepared, rlayout, s);
-        else if (Np == 4 && Nfp == 3) prepare_r<4, 3, 4>(op, prepared, rlayout, s);
-        else return fail(FE_EUNSUPPORTED, "prepare: face-mass operators of tetrahedra p = 1..4 only (Np=%d Nfp=%d)", Np, Nfp);
+        if (!fe::is_tet_order(Np, Nfp))
+            return fail(FE_EUNSUPPORTED, "prepare: face-mass operators of tetrahedra p = 1..4 only (Np=%d Nfp=%d)", Np, Nfp);
+        fe::with_tet_order(Np, [&](auto o) {
+            using O = decltype(o);
+            prepare_r<O::NP, O::NFP, O::MF>(op, prepared, rlayout, s);
+            return 0;
+        });
     } else {
         return fail(FE_EUNSUPPORTED, "prepare: family %d has no prepared form", family);
     }
@@ -1780,17 +1873,15 @@ int fe_grad3d_prepared_f64(const double* J, const double* D, const void* D_prepa
     forget_last_launch();
     if (!u || !out) return fail(FE_EINVAL, "grad: null pointer table");
     if (b < 1) return fail(FE_EINVAL, "grad: b=%d, need at least one field", b);
-    if (b > FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch
-        if (int rc = fe_grad3d_prepared_f64(J, D, D_prepared, u, out, E, Np, FE_MAX_FIELDS, op_flags, variant, stream))
-            return rc;
-        return fe_grad3d_prepared_f64(J, D, D_prepared, u + FE_MAX_FIELDS, out + FE_MAX_FIELDS, E, Np, b - FE_MAX_FIELDS,
-                                      op_flags, variant, stream);
-    }
+    if (b > FE_MAX_FIELDS)   // FE_MAX_FIELDS fields per launch
+        return fe::for_each_field_group(b, FE_MAX_FIELDS, false, [&](int k0, int nb) {
+            return fe_grad3d_prepared_f64(J, D, D_prepared, u + k0, out + k0, E, Np, nb, op_flags, variant, stream);
+        });
     int perr;
     const void* prep = usable_prepared(D_prepared, D, kPreparedD, Np, 0, 0, op_flags, "grad", &perr);
     if (perr != FE_OK) return perr;
     for (int k = 0; k < b; ++k)
-        if (int rc = check_common(J, D, u[k], out[k], E, Np)) return rc;
+        if (int rc = check_common("grad", J, D, u[k], out[k], E, Np)) return rc;
     if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "grad: bad operator flags %d", op_flags);
     const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
 #ifdef FE_EXPERIMENTS
@@ -1810,15 +1901,14 @@ int fe_gradplanes3d_f64(const double* const* J3, const double* D, const double* 
     forget_last_launch();
     if (!J3 || !u || !out) return fail(FE_EINVAL, "grad planes: null pointer table");
     if (b < 1) return fail(FE_EINVAL, "grad planes: b=%d, need at least one field", b);
-    if (b > FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch
-        if (int rc = fe_gradplanes3d_f64(J3, D, u, out, E, Np, FE_MAX_FIELDS, op_flags, variant, stream)) return rc;
-        return fe_gradplanes3d_f64(J3, D, u + FE_MAX_FIELDS, out + 3 * FE_MAX_FIELDS, E, Np, b - FE_MAX_FIELDS,
-                                   op_flags, variant, stream);
-    }
+    if (b > FE_MAX_FIELDS)   // FE_MAX_FIELDS fields per launch
+        return fe::for_each_field_group(b, FE_MAX_FIELDS, false, [&](int k0, int nb) {
+            return fe_gradplanes3d_f64(J3, D, u + k0, out + 3 * k0, E, Np, nb, op_flags, variant, stream);
+        });
     if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "grad planes: bad operator flags %d", op_flags);
     if (variant < FE_VARIANT_AUTO || variant > FE_VARIANT_TILED)
         return fail(FE_EUNSUPPORTED, "grad planes: unknown variant %d", variant);
-    if (E < 0) return fail(FE_EINVAL, "E must be >= 0 (got %lld)", (long long)E);
+    if (E < 0) return fail(FE_EINVAL, "grad planes: E must be >= 0 (got %lld)", (long long)E);
     if (E == 0) return FE_OK;   // empty arrays have no addresses to tell wanted planes from unwanted ones
     fe::GradFields P = {};
     int nx = -1;
@@ -1827,7 +1917,7 @@ int fe_gradplanes3d_f64(const double* const* J3, const double* D, const double* 
         for (int x = 0; x < 3; ++x) {
             double* o = out[3 * k + x];
             if (!o) continue;
-            if (int rc = check_common(J3[x], D, u[k], o, E, Np)) return rc;
+            if (int rc = check_common("grad planes", J3[x], D, u[k], o, E, Np)) return rc;
             P.out[k][x] = o;
             ++planes;
         }
@@ -1840,13 +1930,13 @@ int fe_gradplanes3d_f64(const double* const* J3, const double* D, const double* 
     }
     for (int x = 0; x < 3; ++x) {
         if (!J3[x]) return fail(FE_EINVAL, "grad planes: null geometry-factor array %d", x);
-        if (reinterpret_cast<uintptr_t>(J3[x]) & 7u) return fail(FE_EINVAL, "device pointers must be 8-byte aligned");
+        if (reinterpret_cast<uintptr_t>(J3[x]) & 7u) return fail(FE_EINVAL, "grad planes: device pointers must be 8-byte aligned");
         P.j[x] = J3[x];
     }
     // The planes kernel is the row-permuted MFMA grad kernel (tetrahedra p = 1..4).  Whatever it does
     // not serve -- another order, or an explicitly requested tiled / generic variant -- runs plane by
     // plane through the div-component launcher, which has its own MFMA (p = 5), tiled and generic paths.
-    const bool planes_kernel = (Np == 35 || Np == 20 || Np == 10 || Np == 4) &&
+    const bool planes_kernel = fe::is_tet_order(Np) &&
                                (variant == FE_VARIANT_AUTO || variant == FE_VARIANT_MFMA);
     if (Np == 56 && (variant == FE_VARIANT_AUTO || variant == FE_VARIANT_MFMA)) {   // p = 5: grad by components
         bool launched = false;
@@ -1893,18 +1983,16 @@ int fe_div3d_prepared_f64(const double* J, const double* D, const void* D_prepar
     forget_last_launch();
     if (!u || !out) return fail(FE_EINVAL, "div: null pointer table");
     if (b < 1) return fail(FE_EINVAL, "div: b=%d, need at least one field", b);
-    if (b > FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch
-        if (int rc = fe_div3d_prepared_f64(J, D, D_prepared, u, out, E, Np, FE_MAX_FIELDS, op_flags, variant, stream))
-            return rc;
-        return fe_div3d_prepared_f64(J, D, D_prepared, u + FE_MAX_FIELDS, out + FE_MAX_FIELDS, E, Np, b - FE_MAX_FIELDS,
-                                     op_flags, variant, stream);
-    }
+    if (b > FE_MAX_FIELDS)   // FE_MAX_FIELDS fields per launch
+        return fe::for_each_field_group(b, FE_MAX_FIELDS, false, [&](int k0, int nb) {
+            return fe_div3d_prepared_f64(J, D, D_prepared, u + k0, out + k0, E, Np, nb, op_flags, variant, stream);
+        });
     int perr;
     const void* prep = usable_prepared(D_prepared, D, kPreparedD, Np, 0, 0, op_flags, "div", &perr);
     if (perr != FE_OK) return perr;
     fe::FieldPtrs P = {};
     for (int k = 0; k < b; ++k) {
-        if (int rc = check_common(J, D, u[k], out[k], E, Np)) return rc;
+        if (int rc = check_common("div", J, D, u[k], out[k], E, Np)) return rc;
         P.v[k] = u[k];
         P.out[k] = out[k];
     }
@@ -1918,9 +2006,9 @@ int fe_div3d_prepared_f64(const double* J, const double* D, const void* D_prepar
         return fail(FE_EUNSUPPORTED, "div: unknown variant %d", variant);
     if (E == 0) return FE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool mfma_ok = Np == 56 || Np == 35 || Np == 20 || Np == 10 || Np == 4;
+    const bool mfma_ok = Np == 56 || fe::is_tet_order(Np);
     const bool split_walk = variant == FE_VARIANT_MFMA_SPLIT;
-    if (split_walk && !(Np == 35 || Np == 20 || Np == 10 || Np == 4))
+    if (split_walk && !fe::is_tet_order(Np))
         return fail(FE_EUNSUPPORTED, "div: the split walk is a flavour of the p = 1..4 MFMA kernels (Np=%d)", Np);
     const fe::TiledArgs ta = tiled_args(FE_FAMILY_DIV, J, D, P, b, E, 3, Np, 0, 0, opT, 0, 0);
     KernelPath path;
@@ -1940,15 +2028,12 @@ int fe_div3d_prepared_f64(const double* J, const double* D, const void* D_prepar
     int64_t e_done = 0;
     if (path == kPathMfma) {
         const int dbg = variant >= 1000 ? (variant - 1000) & 255 : 0;   // experiment builds only
-        int rc = FE_OK;
         const int opf = opT | (split_walk ? fe::kDivWalkSplit : 0);
-        switch (Np) {   // wave tile = 16 M elements
-            case 35: rc = launch_div<35, 1>(J, D, prep, P, b, E, dbg, opf, s, &e_done); break;
-            case 20: rc = launch_div<20, 1>(J, D, prep, P, b, E, dbg, opf, s, &e_done); break;
-            case 10: rc = launch_div<10, 3>(J, D, prep, P, b, E, dbg, opf, s, &e_done); break;
-            default: rc = launch_div<4, 5>(J, D, prep, P, b, E, dbg, opf, s, &e_done); break;
-        }
-        if (rc != FE_OK) return rc;
+        if (int rc = fe::with_tet_order(Np, [&](auto o) {   // wave tile = 16 M elements
+                using O = decltype(o);
+                return launch_div<O::NP, O::MD>(J, D, prep, P, b, E, dbg, opf, s, &e_done);
+            }))
+            return rc;
     }
     if (e_done < E)
         for (int k = 0; k < b; ++k)
@@ -1972,29 +2057,30 @@ static int nd_launch(int family, const char* what, const double* J, const double
     const bool mfma_ok = Np == 3 || Np == 6 || Np == 10 || Np == 15 || Np == 21;
     const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {
-        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
-        fe::FieldPtrs P = {};
-        for (int k = 0; k < nb; ++k) {
-            if (int rc = check_common(J, D, u[k0 + k], out[k0 + k], E, Np)) return rc;
-            P.v[k] = u[k0 + k];
-            P.out[k] = out[k0 + k];
-        }
-        if (E == 0) continue;
-        const fe::TiledArgs ta = tiled_args(family, J, D, P, nb, E, ndim, Np, 0, 0, opT, 0, 0);
-        KernelPath path;
-        if (int rc = choose_path(variant, mfma_ok, tiled_fits(ta), what, Np, &path)) return rc;
-        bool launched = false;
-        if (path == kPathMfma) {
-            const int rc = family == FE_FAMILY_GRAD ? launch_nd2_np<4>(J, D, P, nb, E, Np, opT, s, &launched)
-                                                    : launch_nd2_np<0>(J, D, P, nb, E, Np, opT, s, &launched);
-            if (rc != FE_OK) return rc;
-        }
-        if (!launched) {   // no MFMA geometry, or fewer elements than one wave tile
-            if (!tiled_fits(ta)) return fail(FE_EUNSUPPORTED, "%s: no kernel for ndim = 2, Np = %d", what, Np);
-            if (int rc = launch_tiled(ta, s)) return rc;
-        }
-    }
+    if (int rc = fe::for_each_field_group(b, fe::kMaxFields, false, [&](int k0, int nb) {
+            fe::FieldPtrs P = {};
+            for (int k = 0; k < nb; ++k) {
+                if (int rc = check_common(what, J, D, u[k0 + k], out[k0 + k], E, Np)) return rc;
+                P.v[k] = u[k0 + k];
+                P.out[k] = out[k0 + k];
+            }
+            if (E == 0) return FE_OK;
+            const fe::TiledArgs ta = tiled_args(family, J, D, P, nb, E, ndim, Np, 0, 0, opT, 0, 0);
+            KernelPath path;
+            if (int rc = choose_path(variant, mfma_ok, tiled_fits(ta), what, Np, &path)) return rc;
+            bool launched = false;
+            if (path == kPathMfma) {
+                const int rc = family == FE_FAMILY_GRAD ? launch_nd2_np<4>(J, D, P, nb, E, Np, opT, s, &launched)
+                                                        : launch_nd2_np<0>(J, D, P, nb, E, Np, opT, s, &launched);
+                if (rc != FE_OK) return rc;
+            }
+            if (!launched) {   // no MFMA geometry, or fewer elements than one wave tile
+                if (!tiled_fits(ta)) return fail(FE_EUNSUPPORTED, "%s: no kernel for ndim = 2, Np = %d", what, Np);
+                if (int rc = launch_tiled(ta, s)) return rc;
+            }
+            return FE_OK;
+        }))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
@@ -2018,7 +2104,7 @@ int fe_divcomp_f64(const double* J, const double* D, const double* u, double* ou
     forget_last_launch();
     if (ndim == 3) return fe_divcomp3d_f64(J, D, u, out, E, Np, op_flags, variant, stream);
     if (ndim != 2) return fail(FE_EUNSUPPORTED, "div component: ndim must be 2 or 3 (got %d)", ndim);
-    if (int rc = check_common(J, D, u, out, E, Np)) return rc;
+    if (int rc = check_common("div component", J, D, u, out, E, Np)) return rc;
     if (op_flags & ~(FE_OP_TRANSPOSED | FE_OP_J_ES))
         return fail(FE_EINVAL, "div component: bad operator flags %d", op_flags);
     if (variant < FE_VARIANT_AUTO || variant > FE_VARIANT_TILED || variant == FE_VARIANT_GENERIC)
@@ -2047,7 +2133,7 @@ int fe_divcomp_f64(const double* J, const double* D, const double* u, double* ou
 int fe_divcomp3d_f64(const double* J, const double* D, const double* u, double* out, int64_t E,
                      int32_t Np, int32_t op_flags, int32_t variant, void* stream) {
     forget_last_launch();
-    if (int rc = check_common(J, D, u, out, E, Np)) return rc;
+    if (int rc = check_common("div component", J, D, u, out, E, Np)) return rc;
     if (op_flags & ~(FE_OP_TRANSPOSED | FE_OP_J_ES))
         return fail(FE_EINVAL, "div component: bad operator flags %d", op_flags);
     if (variant < FE_VARIANT_AUTO || variant > FE_VARIANT_TILED)
@@ -2087,14 +2173,13 @@ int fe_matapply_f64(const double* J, const double* D, const double* const* u, do
     forget_last_launch();
     if (!u || !out) return fail(FE_EINVAL, "matapply: null pointer table");
     if (b < 1) return fail(FE_EINVAL, "matapply: b=%d, need at least one field", b);
-    if (b > FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch
-        if (int rc = fe_matapply_f64(J, D, u, out, E, Np, FE_MAX_FIELDS, op_flags, variant, stream)) return rc;
-        return fe_matapply_f64(J, D, u + FE_MAX_FIELDS, out + FE_MAX_FIELDS, E, Np, b - FE_MAX_FIELDS, op_flags,
-                               variant, stream);
-    }
+    if (b > FE_MAX_FIELDS)   // FE_MAX_FIELDS fields per launch
+        return fe::for_each_field_group(b, FE_MAX_FIELDS, false, [&](int k0, int nb) {
+            return fe_matapply_f64(J, D, u + k0, out + k0, E, Np, nb, op_flags, variant, stream);
+        });
     fe::FieldPtrs P = {};
     for (int k = 0; k < b; ++k) {
-        if (int rc = check_common(J ? J : D, D, u[k], out[k], E, Np)) return rc;   // J is optional
+        if (int rc = check_common("matapply", J ? J : D, D, u[k], out[k], E, Np)) return rc;   // J is optional
         P.v[k] = u[k];
         P.out[k] = out[k];
     }
@@ -2145,12 +2230,11 @@ int fe_graddiv3d_prepared_f64(const double* J, const double* D, const void* D_pr
     int perr;
     const void* prep = usable_prepared(D_prepared, D, kPreparedD, Np, 0, 0, 0, "graddiv", &perr);
     if (perr != FE_OK) return perr;
-    if (int rc = check_common(J, D, u_grad, grad_out, E, Np)) return rc;
-    if (int rc = check_common(J, D, v_div, div_out, E, Np)) return rc;
+    if (int rc = check_common("graddiv", J, D, u_grad, grad_out, E, Np)) return rc;
+    if (int rc = check_common("graddiv", J, D, v_div, div_out, E, Np)) return rc;
     if (variant < FE_VARIANT_AUTO || variant > FE_VARIANT_TILED)
         return fail(FE_EUNSUPPORTED, "graddiv: unknown variant %d", variant);
-    const bool mfma_ok = Np == 35 || Np == 20 || Np == 10 || Np == 4;
-    if ((variant != FE_VARIANT_AUTO && variant != FE_VARIANT_MFMA) || !mfma_ok) {
+    if ((variant != FE_VARIANT_AUTO && variant != FE_VARIANT_MFMA) || !fe::is_tet_order(Np)) {
         // two launches back to back on the stream
         if (int rc = fe_div3d_prepared_f64(J, D, D_prepared, &v_div, &div_out, E, Np, 1, 0, variant, stream)) return rc;
         return fe_grad3d_prepared_f64(J, D, D_prepared, &u_grad, &grad_out, E, Np, 1, 0, variant, stream);
@@ -2161,14 +2245,11 @@ int fe_graddiv3d_prepared_f64(const double* J, const double* D, const void* D_pr
     fe::FieldPtrs Pd = {};
     Pd.v[0] = v_div;  Pd.out[0] = div_out;
     int64_t done_g = 0, done_d = 0;
-    int rc = FE_OK;
-    switch (Np) {   // same (Np, M) geometries as the separate launches
-        case 35: rc = launch_graddiv<35, 1, 1>(J, D, prep, Pg, Pd, E, s, &done_g, &done_d); break;
-        case 20: rc = launch_graddiv<20, 2, 1>(J, D, prep, Pg, Pd, E, s, &done_g, &done_d); break;
-        case 10: rc = launch_graddiv<10, 3, 3>(J, D, prep, Pg, Pd, E, s, &done_g, &done_d); break;
-        default: rc = launch_graddiv<4, 5, 5>(J, D, prep, Pg, Pd, E, s, &done_g, &done_d); break;
-    }
-    if (rc != FE_OK) return rc;
+    if (int rc = fe::with_tet_order(Np, [&](auto o) {
+            using O = decltype(o);
+            return launch_graddiv<O::NP, O::MG, O::MD>(J, D, prep, Pg, Pd, E, s, &done_g, &done_d);
+        }))
+        return rc;
     if (done_d < E)
         hipLaunchKernelGGL(fe::div3d_generic_kernel, dim3(generic_grid(E - done_d, Np)), dim3(256), 0, s,
                            J, D, v_div, div_out, E, Np, done_d, 0);
@@ -2192,31 +2273,17 @@ int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_pre
     int perr;   // (the J layout flag is not part of the operator)
     const void* prep = usable_prepared(R_prepared, R, kPreparedR, Np, nf, Nfp, layout_flags & ~FE_FM_J_FE, "face-mass", &perr);
     if (perr != FE_OK) return perr;
-    if (E < 0) return fail(FE_EINVAL, "E must be >= 0 (got %lld)", (long long)E);
-    if (Np <= 0 || nf <= 0 || Nfp <= 0 || b <= 0)
-        return fail(FE_EINVAL, "face-mass: Np, nf, Nfp, b must be positive (%d %d %d %d)", Np, nf,
-                    Nfp, b);
-    if (layout_flags & ~7) return fail(FE_EINVAL, "face-mass: bad layout flags %d", layout_flags);
-    if (variant < FE_VARIANT_AUTO || variant > FE_VARIANT_TILED)
-        return fail(FE_EUNSUPPORTED, "face-mass: unknown variant %d", variant);
-    if (!v || !out) return fail(FE_EINVAL, "face-mass: null pointer table");
-    if (E == 0) return FE_OK;
-    if (!J || !R) return fail(FE_EINVAL, "face-mass: null device pointer");
-    for (int k = 0; k < b; ++k) {
-        if (!v[k] || !out[k]) return fail(FE_EINVAL, "face-mass: null field pointer %d", k);
-        if ((reinterpret_cast<uintptr_t>(v[k]) | reinterpret_cast<uintptr_t>(out[k])) & 7u)
-            return fail(FE_EINVAL, "face-mass: field pointers must be 8-byte aligned");
-    }
-    if ((reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(R)) & 7u)
-        return fail(FE_EINVAL, "face-mass: device pointers must be 8-byte aligned");
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "E*Np too large");
+    CallCheck c = {"face-mass", J, R, ptr_table(v), ptr_table(out), E, Np, b, layout_flags, 7};
+    c.flag_name = "layout";
+    c.faces = true; c.nf = nf; c.Nfp = Nfp;
+    c.variant = variant; c.variant_hi = FE_VARIANT_TILED;
+    FE_CHECK_CALL(c);
     hipStream_t s = static_cast<hipStream_t>(stream);
 
     FmChoice geo{0, 16};
     const bool mfma_ok = fm_mfma_geometry(Np, nf, Nfp, &geo) && b >= 2;
-    const int jfe = (layout_flags & FE_FM_J_FE) ? 1 : 0;
-    // operator layouts: 0 R[f][i][j], 1 L[i][f][j], 2 R[f][j][i], 3 L[j][f][i]
-    const int rifj = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((layout_flags & FE_FM_R_T) ? 2 : 0);
+    const fe::FmLayout L(layout_flags, Np, nf, Nfp, E);
+    const int jfe = L.jfe, rifj = L.rifj;
     KernelPath path;
     {
         fe::FieldPtrs none = {};
@@ -2228,65 +2295,51 @@ int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_pre
                                  "face-mass (MFMA: tetrahedra p = 1..4 or triangles p = 1..5, b >= 2)", Np, &path))
             return rc;
     }
-    if (path == kPathTiled) {   // groups of up to kMaxFields fields share the staged operator
-        for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {
-            const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
+    if (path == kPathTiled)   // groups of up to kMaxFields fields share the staged operator
+        return fe::for_each_field_group(b, fe::kMaxFields, false, [&](int k0, int nb) {
             fe::FieldPtrs P = {};
             for (int k = 0; k < nb; ++k) { P.v[k] = v[k0 + k]; P.out[k] = out[k0 + k]; }
-            if (int rc = launch_tiled(tiled_args(FE_FAMILY_FACEMASS, J, R, P, nb, E, 3, Np, nf, Nfp, 0, jfe, rifj), s))
-                return rc;
-        }
-        return FE_OK;
-    }
-    const int64_t jEs = jfe ? 1 : nf, jFs = jfe ? E : 1;
-    const int rF = rifj == 0 ? Np * Nfp : rifj == 1 ? Nfp : rifj == 2 ? Nfp * Np : Np;
-    const int rI = rifj == 0 ? Nfp : rifj == 1 ? nf * Nfp : 1;
-    const int rJ = rifj == 0 || rifj == 1 ? 1 : rifj == 2 ? Np : nf * Np;
+            return launch_tiled(tiled_args(FE_FAMILY_FACEMASS, J, R, P, nb, E, 3, Np, nf, Nfp, 0, jfe, rifj), s);
+        });
     const bool use_mfma = path == kPathMfma;
     const int64_t nTiles = use_mfma ? E / geo.tel : 0;      // full wave tiles
     const int64_t e_done = nTiles > 0 ? E : 0;   // an MFMA launch covers the remainder too
-    const int max_group = use_mfma ? geo.max_group : fe::kMaxFields;
     // fields go in groups of up to max_group per launch; never leave a group of 1 for the MFMA kernel
-    for (int k0 = 0; k0 < b;) {
-        int nb = (b - k0 < max_group) ? b - k0 : max_group;
-        if (use_mfma && b - k0 - nb == 1) nb -= 1;
-        const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
-        if (nTiles > 0) {
-            int rc = FE_OK;
-            if (nf == 3) {
-                switch (Np) {   // triangles; wave tile = 16 M elements
-                    case 21: rc = launch_fm<21, 6, 3, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                    case 15: rc = launch_fm<15, 5, 4, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                    case 10: rc = launch_fm<10, 4, 5, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                    case 6: rc = launch_fm<6, 3, 6, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                    default: rc = launch_fm<3, 2, 8, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
+    if (int rc = fe::for_each_field_group(b, use_mfma ? geo.max_group : fe::kMaxFields, use_mfma, [&](int k0, int nb) {
+            const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
+            if (nTiles > 0) {
+                int rc = FE_OK;
+                if (nf == 3) {
+                    switch (Np) {   // triangles; wave tile = 16 M elements
+                        case 21: rc = launch_fm<21, 6, 3, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
+                        case 15: rc = launch_fm<15, 5, 4, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
+                        case 10: rc = launch_fm<10, 4, 5, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
+                        case 6: rc = launch_fm<6, 3, 6, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
+                        default: rc = launch_fm<3, 2, 8, 3>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
+                    }
+                } else if (Np == 56) {   // p = 5: A fragments in LDS
+                    rc = launch_fm<56, 21, 1, fe::kFmNf, true>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s);
+                } else {
+                    rc = fe::with_tet_order(Np, [&](auto o) {
+                        using O = decltype(o);
+                        return launch_fm<O::NP, O::NFP, O::MF>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s);
+                    });
                 }
-            } else {
-                switch (Np) {   // tetrahedra
-                    case 56: rc = launch_fm<56, 21, 1, fe::kFmNf, true>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                    case 35: rc = launch_fm<35, 15, 1>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                    case 20: rc = launch_fm<20, 10, 1>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                    case 10: rc = launch_fm<10, 6, 2>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                    default: rc = launch_fm<4, 3, 4>(J, R, prep, P, nb, E, nTiles, jfe, rifj, s); break;
-                }
+                if (rc != FE_OK) return rc;
             }
-            if (rc != FE_OK) return rc;
-        }
-        if (e_done < E) {
-            const dim3 grid(generic_grid(E - e_done, Np)), block(256);
-#define FE_FM_CASE(NB)                                                                             \
-    case NB:                                                                                       \
-        hipLaunchKernelGGL(fe::facemass_generic_kernel<NB>, grid, block, 0, s, J, R, P, E, Np, nf, \
-                           Nfp, jEs, jFs, rF, rI, rJ, e_done);                                     \
-        break;
-            switch (nb) {
-                FE_FM_CASE(1) FE_FM_CASE(2) FE_FM_CASE(3) FE_FM_CASE(4)
-                FE_FM_CASE(5) FE_FM_CASE(6) FE_FM_CASE(7) FE_FM_CASE(8)
+            if (e_done < E) {
+                const dim3 grid(generic_grid(E - e_done, Np)), block(256);
+                int launched = FE_OK;
+                if (!fe::with_field_count<1, fe::kMaxFields>(nb, &launched, [&](auto NB) {
+                        hipLaunchKernelGGL(fe::facemass_generic_kernel<decltype(NB)::value>, grid, block, 0, s, J, R, P, E, Np, nf, Nfp,
+                                           L.jEs, L.jFs, L.rF, L.rI, L.rJ, e_done);
+                        return FE_OK;
+                    }))
+                    return fail(FE_EINVAL, "face-mass: internal field grouping error (nb=%d)", nb);
             }
-#undef FE_FM_CASE
-        }
-        k0 += nb;
-    }
+            return FE_OK;
+        }))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
@@ -2294,106 +2347,56 @@ int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_pre
 int fe_facemass_acc_f64(const double* J, const double* R, const double* const* v, double* const* out, int64_t E, int32_t Np,
                         int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, double alpha, double beta, void* stream) {
     forget_last_launch();
-    if (E < 0) return fail(FE_EINVAL, "accumulating face-mass: E must be >= 0 (got %lld)", (long long)E);
-    if (Np <= 0 || nf <= 0 || Nfp <= 0 || b <= 0)
-        return fail(FE_EINVAL, "accumulating face-mass: Np, nf, Nfp, b must be positive (%d %d %d %d)", Np, nf, Nfp, b);
-    if (layout_flags & ~7) return fail(FE_EINVAL, "accumulating face-mass: bad layout flags %d", layout_flags);
-    if (!std::isfinite(alpha) || !std::isfinite(beta))
-        return fail(FE_EINVAL, "accumulating face-mass: alpha and beta must be finite (got %g, %g)", alpha, beta);
-    if (!v || !out) return fail(FE_EINVAL, "accumulating face-mass: null pointer table");
-    FmChoice geo{0, 16};
     // the compiled scope: tetrahedra p = 1..4, two or more fields (in groups of 2..4); the caller evaluates anything else into
     // an array of its own and combines with fe_axpby
-    if (nf != fe::kFmNf || Np == 56 || !fm_mfma_geometry(Np, nf, Nfp, &geo) || b < 2)
-        return fail(FE_EUNSUPPORTED, "accumulating face-mass: (nf, Np, Nfp, b) = (%d, %d, %d, %d) has no fused kernel"
-                    " (tetrahedra p = 1..4, b >= 2)", nf, Np, Nfp, b);
-    if (E == 0) return FE_OK;
-    if (!J || !R) return fail(FE_EINVAL, "accumulating face-mass: null device pointer");
-    for (int k = 0; k < b; ++k) {
-        if (!v[k] || !out[k]) return fail(FE_EINVAL, "accumulating face-mass: null field pointer %d", k);
-        if ((reinterpret_cast<uintptr_t>(v[k]) | reinterpret_cast<uintptr_t>(out[k])) & 7u)
-            return fail(FE_EINVAL, "accumulating face-mass: field pointers must be 8-byte aligned");
-    }
-    if ((reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(R)) & 7u)
-        return fail(FE_EINVAL, "accumulating face-mass: device pointers must be 8-byte aligned");
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "accumulating face-mass: E*Np too large");
+    CallCheck c = {"accumulating face-mass", J, R, ptr_table(v), ptr_table(out), E, Np, b, layout_flags, 7};
+    c.flag_name = "layout";
+    c.alpha = &alpha; c.beta = &beta;
+    c.faces = true; c.nf = nf; c.Nfp = Nfp;
+    c.scope = kScopeTetFaces; c.min_b = 2; c.kernel = "fused kernel";
+    FE_CHECK_CALL(c);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int jfe = (layout_flags & FE_FM_J_FE) ? 1 : 0;
-    const int rifj = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((layout_flags & FE_FM_R_T) ? 2 : 0);
-    const int64_t jEs = jfe ? 1 : nf, jFs = jfe ? E : 1;
-    const int rF = rifj == 0 ? Np * Nfp : rifj == 1 ? Nfp : rifj == 2 ? Nfp * Np : Np;
-    const int rI = rifj == 0 ? Nfp : rifj == 1 ? nf * Nfp : 1;
-    const int rJ = rifj == 0 || rifj == 1 ? 1 : rifj == 2 ? Np : nf * Np;
-    const int64_t nTiles = E / geo.tel;   // full wave tiles; the launch covers the elements behind the last one too
+    const fe::FmLayout L(layout_flags, Np, nf, Nfp, E);
     // fields go in groups of up to four per launch; never leave a group of one
-    for (int k0 = 0; k0 < b;) {
-        int nb = b - k0 < 4 ? b - k0 : 4;
-        if (b - k0 - nb == 1) nb -= 1;
-        const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
-        if (nTiles > 0) {
-            int rc = FE_OK;
-            switch (Np) {   // the (Np, Nfp, M) geometries of fe_facemass_f64
-                case 35: rc = launch_fm_acc<35, 15, 1>(J, R, P, nb, E, nTiles, jfe, rifj, alpha, beta, s); break;
-                case 20: rc = launch_fm_acc<20, 10, 1>(J, R, P, nb, E, nTiles, jfe, rifj, alpha, beta, s); break;
-                case 10: rc = launch_fm_acc<10, 6, 2>(J, R, P, nb, E, nTiles, jfe, rifj, alpha, beta, s); break;
-                default: rc = launch_fm_acc<4, 3, 4>(J, R, P, nb, E, nTiles, jfe, rifj, alpha, beta, s); break;
-            }
-            if (rc != FE_OK) return rc;
-        } else {   // fewer elements than a wave tile: one thread per entry
-            const dim3 grid(generic_grid(E, Np)), block(256);
-#define FE_FM_ACC_CASE(NB)                                                                                 \
-    case NB:                                                                                               \
-        hipLaunchKernelGGL(fe::facemass_generic_acc_kernel<NB>, grid, block, 0, s, J, R, P, E, Np, nf, Nfp, \
-                           jEs, jFs, rF, rI, rJ, (int64_t)0, alpha, beta);                                 \
-        break;
-            switch (nb) { FE_FM_ACC_CASE(2) FE_FM_ACC_CASE(3) FE_FM_ACC_CASE(4) }
-#undef FE_FM_ACC_CASE
-        }
-        k0 += nb;
-    }
+    if (int rc = fe::for_each_field_group(b, 4, true, [&](int k0, int nb) {
+            const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
+            return fe::with_tet_order(Np, [&](auto o) {
+                using O = decltype(o);
+                // full wave tiles; the launch covers the elements behind the last one too
+                if (const int64_t nTiles = E / (16 * O::MF))
+                    return launch_fm_acc<O::NP, O::NFP, O::MF>(J, R, P, nb, E, nTiles, L.jfe, L.rifj, alpha, beta, s);
+                int rc = FE_OK;   // fewer elements than a wave tile: one thread per entry
+                if (!fe::with_field_count<2, 4>(nb, &rc, [&](auto NB) {
+                        hipLaunchKernelGGL(fe::facemass_generic_acc_kernel<decltype(NB)::value>, dim3(generic_grid(E, Np)), dim3(256), 0, s,
+                                           J, R, P, E, Np, nf, Nfp, L.jEs, L.jFs, L.rF, L.rI, L.rJ, (int64_t)0, alpha, beta);
+                        return FE_OK;
+                    }))
+                    return fail(FE_EINVAL, "accumulating face-mass: internal field grouping error (nb=%d)", nb);
+                return rc;
+            });
+        }))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
-    return FE_OK;
-}
-
-// the argument checks the two accumulating DG entry points below share (`who`: "accumulating grad" / "accumulating div")
-static int check_acc(const char* who, const double* J, const double* D, const double* u, double* out, int64_t E, int32_t Np,
-                     int32_t op_flags, double alpha, double beta) {
-    if (E < 0) return fail(FE_EINVAL, "%s: E must be >= 0 (got %lld)", who, (long long)E);
-    if (Np <= 0) return fail(FE_EINVAL, "%s: Np must be positive (got %d)", who, Np);
-    if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, op_flags);
-    if (!std::isfinite(alpha) || !std::isfinite(beta))
-        return fail(FE_EINVAL, "%s: alpha and beta must be finite (got %g, %g)", who, alpha, beta);
-    if ((reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(u) |
-         reinterpret_cast<uintptr_t>(out)) & 7u)
-        return fail(FE_EINVAL, "%s: device pointers must be 8-byte aligned", who);
-    // the compiled scope: tetrahedra p = 1..4; the caller evaluates anything else into an array of its own and combines with fe_axpby
-    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
-        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no accumulating kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
-    if (E == 0) return FE_OK;
-    if (!J || !D || !u || !out) return fail(FE_EINVAL, "%s: null device pointer", who);
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
     return FE_OK;
 }
 
 int fe_grad3d_acc_f64(const double* J, const double* D, const double* u, double* out, int64_t E, int32_t Np, int32_t op_flags,
                       double alpha, double beta, void* stream) {
     forget_last_launch();
-    if (int rc = check_acc("accumulating grad", J, D, u, out, E, Np, op_flags, alpha, beta)) return rc;
-    if (E == 0) return FE_OK;
+    // the compiled scope: tetrahedra p = 1..4; the caller evaluates anything else into an array of its own and combines with fe_axpby
+    CallCheck c = {"accumulating grad", J, D, ptr_table(&u), ptr_table(&out), E, Np, 1, op_flags, FE_OP_TRANSPOSED};
+    c.alpha = &alpha; c.beta = &beta;
+    c.scope = kScopeTet; c.kernel = "accumulating kernel";
+    FE_CHECK_CALL(c);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
-    const double* ua[1] = {u};
-    double* oa[1] = {out};
-    const fe::GradFields P = grad_fields(J, ua, oa, 1, E, Np);
+    const fe::GradFields P = grad_fields(J, &u, &out, 1, E, Np);
     bool launched = false;
-    int rc = FE_OK;
-    switch (Np) {   // the (Np, M) geometries of fe_grad3d_f64
-        case 35: rc = launch_grad_acc<35, 1>(P, D, E, opT, alpha, beta, s, &launched); break;
-        case 20: rc = launch_grad_acc<20, 2>(P, D, E, opT, alpha, beta, s, &launched); break;
-        case 10: rc = launch_grad_acc<10, 3>(P, D, E, opT, alpha, beta, s, &launched); break;
-        default: rc = launch_grad_acc<4, 5>(P, D, E, opT, alpha, beta, s, &launched); break;
-    }
-    if (rc != FE_OK) return rc;
+    if (int rc = fe::with_tet_order(Np, [&](auto o) {
+            using O = decltype(o);
+            return launch_grad_acc<O::NP, O::MG>(P, D, E, opT, alpha, beta, s, &launched);
+        }))
+        return rc;
     if (!launched) {   // fewer elements than a wave tile: one thread per entry
         hipLaunchKernelGGL(fe::grad3d_generic_acc_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, u, out, E, Np,
                            (int64_t)0, opT, alpha, beta);
@@ -2405,22 +2408,21 @@ int fe_grad3d_acc_f64(const double* J, const double* D, const double* u, double*
 int fe_div3d_acc_f64(const double* J, const double* D, const double* u, double* out, int64_t E, int32_t Np, int32_t op_flags,
                      double alpha, double beta, void* stream) {
     forget_last_launch();
-    if (int rc = check_acc("accumulating div", J, D, u, out, E, Np, op_flags, alpha, beta)) return rc;
-    if (E == 0) return FE_OK;
+    CallCheck c = {"accumulating div", J, D, ptr_table(&u), ptr_table(&out), E, Np, 1, op_flags, FE_OP_TRANSPOSED};
+    c.alpha = &alpha; c.beta = &beta;
+    c.scope = kScopeTet; c.kernel = "accumulating kernel";
+    FE_CHECK_CALL(c);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
     fe::FieldPtrs P = {};
     P.v[0] = u;
     P.out[0] = out;
     bool launched = false;
-    int rc = FE_OK;
-    switch (Np) {   // the (Np, M) geometries of fe_div3d_f64
-        case 35: rc = launch_div_acc<35, 1>(J, D, P, E, opT, alpha, beta, s, &launched); break;
-        case 20: rc = launch_div_acc<20, 1>(J, D, P, E, opT, alpha, beta, s, &launched); break;
-        case 10: rc = launch_div_acc<10, 3>(J, D, P, E, opT, alpha, beta, s, &launched); break;
-        default: rc = launch_div_acc<4, 5>(J, D, P, E, opT, alpha, beta, s, &launched); break;
-    }
-    if (rc != FE_OK) return rc;
+    if (int rc = fe::with_tet_order(Np, [&](auto o) {
+            using O = decltype(o);
+            return launch_div_acc<O::NP, O::MD>(J, D, P, E, opT, alpha, beta, s, &launched);
+        }))
+        return rc;
     if (!launched) {
         hipLaunchKernelGGL(fe::div3d_generic_acc_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, u, out, E, Np,
                            (int64_t)0, opT, alpha, beta);
@@ -2430,64 +2432,36 @@ int fe_div3d_acc_f64(const double* J, const double* D, const double* u, double* 
 }
 
 // ---- element slices of larger arrays: E elements, plane distances (leading dimensions) of their own.
-// the argument checks the three entry points share; everything here comes before any device work
-static int check_strided(const char* who, const void* J, const void* A, const void* const* in, const void* const* out, int64_t E,
-                         int32_t b, int64_t ldJ, bool ldJ_used, int64_t ldIn, bool ldIn_used, int64_t ldOut, bool ldOut_used) {
-    if (E < 0) return fail(FE_EINVAL, "%s: E must be >= 0 (got %lld)", who, (long long)E);
-    if (b < 1) return fail(FE_EINVAL, "%s: b=%d, need at least one field", who, b);
-    if (!in || !out) return fail(FE_EINVAL, "%s: null pointer table", who);
-    if ((ldJ_used && ldJ < E) || (ldIn_used && ldIn < E) || (ldOut_used && ldOut < E))
-        return fail(FE_EINVAL, "%s: a leading dimension is smaller than E = %lld (ldJ %lld, ldIn %lld, ldOut %lld)", who, (long long)E,
-                    (long long)ldJ, (long long)ldIn, (long long)ldOut);
-    const int64_t ld_max = (int64_t)1 << 40;
-    if ((ldJ_used && ldJ >= ld_max) || (ldIn_used && ldIn >= ld_max) || (ldOut_used && ldOut >= ld_max))
-        return fail(FE_EINVAL, "%s: leading dimension too large", who);
-    uintptr_t bits = reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(A);
-    for (int k = 0; k < b; ++k) bits |= reinterpret_cast<uintptr_t>(in[k]) | reinterpret_cast<uintptr_t>(out[k]);
-    if (bits & 7u) return fail(FE_EINVAL, "%s: device pointers must be 8-byte aligned", who);
-    if (E == 0) return FE_OK;
-    if (!J || !A) return fail(FE_EINVAL, "%s: null device pointer", who);
-    for (int k = 0; k < b; ++k)
-        if (!in[k] || !out[k]) return fail(FE_EINVAL, "%s: null field pointer %d", who, k);
-    return FE_OK;
-}
-
 int fe_grad3d_strided_f64(const double* J, int64_t ldJ, const double* D, const double* const* u, double* const* out, int64_t ldOut,
                           int64_t E, int32_t Np, int32_t b, int32_t op_flags, void* stream) {
     forget_last_launch();
-    const char* who = "grad on an element slice";
-    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
-        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
-    if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, op_flags);
-    if (int rc = check_strided(who, J, D, reinterpret_cast<const void* const*>(u), reinterpret_cast<const void* const*>(out), E, b,
-                               ldJ, true, 0, false, ldOut, true))
-        return rc;
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
-    if (E == 0) return FE_OK;
+    CallCheck c = {"grad on an element slice", J, D, ptr_table(u), ptr_table(out), E, Np, b, op_flags, FE_OP_TRANSPOSED};
+    use_ld(c, 0, ldJ);
+    use_ld(c, 2, ldOut);
+    c.scope = kScopeTet; c.scope_first = true;
+    FE_CHECK_CALL(c);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
-    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // kMaxFields fields per launch
-        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
-        fe::GradFields P = {};
-        for (int x = 0; x < 3; ++x) P.j[x] = J + (int64_t)x * 3 * ldJ;
-        for (int k = 0; k < nb; ++k) {
-            P.u[k] = u[k0 + k];
-            for (int x = 0; x < 3; ++x) P.out[k][x] = out[k0 + k] + (int64_t)x * ldOut * Np;
-        }
-        bool launched = false;
-        int rc = FE_OK;
-        switch (Np) {   // the (Np, M) geometries of fe_grad3d_f64
-            case 35: rc = launch_grad_strided<35, 1>(P, D, nb, E, ldJ, ldOut, opT, s, &launched); break;
-            case 20: rc = launch_grad_strided<20, 2>(P, D, nb, E, ldJ, ldOut, opT, s, &launched); break;
-            case 10: rc = launch_grad_strided<10, 3>(P, D, nb, E, ldJ, ldOut, opT, s, &launched); break;
-            default: rc = launch_grad_strided<4, 5>(P, D, nb, E, ldJ, ldOut, opT, s, &launched); break;
-        }
-        if (rc != FE_OK) return rc;
-        if (!launched)   // fewer elements than a wave tile: one thread per entry
-            for (int k = 0; k < nb; ++k)
-                hipLaunchKernelGGL(fe::grad3d_generic_ld_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, P.u[k], P.out[k][0], E,
-                                   ldJ, ldOut, Np, opT);
-    }
+    if (int rc = fe::for_each_field_group(b, fe::kMaxFields, false, [&](int k0, int nb) {   // kMaxFields fields per launch
+            fe::GradFields P = {};
+            for (int x = 0; x < 3; ++x) P.j[x] = J + (int64_t)x * 3 * ldJ;
+            for (int k = 0; k < nb; ++k) {
+                P.u[k] = u[k0 + k];
+                for (int x = 0; x < 3; ++x) P.out[k][x] = out[k0 + k] + (int64_t)x * ldOut * Np;
+            }
+            bool launched = false;
+            if (int rc = fe::with_tet_order(Np, [&](auto o) {
+                    using O = decltype(o);
+                    return launch_grad_strided<O::NP, O::MG>(P, D, nb, E, ldJ, ldOut, opT, s, &launched);
+                }))
+                return rc;
+            if (!launched)   // fewer elements than a wave tile: one thread per entry
+                for (int k = 0; k < nb; ++k)
+                    hipLaunchKernelGGL(fe::grad3d_generic_ld_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, P.u[k], P.out[k][0],
+                                       E, ldJ, ldOut, Np, opT);
+            return FE_OK;
+        }))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
@@ -2495,34 +2469,28 @@ int fe_grad3d_strided_f64(const double* J, int64_t ldJ, const double* D, const d
 int fe_div3d_strided_f64(const double* J, int64_t ldJ, const double* D, const double* const* u, int64_t ldIn, double* const* out,
                          int64_t E, int32_t Np, int32_t b, int32_t op_flags, void* stream) {
     forget_last_launch();
-    const char* who = "div on an element slice";
-    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
-        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
-    if (op_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, op_flags);
-    if (int rc = check_strided(who, J, D, reinterpret_cast<const void* const*>(u), reinterpret_cast<const void* const*>(out), E, b,
-                               ldJ, true, ldIn, true, 0, false))
-        return rc;
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
-    if (E == 0) return FE_OK;
+    CallCheck c = {"div on an element slice", J, D, ptr_table(u), ptr_table(out), E, Np, b, op_flags, FE_OP_TRANSPOSED};
+    use_ld(c, 0, ldJ);
+    use_ld(c, 1, ldIn);
+    c.scope = kScopeTet; c.scope_first = true;
+    FE_CHECK_CALL(c);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
-    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // kMaxFields fields per launch
-        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
-        const fe::FieldPtrs P = field_group(u + k0, out + k0, nb);
-        bool launched = false;
-        int rc = FE_OK;
-        switch (Np) {   // the (Np, M) geometries of fe_div3d_f64
-            case 35: rc = launch_div_strided<35, 1>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched); break;
-            case 20: rc = launch_div_strided<20, 1>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched); break;
-            case 10: rc = launch_div_strided<10, 3>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched); break;
-            default: rc = launch_div_strided<4, 5>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched); break;
-        }
-        if (rc != FE_OK) return rc;
-        if (!launched)
-            for (int k = 0; k < nb; ++k)
-                hipLaunchKernelGGL(fe::div3d_generic_ld_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, P.v[k], P.out[k], E, ldJ,
-                                   ldIn, Np, opT);
-    }
+    if (int rc = fe::for_each_field_group(b, fe::kMaxFields, false, [&](int k0, int nb) {   // kMaxFields fields per launch
+            const fe::FieldPtrs P = field_group(u + k0, out + k0, nb);
+            bool launched = false;
+            if (int rc = fe::with_tet_order(Np, [&](auto o) {
+                    using O = decltype(o);
+                    return launch_div_strided<O::NP, O::MD>(J, D, P, nb, E, ldJ, ldIn, opT, s, &launched);
+                }))
+                return rc;
+            if (!launched)
+                for (int k = 0; k < nb; ++k)
+                    hipLaunchKernelGGL(fe::div3d_generic_ld_kernel, dim3(generic_grid(E, Np)), dim3(256), 0, s, J, D, P.v[k], P.out[k], E,
+                                       ldJ, ldIn, Np, opT);
+            return FE_OK;
+        }))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
@@ -2530,52 +2498,35 @@ int fe_div3d_strided_f64(const double* J, int64_t ldJ, const double* D, const do
 int fe_facemass_strided_f64(const double* J, int64_t ldJ, const double* R, const double* const* v, int64_t ldIn, double* const* out,
                             int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream) {
     forget_last_launch();
-    const char* who = "face-mass on an element slice";
-    FmChoice geo{0, 16};
     // the compiled scope: tetrahedra p = 1..4, two or more fields (in groups of 2..4)
-    if (nf != fe::kFmNf || Np == 56 || !fm_mfma_geometry(Np, nf, Nfp, &geo) || b == 1)
-        return fail(FE_EUNSUPPORTED, "%s: (nf, Np, Nfp, b) = (%d, %d, %d, %d) has no kernel (tetrahedra p = 1..4, b >= 2)", who, nf, Np,
-                    Nfp, b);
-    if (layout_flags & ~7) return fail(FE_EINVAL, "%s: bad layout flags %d", who, layout_flags);
-    const int jfe = (layout_flags & FE_FM_J_FE) ? 1 : 0;
-    if (int rc = check_strided(who, J, R, reinterpret_cast<const void* const*>(v), reinterpret_cast<const void* const*>(out), E, b,
-                               ldJ, jfe != 0, ldIn, true, 0, false))
-        return rc;
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
-    if (E == 0) return FE_OK;
+    CallCheck c = {"face-mass on an element slice", J, R, ptr_table(v), ptr_table(out), E, Np, b, layout_flags, 7};
+    c.flag_name = "layout";
+    if (layout_flags & FE_FM_J_FE) use_ld(c, 0, ldJ);   // (J[E][nf] has no plane distance)
+    use_ld(c, 1, ldIn);
+    c.faces = true; c.nf = nf; c.Nfp = Nfp;
+    c.scope = kScopeTetFaces; c.min_b = 2; c.scope_first = true;
+    FE_CHECK_CALL(c);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rifj = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((layout_flags & FE_FM_R_T) ? 2 : 0);
-    const int64_t jEs = jfe ? 1 : nf, jFs = jfe ? ldJ : 1;
-    const int rF = rifj == 0 ? Np * Nfp : rifj == 1 ? Nfp : rifj == 2 ? Nfp * Np : Np;
-    const int rI = rifj == 0 ? Nfp : rifj == 1 ? nf * Nfp : 1;
-    const int rJ = rifj == 0 || rifj == 1 ? 1 : rifj == 2 ? Np : nf * Np;
-    const int64_t nTiles = E / geo.tel;   // full wave tiles; the launch covers the elements behind the last one too
+    const fe::FmLayout L(layout_flags, Np, nf, Nfp, ldJ);
     // fields go in groups of up to four per launch; never leave a group of one
-    for (int k0 = 0; k0 < b;) {
-        int nb = b - k0 < 4 ? b - k0 : 4;
-        if (b - k0 - nb == 1) nb -= 1;
-        const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
-        if (nTiles > 0) {
-            int rc = FE_OK;
-            switch (Np) {   // the (Np, Nfp, M) geometries of fe_facemass_f64
-                case 35: rc = launch_fm_strided<35, 15, 1>(J, R, P, nb, E, ldJ, ldIn, nTiles, jfe, rifj, s); break;
-                case 20: rc = launch_fm_strided<20, 10, 1>(J, R, P, nb, E, ldJ, ldIn, nTiles, jfe, rifj, s); break;
-                case 10: rc = launch_fm_strided<10, 6, 2>(J, R, P, nb, E, ldJ, ldIn, nTiles, jfe, rifj, s); break;
-                default: rc = launch_fm_strided<4, 3, 4>(J, R, P, nb, E, ldJ, ldIn, nTiles, jfe, rifj, s); break;
-            }
-            if (rc != FE_OK) return rc;
-        } else {   // fewer elements than a wave tile: one thread per entry
-            const dim3 grid(generic_grid(E, Np)), block(256);
-#define FE_FM_LD_CASE(NB)                                                                                            \
-    case NB:                                                                                                         \
-        hipLaunchKernelGGL(fe::facemass_generic_ld_kernel<NB>, grid, block, 0, s, J, R, P, E, ldIn, Np, nf, Nfp, jEs, \
-                           jFs, rF, rI, rJ);                                                                         \
-        break;
-            switch (nb) { FE_FM_LD_CASE(2) FE_FM_LD_CASE(3) FE_FM_LD_CASE(4) }
-#undef FE_FM_LD_CASE
-        }
-        k0 += nb;
-    }
+    if (int rc = fe::for_each_field_group(b, 4, true, [&](int k0, int nb) {
+            const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
+            return fe::with_tet_order(Np, [&](auto o) {
+                using O = decltype(o);
+                // full wave tiles; the launch covers the elements behind the last one too
+                if (const int64_t nTiles = E / (16 * O::MF))
+                    return launch_fm_strided<O::NP, O::NFP, O::MF>(J, R, P, nb, E, ldJ, ldIn, nTiles, L.jfe, L.rifj, s);
+                int rc = FE_OK;   // fewer elements than a wave tile: one thread per entry
+                if (!fe::with_field_count<2, 4>(nb, &rc, [&](auto NB) {
+                        hipLaunchKernelGGL(fe::facemass_generic_ld_kernel<decltype(NB)::value>, dim3(generic_grid(E, Np)), dim3(256), 0, s,
+                                           J, R, P, E, ldIn, Np, nf, Nfp, L.jEs, L.jFs, L.rF, L.rI, L.rJ);
+                        return FE_OK;
+                    }))
+                    return fail(FE_EINVAL, "face-mass on an element slice: internal field grouping error (nb=%d)", nb);
+                return rc;
+            });
+        }))
+        return rc;
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
 }
@@ -2633,8 +2584,8 @@ int fe_waveop3d_prepared_f64(const double* J, const double* D, const void* D_pre
             return rc;
         return fe_facemass_prepared_f64(Jface, R, R_prepared, f, lift, E, Np, nf, Nfp, b, fm_layout_flags, variant, stream);
     }
-    if (int rc = check_common(J, D, u_grad, grad_out, E, Np)) return rc;
-    if (int rc = check_common(J, D, v_div, div_out, E, Np)) return rc;
+    if (int rc = check_common("waveop", J, D, u_grad, grad_out, E, Np)) return rc;
+    if (int rc = check_common("waveop", J, D, v_div, div_out, E, Np)) return rc;
     if (variant < FE_VARIANT_AUTO || variant > FE_VARIANT_TILED)
         return fail(FE_EUNSUPPORTED, "waveop: unknown variant %d", variant);
     if (!Jface || !R) return fail(FE_EINVAL, "waveop: null device pointer");
@@ -2652,17 +2603,15 @@ int fe_waveop3d_prepared_f64(const double* J, const double* D, const void* D_pre
     fe::WaveOpArgs a = {};
     a.J = J; a.D = D; a.Jf = Jface; a.R = R; a.E = E;
     a.prepD = prepD; a.prepR = prepR;
-    a.jfe = (fm_layout_flags & FE_FM_J_FE) ? 1 : 0;
-    a.rlayout = ((fm_layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((fm_layout_flags & FE_FM_R_T) ? 2 : 0);
+    const fe::FmLayout L(fm_layout_flags, Np, nf, Nfp, E);
+    a.jfe = L.jfe;
+    a.rlayout = L.rifj;
     bool launched = false;
-    int rc = FE_OK;
-    switch (Np) {   // the (Np, M) geometries of the three separate launches
-        case 35: rc = launch_waveop<35, 15, 1, 1, 1>(a, Pg, Pd, Pf, b, s, &launched); break;
-        case 20: rc = launch_waveop<20, 10, 2, 1, 1>(a, Pg, Pd, Pf, b, s, &launched); break;
-        case 10: rc = launch_waveop<10, 6, 3, 3, 2>(a, Pg, Pd, Pf, b, s, &launched); break;
-        default: rc = launch_waveop<4, 3, 5, 5, 4>(a, Pg, Pd, Pf, b, s, &launched); break;
-    }
-    if (rc != FE_OK) return rc;
+    if (int rc = fe::with_tet_order(Np, [&](auto o) {
+            using O = decltype(o);
+            return launch_waveop<O::NP, O::NFP, O::MG, O::MD, O::MF>(a, Pg, Pd, Pf, b, s, &launched);
+        }))
+        return rc;
     if (!launched) {   // fewer elements than any wave tile: the generic kernels
         if (int rc2 = fe_graddiv3d_f64(J, D, u_grad, v_div, grad_out, div_out, E, Np, variant, stream)) return rc2;
         return fe_facemass_f64(Jface, R, f, lift, E, Np, nf, Nfp, b, fm_layout_flags, variant, stream);
@@ -3257,17 +3206,11 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
     if (a->E == 0) return FE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int ndim = a->ndim == 2 ? 2 : 3;
-    // field pointers: the b-field form (v / outs) when given, else the single pair (u / out)
-    const int b = a->b > 0 ? a->b : 1;
-    const double* const* vin = a->v;
-    double* const* vout = a->outs;
-    const double* one_in[1] = {a->u};
-    double* one_out[1] = {a->out};
-    if (!vin || !vout) {
-        if (b != 1) return fail(FE_EINVAL, "fe_launch_f32: b = %d needs the v / outs pointer arrays", b);
-        vin = one_in;
-        vout = one_out;
-    }
+    PackFields fields;
+    if (int rc = pack_fields("fe_launch_f32", a, &fields)) return rc;
+    const int b = fields.b;
+    const double* const* vin = reinterpret_cast<const double* const*>(fields.in);
+    double* const* vout = fields.out;
     int opT = 0, jl = 0, rl = 0, nf = 0, Nfp = 0;
     switch (family) {
         case FE_FAMILY_GRAD:
@@ -3281,13 +3224,15 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
             opT = (a->layout_flags & FE_OP_TRANSPOSED) ? 1 : 0;
             jl = (a->layout_flags & FE_OP_J_ES) ? 1 : 0;
             break;
-        case FE_FAMILY_FACEMASS:
+        case FE_FAMILY_FACEMASS: {
             if (a->nf <= 0 || a->Nfp <= 0) return fail(FE_EINVAL, "fe_launch_f32: face-mass needs nf and Nfp");
             nf = a->nf;
             Nfp = a->Nfp;
-            jl = (a->layout_flags & FE_FM_J_FE) ? 1 : 0;
-            rl = ((a->layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((a->layout_flags & FE_FM_R_T) ? 2 : 0);
+            const fe::FmLayout L(a->layout_flags, a->Np, nf, Nfp, a->E);
+            jl = L.jfe;
+            rl = L.rifj;
             break;
+        }
         default:
             return fail(FE_EUNSUPPORTED, "fe_launch_f32: family %d has no float32 kernel", family);
     }
@@ -3302,18 +3247,21 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
             aligned = aligned && vin[k] && vout[k] && ((reinterpret_cast<uintptr_t>(vin[k]) | reinterpret_cast<uintptr_t>(vout[k])) & 15u) == 0;
         int rc = 1;   // 1: no MFMA launch (no kernel for the shape, unaligned, or too few elements for a wave tile): the tiled kernel below
         if (!aligned) {
-        } else if (family == FE_FAMILY_DIV) {   // the kernel over the geometry (Np, M)
-            rc = a->Np == 35 ? launch_f32_fields<fe::DivF32GeomT<35, 1>, fe::div3d_mfma_f32_kernel<35, 1>>(a, vin, vout, b, opT, "div float32 Np=35", s)
-                 : a->Np == 20 ? launch_f32_fields<fe::DivF32GeomT<20, 1>, fe::div3d_mfma_f32_kernel<20, 1>>(a, vin, vout, b, opT, "div float32 Np=20 M=1", s)
-                 : a->Np == 10 ? launch_f32_fields<fe::DivF32GeomT<10, 3>, fe::div3d_mfma_f32_kernel<10, 3>>(a, vin, vout, b, opT, "div float32 Np=10 M=3", s)
-                 : a->Np == 4 ? launch_f32_fields<fe::DivF32GeomT<4, 5>, fe::div3d_mfma_f32_kernel<4, 5>>(a, vin, vout, b, opT, "div float32 Np=4 M=5", s)
-                              : 1;
-        } else if (family == FE_FAMILY_FACEMASS) {   // the kernel over the geometry (Np, Nfp, M)
-            rc = a->Np == 35 && Nfp == 15 ? launch_f32_facemass<fe::FmF32GeomT<35, 15, 1>, fe::facemass_mfma_f32_kernel<35, 15, 1>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=35", s)
-                 : a->Np == 20 && Nfp == 10 ? launch_f32_facemass<fe::FmF32GeomT<20, 10, 1>, fe::facemass_mfma_f32_kernel<20, 10, 1>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=20 M=1", s)
-                 : a->Np == 10 && Nfp == 6 ? launch_f32_facemass<fe::FmF32GeomT<10, 6, 2>, fe::facemass_mfma_f32_kernel<10, 6, 2>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=10 M=2", s)
-                 : a->Np == 4 && Nfp == 3 ? launch_f32_facemass<fe::FmF32GeomT<4, 3, 4>, fe::facemass_mfma_f32_kernel<4, 3, 4>>(a, vin, vout, b, jl, rl, "face-mass float32 Np=4 M=4", s)
-                                          : 1;
+        } else if (family == FE_FAMILY_DIV) {   // the kernel over the geometry (Np, M) of the float64 div
+            if (fe::is_tet_order(a->Np))
+                rc = fe::with_tet_order(a->Np, [&](auto o) {
+                    using O = decltype(o);
+                    static const What what(O::NP == 35 ? "div float32 Np=%d" : "div float32 Np=%d M=%d", O::NP, O::MD);
+                    return launch_f32_fields<fe::DivF32GeomT<O::NP, O::MD>, fe::div3d_mfma_f32_kernel<O::NP, O::MD>>(a, vin, vout, b, opT, what, s);
+                });
+        } else if (family == FE_FAMILY_FACEMASS) {   // the kernel over the geometry (Np, Nfp, M) of the float64 face-mass
+            if (fe::is_tet_order(a->Np, Nfp))
+                rc = fe::with_tet_order(a->Np, [&](auto o) {
+                    using O = decltype(o);
+                    static const What what(O::NP == 35 ? "face-mass float32 Np=%d" : "face-mass float32 Np=%d M=%d", O::NP, O::MF);
+                    return launch_f32_facemass<fe::FmF32GeomT<O::NP, O::NFP, O::MF>, fe::facemass_mfma_f32_kernel<O::NP, O::NFP, O::MF>>(
+                        a, vin, vout, b, jl, rl, what, s);
+                });
         } else {
             // two 16-element sub-tiles per wave iteration from E = 2e5 on (round 4: 4.5 KB store bursts, two blocks per CU: 68.1 ->
             // 70.5 % of the float32 roofline at 1e6, 70.2 -> 75.5 % at 4e6; below 2e5 the three-blocks-per-CU kernel of one sub-tile
@@ -3335,8 +3283,10 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
         }
         if (rc <= 0) return rc;
     }
-    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {   // groups of up to kMaxFields fields share the staged operator
-        const int nb = b - k0 < fe::kMaxFields ? b - k0 : fe::kMaxFields;
+    // groups of up to kMaxFields fields share the staged operator; a div component is one launch of one field, whatever b
+    // says (the pointers of its first group are still checked)
+    const int walked = family == FE_FAMILY_DIVCOMP && b > fe::kMaxFields ? fe::kMaxFields : b;
+    return fe::for_each_field_group(walked, fe::kMaxFields, false, [&](int k0, int nb) {
         fe::FieldPtrs P = {};
         for (int k = 0; k < nb; ++k) {
             if (!vin[k0 + k] || !vout[k0 + k]) return fail(FE_EINVAL, "fe_launch_f32: null field pointer");
@@ -3345,10 +3295,8 @@ int fe_launch_f32(int32_t family, const fe_argpack* a, void* stream) {
         }
         const fe::TiledArgs ta = tiled_args(family, a->J, a->D, P, family == FE_FAMILY_DIVCOMP ? 1 : nb, a->E,
                                             family == FE_FAMILY_MATAPPLY ? 1 : ndim, a->Np, nf, Nfp, opT, jl, rl);
-        if (int rc = launch_tiled_t<float>(ta, s)) return rc;
-        if (family == FE_FAMILY_DIVCOMP) break;
-    }
-    return FE_OK;
+        return launch_tiled_t<float>(ta, s);
+    });
 }
 
 // float32 fields, float64 J / operator / outputs (fe_mixed.h)
@@ -3356,97 +3304,68 @@ int fe_div3d_mixed_f64(const double* J, const double* D, const void* const* fiel
                        int32_t b, int32_t layout_flags, void* stream) {
     forget_last_launch();
     const float* const* v = reinterpret_cast<const float* const*>(fields);
-    const char* who = "div, float32 fields";
-    if (int rc = check_mixed(who, J, D, v, outs, E, Np, b)) return rc;
-    if (layout_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, layout_flags);
-    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
-        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
-    if (E == 0) return FE_OK;
-    if (!J || !D) return fail(FE_EINVAL, "%s: null device pointer", who);
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    CallCheck c = {"div, float32 fields", J, D, fields, ptr_table(outs), E, Np, b, layout_flags, FE_OP_TRANSPOSED};
+    c.in_align = 4;
+    c.scope = kScopeTet;
+    FE_CHECK_CALL(c);
     bool plain = false;   // a plane x E Np floats behind a field's start that is not on an 8-byte boundary: no LDS-DMA for the fields
-    for (int k = 0; k < b; ++k) {
-        if (!v[k] || !outs[k]) return fail(FE_EINVAL, "%s: null field pointer %d", who, k);
+    for (int k = 0; k < b; ++k)
         for (int x = 0; x < 3; ++x) plain = plain || ((reinterpret_cast<uintptr_t>(v[k]) + (uintptr_t)x * (uintptr_t)E * Np * 4u) & 7u) != 0;
-    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int opT = (layout_flags & FE_OP_TRANSPOSED) ? 1 : 0;
-#define FE_MIXED_DIV(NP, M)                                                                                                   \
-    launch_mixed_fields<fe::DivMixedGeomT<NP, M>, fe::div3d_mixed_kernel<NP, M, false>, fe::div3d_mixed_kernel<NP, M, true>>( \
-        J, D, v, outs, b, E, opT, plain, "div float32 fields Np=" #NP " M=" #M, "div float32 fields Np=" #NP " M=" #M ", plain loads", s)
-    switch (Np) {   // the (Np, M) geometries of fe_div3d_f64
-        case 35: return FE_MIXED_DIV(35, 1);
-        case 20: return FE_MIXED_DIV(20, 1);
-        case 10: return FE_MIXED_DIV(10, 3);
-        default: return FE_MIXED_DIV(4, 5);
-    }
-#undef FE_MIXED_DIV
+    return fe::with_tet_order(Np, [&](auto o) {
+        using O = decltype(o);
+        static const What what("div float32 fields Np=%d M=%d", O::NP, O::MD),
+            what_plain("div float32 fields Np=%d M=%d, plain loads", O::NP, O::MD);
+        return launch_mixed_fields<fe::DivMixedGeomT<O::NP, O::MD>, fe::div3d_mixed_kernel<O::NP, O::MD, false>,
+                                   fe::div3d_mixed_kernel<O::NP, O::MD, true>>(J, D, v, outs, b, E, opT, plain, what, what_plain, s);
+    });
 }
 
 int fe_grad3d_mixed_f64(const double* J, const double* D, const void* const* fields, double* const* outs, int64_t E, int32_t Np,
                         int32_t b, int32_t layout_flags, void* stream) {
     forget_last_launch();
     const float* const* v = reinterpret_cast<const float* const*>(fields);
-    const char* who = "grad, float32 fields";
-    if (int rc = check_mixed(who, J, D, v, outs, E, Np, b)) return rc;
-    if (layout_flags & ~FE_OP_TRANSPOSED) return fail(FE_EINVAL, "%s: bad operator flags %d", who, layout_flags);
-    if (!(Np == 35 || Np == 20 || Np == 10 || Np == 4))
-        return fail(FE_EUNSUPPORTED, "%s: Np = %d has no kernel (tetrahedra p = 1..4: Np = 4, 10, 20, 35)", who, Np);
-    if (E == 0) return FE_OK;
-    if (!J || !D) return fail(FE_EINVAL, "%s: null device pointer", who);
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    CallCheck c = {"grad, float32 fields", J, D, fields, ptr_table(outs), E, Np, b, layout_flags, FE_OP_TRANSPOSED};
+    c.in_align = 4;
+    c.scope = kScopeTet;
+    FE_CHECK_CALL(c);
     bool plain = false;   // a field that does not start on an 8-byte boundary: no LDS-DMA for the fields
-    for (int k = 0; k < b; ++k) {
-        if (!v[k] || !outs[k]) return fail(FE_EINVAL, "%s: null field pointer %d", who, k);
-        plain = plain || (reinterpret_cast<uintptr_t>(v[k]) & 7u) != 0;
-    }
+    for (int k = 0; k < b; ++k) plain = plain || (reinterpret_cast<uintptr_t>(v[k]) & 7u) != 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int opT = (layout_flags & FE_OP_TRANSPOSED) ? 1 : 0;
-#define FE_MIXED_GRAD(NP, M)                                                                                                     \
-    launch_mixed_fields<fe::GradMixedGeomT<M, NP>, fe::grad3d_mixed_kernel<M, NP, false>, fe::grad3d_mixed_kernel<M, NP, true>>( \
-        J, D, v, outs, b, E, opT, plain, "grad float32 fields Np=" #NP " M=" #M, "grad float32 fields Np=" #NP " M=" #M ", plain loads", s)
-    switch (Np) {   // the (Np, M) geometries of fe_grad3d_f64
-        case 35: return FE_MIXED_GRAD(35, 1);
-        case 20: return FE_MIXED_GRAD(20, 2);
-        case 10: return FE_MIXED_GRAD(10, 3);
-        default: return FE_MIXED_GRAD(4, 5);
-    }
-#undef FE_MIXED_GRAD
+    return fe::with_tet_order(Np, [&](auto o) {
+        using O = decltype(o);
+        static const What what("grad float32 fields Np=%d M=%d", O::NP, O::MG),
+            what_plain("grad float32 fields Np=%d M=%d, plain loads", O::NP, O::MG);
+        return launch_mixed_fields<fe::GradMixedGeomT<O::MG, O::NP>, fe::grad3d_mixed_kernel<O::MG, O::NP, false>,
+                                   fe::grad3d_mixed_kernel<O::MG, O::NP, true>>(J, D, v, outs, b, E, opT, plain, what, what_plain, s);
+    });
 }
 
 int fe_facemass_mixed_f64(const double* J, const double* R, const void* const* fields, double* const* outs, int64_t E, int32_t Np,
                           int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream) {
     forget_last_launch();
     const float* const* v = reinterpret_cast<const float* const*>(fields);
-    const char* who = "face-mass, float32 fields";
-    if (int rc = check_mixed(who, J, R, v, outs, E, Np, b)) return rc;
-    if (nf <= 0 || Nfp <= 0) return fail(FE_EINVAL, "%s: nf and Nfp must be positive (got %d, %d)", who, nf, Nfp);
-    if (layout_flags & ~7) return fail(FE_EINVAL, "%s: bad layout flags %d", who, layout_flags);
-    if (!(nf == 4 && ((Np == 35 && Nfp == 15) || (Np == 20 && Nfp == 10) || (Np == 10 && Nfp == 6) || (Np == 4 && Nfp == 3))))
-        return fail(FE_EUNSUPPORTED, "%s: (nf, Np, Nfp) = (%d, %d, %d) has no kernel (tetrahedra p = 1..4)", who, nf, Np, Nfp);
-    if (E == 0) return FE_OK;
-    if (!J || !R) return fail(FE_EINVAL, "%s: null device pointer", who);
-    if (E * (int64_t)Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large", who);
+    CallCheck c = {"face-mass, float32 fields", J, R, fields, ptr_table(outs), E, Np, b, layout_flags, 7};
+    c.flag_name = "layout";
+    c.in_align = 4;
+    c.faces = true; c.nf = nf; c.Nfp = Nfp;
+    c.scope = kScopeTetFaces;
+    FE_CHECK_CALL(c);
     bool plain = false;   // a face slab f E Nfp floats behind a field's start that is not on an 8-byte boundary
-    for (int k = 0; k < b; ++k) {
-        if (!v[k] || !outs[k]) return fail(FE_EINVAL, "%s: null field pointer %d", who, k);
+    for (int k = 0; k < b; ++k)
         for (int f = 0; f < 4; ++f) plain = plain || ((reinterpret_cast<uintptr_t>(v[k]) + (uintptr_t)f * (uintptr_t)E * Nfp * 4u) & 7u) != 0;
-    }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int jl = (layout_flags & FE_FM_J_FE) ? 1 : 0;
-    const int rl = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) + ((layout_flags & FE_FM_R_T) ? 2 : 0);
-#define FE_MIXED_FM(NP, NFP, M)                                                                                     \
-    launch_mixed_facemass<fe::FmMixedGeomT<NP, NFP, M>, fe::facemass_mixed_kernel<NP, NFP, M, false>,               \
-                          fe::facemass_mixed_kernel<NP, NFP, M, true>>(J, R, v, outs, b, E, jl, rl, plain,          \
-                                                                       "face-mass float32 fields Np=" #NP " M=" #M, \
-                                                                       "face-mass float32 fields Np=" #NP " M=" #M ", plain loads", s)
-    switch (Np) {   // the (Np, Nfp, M) geometries of fe_facemass_f64
-        case 35: return FE_MIXED_FM(35, 15, 1);
-        case 20: return FE_MIXED_FM(20, 10, 1);
-        case 10: return FE_MIXED_FM(10, 6, 2);
-        default: return FE_MIXED_FM(4, 3, 4);
-    }
-#undef FE_MIXED_FM
+    const fe::FmLayout L(layout_flags, Np, nf, Nfp, E);
+    return fe::with_tet_order(Np, [&](auto o) {
+        using O = decltype(o);
+        static const What what("face-mass float32 fields Np=%d M=%d", O::NP, O::MF),
+            what_plain("face-mass float32 fields Np=%d M=%d, plain loads", O::NP, O::MF);
+        return launch_mixed_facemass<fe::FmMixedGeomT<O::NP, O::NFP, O::MF>, fe::facemass_mixed_kernel<O::NP, O::NFP, O::MF, false>,
+                                     fe::facemass_mixed_kernel<O::NP, O::NFP, O::MF, true>>(J, R, v, outs, b, E, L.jfe, L.rifj, plain, what,
+                                                                                            what_plain, s);
+    });
 }
 
 int fe_launch(int32_t family, const fe_argpack* a, void* stream) {
@@ -3456,19 +3375,11 @@ int fe_launch(int32_t family, const fe_argpack* a, void* stream) {
         if (base != FE_FAMILY_GRAD && base != FE_FAMILY_DIV && base != FE_FAMILY_FACEMASS)
             return fail(FE_EUNSUPPORTED, "fe_launch: family 0x%x has no kernel for float32 fields (float64 grad, div and face-mass "
                         "of tetrahedra; not together with FE_FAMILY_F32 or FE_FAMILY_ACC)", base);
-        const int b = a->b > 0 ? a->b : 1;
-        const void* one_in[1] = {a->u};
-        double* one_out[1] = {a->out};
-        const void* const* v = reinterpret_cast<const void* const*>(a->v);
-        double* const* outs = a->outs;
-        if (!v || !outs) {
-            if (b != 1) return fail(FE_EINVAL, "fe_launch: b = %d needs the v / outs pointer arrays", b);
-            v = one_in;
-            outs = one_out;
-        }
-        if (base == FE_FAMILY_GRAD) return fe_grad3d_mixed_f64(a->J, a->D, v, outs, a->E, a->Np, b, a->layout_flags, stream);
-        if (base == FE_FAMILY_DIV) return fe_div3d_mixed_f64(a->J, a->D, v, outs, a->E, a->Np, b, a->layout_flags, stream);
-        return fe_facemass_mixed_f64(a->J, a->D, v, outs, a->E, a->Np, a->nf, a->Nfp, b, a->layout_flags, stream);
+        PackFields f;
+        if (int rc = pack_fields("fe_launch", a, &f)) return rc;
+        if (base == FE_FAMILY_GRAD) return fe_grad3d_mixed_f64(a->J, a->D, f.in, f.out, a->E, a->Np, f.b, a->layout_flags, stream);
+        if (base == FE_FAMILY_DIV) return fe_div3d_mixed_f64(a->J, a->D, f.in, f.out, a->E, a->Np, f.b, a->layout_flags, stream);
+        return fe_facemass_mixed_f64(a->J, a->D, f.in, f.out, a->E, a->Np, a->nf, a->Nfp, f.b, a->layout_flags, stream);
     }
     if (family & FE_FAMILY_ACC) {   // out <- alpha * E + beta * out
         const int32_t base = family & ~FE_FAMILY_ACC;
@@ -3517,7 +3428,7 @@ int fe_launch(int32_t family, const fe_argpack* a, void* stream) {
         case FE_FAMILY_FACEMASS:
             return fe_facemass_prepared_f64(a->J, a->D, a->prepared, a->v, a->outs, a->E, a->Np, a->nf, a->Nfp, a->b,
                                             a->layout_flags, a->variant, stream);
-        default: return fail(FE_EINVAL, "unknown family %d", family);
+        default: return fail(FE_EINVAL, "fe_launch: unknown family %d", family);
     }
 }
 
@@ -3645,13 +3556,9 @@ int fe_facemass_adj_f64(const double* J, const double* R, const double* const* g
     if (E == 0) return FE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // R's strides of (f, i, j): 'fij', 'ifj', 'fji', 'jfi' (as the face-mass kernels read it)
-    const int rl = ((layout_flags & FE_FM_R_IFJ) ? 1 : 0) | ((layout_flags & FE_FM_R_T) ? 2 : 0);
-    const int sF = rl == 0 ? Np * Nfp : rl == 1 ? Nfp : rl == 2 ? Nfp * Np : Np;
-    const int sI = rl == 0 ? Nfp : rl == 1 ? nf * Nfp : 1;
-    const int sJ = rl == 0 || rl == 1 ? 1 : rl == 2 ? Np : nf * Np;
-    const bool jfe = (layout_flags & FE_FM_J_FE) != 0;
-    for (int k0 = 0; k0 < b; k0 += FE_MAX_FIELDS) {   // FE_MAX_FIELDS fields per launch; dJ accumulates over launches
-        const int nb = std::min(b - k0, FE_MAX_FIELDS);
+    const fe::FmLayout L(layout_flags, Np, nf, Nfp, E);
+    // FE_MAX_FIELDS fields per launch; dJ accumulates over launches
+    return fe::for_each_field_group(b, FE_MAX_FIELDS, false, [&](int k0, int nb) {
         fe::FmAdjArgs a = {};
         a.J = J;
         a.R = R;
@@ -3662,9 +3569,9 @@ int fe_facemass_adj_f64(const double* J, const double* R, const double* const* g
         }
         a.dJ = with_dJ ? dJ : nullptr;
         a.E = E;
-        a.sje = jfe ? 1 : nf;
-        a.sjf = jfe ? E : 1;
-        a.sF = sF, a.sI = sI, a.sJ = sJ;
+        a.sje = L.jEs;
+        a.sjf = L.jFs;
+        a.sF = L.rF, a.sI = L.rI, a.sJ = L.rJ;
         a.nb = nb;
         a.with_dv = with_dv ? 1 : 0;
         a.accumulate = k0 > 0 ? 1 : 0;
@@ -3680,9 +3587,8 @@ int fe_facemass_adj_f64(const double* J, const double* R, const double* const* g
             case 7: rc = launch_facemass_adj<15, 5, 3>(a, s); break;
             default: rc = launch_facemass_adj<21, 6, 3>(a, s); break;
         }
-        if (rc != FE_OK) return rc;
-    }
-    return FE_OK;
+        return rc;
+    });
 }
 
 }  // extern "C"
