@@ -312,6 +312,9 @@ def waveop3d(J: int, D: int, u_grad: int, grad_out: int, v_div: int, div_out: in
 
 def facemass(J: int, R: int, v: Sequence[int], out: Sequence[int], E: int, Np: int, nf: int,
              Nfp: int, layout_flags: int = 0, variant=None, stream: int = 0) -> None:
+    """``out_k[e,i] = sum_fj J[e,f] R[f,i,j] v_k[f,e,j]`` for ``len(v)`` fields (fe_facemass_f64).  On the matrix cores for
+    tetrahedra and triangles p = 1..5 and any number of fields: one field runs the single-field kernel, with the bits it has as
+    a member of a larger call."""
     if len(v) != len(out):
         raise InvalidParameterError("face-mass: need as many outputs as fields")
     check(load_library().fe_facemass_f64(J, R, _ptr_array(v), _ptr_array(out), E, Np, nf, Nfp,

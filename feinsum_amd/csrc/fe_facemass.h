@@ -17,6 +17,7 @@
 // through a separate LDS transposition buffer as contiguous 16-byte-per-lane stores.  Loads for
 // unit m+2 are issued as soon as unit m's B fragments are in registers, i.e. BEFORE unit m's
 // MFMAs and stores, so the counted vmcnt at the top of a unit never waits for stores.
+// A launch of ONE field (NB = 1) has the same units, one per tile: slabs two tiles ahead, J one tile ahead.
 #pragma once
 #include "fe_generic.h"
 #include "fe_grad.h"
@@ -109,10 +110,31 @@ __device__ __forceinline__ void fm_issue_unit_loads(const double* __restrict__ J
     }
 }
 
+// J_INSTR x 16-byte LDS-DMA for the J tile alone, as the tail of fm_issue_unit_loads<.., kWithJ = true> issues it: the launch of
+// one field requests J apart from the slabs (facemass_mfma_body, NB == 1).  (A copy, not a part factored out of
+// fm_issue_unit_loads: a first form that shared it, and the unit's MFMA / store block, through helpers changed the
+// instruction streams of 129 existing kernels -- profiles/facemass_single/device_code.txt.)
+template <int NP, int NFP, int M, int NF = kFmNf, bool ALDS = false, bool W8 = false>
+__device__ __forceinline__ void fm_issue_j_loads(const double* __restrict__ J, int64_t E, int64_t tile, int lane,
+                                                 unsigned lds_j, int jfe) {
+    using G = FmGeom<NP, NFP, M, NF, ALDS, W8>;
+    const int64_t e0 = tile * G::TEL;
+    const char* jb = reinterpret_cast<const char*>(J);
+#pragma unroll
+    for (int c = 0; c < G::J_INSTR; ++c) {
+        const int q = c * 64 + lane;                       // 16-byte chunk of the J tile
+        const int row = q / (G::TEL / 2), col = q - row * (G::TEL / 2);   // "fe": NF rows of TEL doubles
+        const char* src = jfe ? jb + ((int64_t)row * E + e0) * 8 + col * 16 : jb + e0 * (NF * 8) + q * 16;
+        if ((c + 1) * 64 <= G::J_CHUNKS || q < G::J_CHUNKS) glds16(src, lds_j + c * 1024);
+    }
+}
+
 // bid / nblk: see grad3d_mfma_body.
 // kPrep (register-resident fragments only): the A fragments come from a prepared operator (`prep` =
 // the whole prepared buffer: fragments ks BT + t of the 16-row tiles, then BT KS + ks NS + q of the
 // 4-row groups); no LDS staging and no block barrier.  R itself is still needed by the remainder code.
+// NB == 1 (one field; register fragments, or ALDS with W8): every unit is a tile start -- the slabs two TILES ahead, J one; see
+// the block of one field below.  Its kDyn asks for a ticket one unit before the prefetch that needs the tile.
 // kDyn (register fragments, NB >= 3): behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk): the
 // ticket for the next tile is asked for with unit 0 of a tile and read with unit NB - 2, whose prefetch is the next tile's
 // first unit; `tail` = the launch's counters (null: static walk), `t_static` = statically walked tiles.
@@ -139,11 +161,12 @@ __device__ __forceinline__ void facemass_mfma_body(
     const int jfe = jfe_flags & 1;   // J stored [nf][E]; bit kOpLoadsTemporal: the field slabs by plain loads (fe_common.h)
     static_assert(!kPrep || !ALDS, "prepared operators: fragments in registers");
     static_assert(!kAcc || (!ALDS && !W8 && !kPrep && !kDyn), "accumulating launches: register fragments, static walk");
-    static_assert(!kDyn || (NB >= 3 && !ALDS && !W8 && !kPrep) || (NB >= 2 && ALDS && W8),
-                  "dynamic walk: three or more fields with the fragments in registers, or the eight-wave blocks (p = 5)");
+    static_assert(!kDyn || ((NB >= 3 || NB == 1) && !ALDS && !W8 && !kPrep) || (NB >= 2 && ALDS && W8),
+                  "dynamic walk: one field or three and more with the fragments in registers, or the eight-wave blocks (p = 5)");
     using G = FmGeom<NP, NFP, M, NF, ALDS, W8>;
     using WaveLds = typename G::WaveLds;
-    static_assert(NB >= 2 && NB <= kMaxFields, "2..8 fields per launch");
+    static_assert(NB >= 1 && NB <= kMaxFields, "1..8 fields per launch");
+    static_assert(NB >= 2 || (!kPrep && !kAcc && !kLd), "one field: the plain operator, contiguous arrays, no accumulation");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -196,7 +219,12 @@ __device__ __forceinline__ void facemass_mfma_body(
             if (wave * (int)sizeof(WaveLds) >= G::OP_D * 8 && first_ < nTiles) {
                 const unsigned lv = lds_addr_uniform(L->v[0]), lj = lds_addr_uniform(L->j);
                 FM_ISSUE(true, P.v[0], first_, lv, lj);
-                FM_ISSUE(false, P.v[1], first_, lv + G::UNIT_D * 8, lj);
+                if constexpr (NB == 1) {   // one field: the second unit is the wave's second tile (see the walk of one field)
+                    const int64_t second_ = first_ + (int64_t)nblk * G::WAVES;
+                    if (second_ < nTiles) { FM_ISSUE(false, P.v[0], second_, lv + G::UNIT_D * 8, lj); }
+                } else {
+                    FM_ISSUE(false, P.v[1], first_, lv + G::UNIT_D * 8, lj);
+                }
                 first_requested = true;
             }
         }
@@ -360,6 +388,144 @@ __device__ __forceinline__ void facemass_mfma_body(
         return;
     }
 
+    if constexpr (NB == 1) {
+        // ---- one field: every unit is a tile start, so the ring of field slabs runs two TILES ahead and the single J buffer one:
+        //      J of the next tile is requested once jv of the current one is in registers.  Vector-memory operations of unit m in
+        //      issue order: [report] [ticket] J(m+1) L(m+2) S(m), behind the prologue's L(0) J(0) L(1) [ticket].  The wait at the
+        //      top of unit m is for J(m), the youngest it needs; younger than that are L(m+1), where there is such a tile, and
+        //      S(m-1).  A wave's first unit waits for everything.
+        //      Static walk: tile m of a wave is first + m stride.  Dynamic walk (fe_common.h): every wave has two static tiles
+        //      (t_static is two rounds or more); a tile is needed two units ahead, for its prefetch, so its ticket is asked for
+        //      a unit earlier still -- in unit m - 1, or the prologue, for tile m + 2 -- and read in unit m behind the top wait,
+        //      which has waited for it: it is older than J(m).  One ticket is under way at a time (v255).
+        //      The arithmetic and the store of a unit are those of the loop below, statement for statement.
+        const bool younger_half = bid >= (nblk + 1) / 2;
+        int iteration = 0;
+        const bool dyn = kDyn && tail != nullptr && t_static < nTiles;   // grid-uniform
+        const int pool = (bid >> 3) & (kTailPools - 1);
+        unsigned* const counter = tail_pool_counters(tail, pool);
+        unsigned* const done = tail_pool_reports(counter);
+        bool reported = false, pending = false;
+        // the tile behind t: tEnd = none, -1 = by a ticket yet to be asked for
+        auto after = [&](int64_t t) -> int64_t {
+            if (t >= tEnd) return tEnd;
+            if (!dyn) return t + stride < tEnd ? t + stride : tEnd;
+            return (t < t_static && t + stride < t_static) ? t + stride : (int64_t)-1;
+        };
+        int64_t t0 = first, t1 = first + stride < tEnd ? first + stride : tEnd;
+        if (!first_requested) {
+            FM_ISSUE(true, P.v[0], t0, lds_v0, lds_j);
+            if (t1 < tEnd) { FM_ISSUE(false, P.v[0], t1, lds_v0 + G::UNIT_D * 8, lds_j); }
+        }
+        int64_t t2 = after(t1);
+        if constexpr (kDyn) {
+            if (t2 < 0) {
+                tail_request<0>(counter);
+                pending = true;
+            }
+        }
+        int slot = 0;
+        bool cold = true;
+        while (t0 < tEnd) {
+            balance_priority(younger_half, iteration++);
+            if (cold) wait_vmcnt<0>();
+            else if (t1 < tEnd) wait_vmcnt<G::UNIT_LOADS + G::UNIT_STORES>();
+            else wait_vmcnt<G::UNIT_STORES>();
+            cold = false;
+
+            const double* vs = L->v[slot];
+            double bfrag[M][G::KS];
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+#pragma unroll
+                for (int ks = 0; ks < G::KS; ++ks)
+                    bfrag[m][ks] = L->j[joff[ks] + (jfe ? 16 * m : 16 * m * NF)] * vs[voff[ks] + 16 * m * NFP];
+            // the slab and the J tile are in registers before their buffers are handed back to the DMA engine
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+#pragma unroll
+                for (int ks = 0; ks < G::KS; ++ks) asm volatile("" : "+v"(bfrag[m][ks]));
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+            if constexpr (kDyn) {
+                if (pending) {   // asked for a unit ago; younger than the request: J(m), L(m+1), S(m-1)
+                    const int64_t x = tail_ticket_tile(tail_wait<G::UNIT_LOADS + G::UNIT_STORES, 0>(), t_static, pool, tEnd);
+                    pending = false;
+                    t2 = x >= 0 ? x : tEnd;
+                    if (x < 0) {   // this wave's pool is empty: stop asking, report
+                        tail_request<1>(done);
+                        reported = true;
+                    }
+                }
+            }
+            const int64_t t3 = after(t2);
+            if constexpr (kDyn) {
+                if (t3 < 0) {
+                    tail_request<0>(counter);
+                    pending = true;
+                }
+            }
+            if (t1 < tEnd) fm_issue_j_loads<NP, NFP, M, NF, ALDS, W8>(J, E, t1, lane, lds_j, jfe);
+            if (t2 < tEnd) { FM_ISSUE(false, P.v[0], t2, lds_v0 + slot * (G::UNIT_D * 8), lds_j); }
+
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                v4d acc[G::BT > 0 ? G::BT : 1];
+                double accs[G::NS > 0 ? G::NS : 1];
+#pragma unroll
+                for (int t = 0; t < G::BT; ++t) acc[t] = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int q = 0; q < G::NS; ++q) accs[q] = 0.0;
+#pragma unroll
+                for (int ks = 0; ks < G::KS; ++ks) {
+#pragma unroll
+                    for (int t = 0; t < G::BT; ++t)
+                        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_big(t, ks), bfrag[m][ks], acc[t], 0, 0, 0);
+#pragma unroll
+                    for (int q = 0; q < G::NS; ++q)
+                        accs[q] = __builtin_amdgcn_mfma_f64_4x4x4f64(a_small(q, ks), bfrag[m][ks], accs[q], 0, 0, 0);
+                }
+                double* ob = L->o;
+#pragma unroll
+                for (int t = 0; t < G::BT; ++t)
+#pragma unroll
+                    for (int qq = 0; qq < 4; ++qq) ob[tile_index<NP>(n, 16 * t + g + 4 * qq)] = acc[t][qq];
+#pragma unroll
+                for (int q = 0; q < G::NS; ++q) {
+                    const int i = 16 * G::BT + 4 * q + g;
+                    if (16 * G::BT + 4 * q + 3 < NP || i < NP) ob[tile_index<NP>(n, i)] = accs[q];
+                }
+                wave_lds_fence();
+                double* op = P.out[0] + (t0 * G::TEL + 16 * m) * NP;
+#pragma unroll
+                for (int c = 0; c < G::SUB_INSTR; ++c) {
+                    const int qc = c * 64 + lane;
+                    if ((c + 1) * 64 <= G::SUB_CHUNKS || qc < G::SUB_CHUNKS)
+                        __builtin_nontemporal_store(*reinterpret_cast<const v2d*>(ob + 2 * tile_dst_chunk<NP>(qc)),
+                                                    reinterpret_cast<v2d*>(op + 2 * qc));
+                }
+                wave_lds_fence();
+            }
+            slot ^= 1;
+            t0 = t1;
+            t1 = t2;
+            t2 = t3;
+        }
+        if constexpr (kDyn) {
+            // the last wave of a pool to report leaves the pool's two counters zeroed for the next launch (younger than its
+            // report: the stores of the unit that made it, at the least)
+            if (reported) {
+                const unsigned pool_blocks = (nblk / (8 * kTailPools)) * 8 + (unsigned)max(0, min(8, (int)(nblk % (8 * kTailPools)) - 8 * pool));
+                const unsigned before = tail_wait<G::UNIT_STORES, 1>();
+                if (before + 1 == pool_blocks * G::WAVES && lane == 0) {
+                    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+        return;
+    }
+
     // prologue: units 0 and 1 of the first tile (unless requested in front of the fragment build)
     if (!first_requested) {
         FM_ISSUE(true, P.v[0], first, lds_v0, lds_j);
@@ -431,7 +597,7 @@ __device__ __forceinline__ void facemass_mfma_body(
                 }
                 if (k == NB - 2 && requested) {
                     // younger than the request: the loads and stores of units 0 .. NB - 3 (at most; this unit has waited for more)
-                    constexpr int kYounger = (NB - 2) * (G::UNIT_LOADS + G::UNIT_STORES);
+                    constexpr int kYounger = (NB >= 2 ? NB - 2 : 0) * (G::UNIT_LOADS + G::UNIT_STORES);   // (NB = 1 has left above)
                     const unsigned t = tail_wait<(kYounger < 56 ? kYounger : 56), 0>();
                     const int64_t x = tail_ticket_tile(t, t_static, pool, tEnd);
                     nt = x >= 0 ? x : tEnd;

@@ -963,7 +963,7 @@ int launch_fm_nb(const double* J, const double* R, const void* prep, const fe::F
     jfe = (jfe ? 1 : 0) | temporal_flag((NF + (int64_t)NB * NF * NFP) * E * 8, kTemporalFloorFaceMass, kTemporalCapFaceMassMib);
     const Geometry geo = {G::WAVES, G::THREADS, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
     char what[96], tail_what[96];
-    if constexpr (!ALDS && NF == fe::kFmNf) {   // prepared operators: tetrahedra p = 1..4
+    if constexpr (!ALDS && NF == fe::kFmNf && NB >= 2) {   // prepared operators: tetrahedra p = 1..4, two or more fields
         if (prep) {
             snprintf(what, sizeof(what), "face-mass Np=%d Nfp=%d M=%d b=%d, prepared operator", NP, NFP, M, NB);
             return mfma_launch<fe::facemass_mfma_kernel<NP, NFP, M, NB, NF, false, false, true>>(
@@ -976,10 +976,14 @@ int launch_fm_nb(const double* J, const double* R, const void* prep, const fe::F
     auto tail_args = [&](const Launch& L) { return call(jfe, 0, J, R, P, E, nTiles, jfe, rifj, L.tail, L.t_static[0]); };
     constexpr auto K = fe::facemass_mfma_kernel<NP, NFP, M, NB, NF, ALDS, W8>;
     // behind two static rounds the tiles come by tickets (fe_common.h, dynamic walk): p = 5 x 4, and tetrahedra p = 1 .. 4 and
-    // triangles with three or more fields
+    // triangles with three or more fields, or with one (from four and a half rounds on, as every single launch)
     if constexpr (NP == 56 && NFP == 21 && M == 1 && NF == fe::kFmNf && ALDS && NB == 4) {
         snprintf(tail_what, sizeof(tail_what), "face-mass Np=56 b=%d (A in LDS), dynamic walk", NB);
         return mfma_launch<K, fe::facemass_w8_tail_kernel<NP, NFP, NB>>(s, walk_tickets(nTiles), geo, what, args, tail_what, tail_args);
+    } else if constexpr (!ALDS && NB == 1) {
+        snprintf(tail_what, sizeof(tail_what), "face-mass Np=%d nf=%d M=%d b=1, dynamic walk", NP, NF, M);
+        return mfma_launch<K, fe::facemass_mfma_tail_kernel<NP, NFP, M, 1, NF>>(s, walk_tickets(nTiles), geo, what, args, tail_what,
+                                                                               tail_args);
     } else if constexpr (!ALDS && NB >= 3) {
         snprintf(tail_what, sizeof(tail_what), "face-mass Np=%d nf=%d M=%d b=%d, dynamic walk", NP, NF, M, NB);
         return mfma_launch<K, fe::facemass_mfma_tail_kernel<NP, NFP, M, NB, NF>>(
@@ -989,13 +993,13 @@ int launch_fm_nb(const double* J, const double* R, const void* prep, const fe::F
     }
 }
 
-// One MFMA launch for a group of nb fields (2 <= nb <= kMaxGroup of the geometry).
+// One MFMA launch for a group of nb fields (nb <= kMaxGroup of the geometry; nb = 1 only for a call of one field).
 template <int NP, int NFP, int M, int NF = fe::kFmNf, bool ALDS = false>
 int launch_fm(const double* J, const double* R, const void* prep, const fe::FieldPtrs& P, int nb, int64_t E,
               int64_t nTiles, int jfe, int rifj, hipStream_t s) {
     int rc = FE_OK;
     auto launch = [&](auto NB) { return launch_fm_nb<NP, NFP, M, decltype(NB)::value, NF, ALDS>(J, R, prep, P, E, nTiles, jfe, rifj, s); };
-    if (fe::with_field_count<2, 4>(nb, &rc, launch)) return rc;
+    if (fe::with_field_count<1, 4>(nb, &rc, launch)) return rc;
     if constexpr (NP == 35 && NF == fe::kFmNf) {   // p = 4, the headline order: groups of up to 8 fields
         if (fe::with_field_count<5, 8>(nb, &rc, launch)) return rc;
     }
@@ -2281,7 +2285,7 @@ int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_pre
     hipStream_t s = static_cast<hipStream_t>(stream);
 
     FmChoice geo{0, 16};
-    const bool mfma_ok = fm_mfma_geometry(Np, nf, Nfp, &geo) && b >= 2;
+    const bool mfma_ok = fm_mfma_geometry(Np, nf, Nfp, &geo);
     const fe::FmLayout L(layout_flags, Np, nf, Nfp, E);
     const int jfe = L.jfe, rifj = L.rifj;
     KernelPath path;
@@ -2292,7 +2296,7 @@ int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_pre
         // triangles p = 2, Np = 6: 1.4 vs 2.2 TFLOP/s; p = 4, Np = 15: 3.1 vs 2.6)
         const bool tiled_ok = tiled_fits(probe) && (variant == FE_VARIANT_TILED || Np >= 10);
         if (int rc = choose_path(variant, mfma_ok, tiled_ok,
-                                 "face-mass (MFMA: tetrahedra p = 1..4 or triangles p = 1..5, b >= 2)", Np, &path))
+                                 "face-mass (MFMA: tetrahedra p = 1..5 or triangles p = 1..5)", Np, &path))
             return rc;
     }
     if (path == kPathTiled)   // groups of up to kMaxFields fields share the staged operator
@@ -2304,7 +2308,7 @@ int fe_facemass_prepared_f64(const double* J, const double* R, const void* R_pre
     const bool use_mfma = path == kPathMfma;
     const int64_t nTiles = use_mfma ? E / geo.tel : 0;      // full wave tiles
     const int64_t e_done = nTiles > 0 ? E : 0;   // an MFMA launch covers the remainder too
-    // fields go in groups of up to max_group per launch; never leave a group of 1 for the MFMA kernel
+    // fields go in groups of up to max_group per launch; two or more fields never leave a group of 1 for the MFMA kernel
     if (int rc = fe::for_each_field_group(b, use_mfma ? geo.max_group : fe::kMaxFields, use_mfma, [&](int k0, int nb) {
             const fe::FieldPtrs P = field_group(v + k0, out + k0, nb);
             if (nTiles > 0) {

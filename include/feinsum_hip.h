@@ -231,7 +231,11 @@ int fe_waveop3d_f64(const double* J, const double* D,
  *   out_k[e,i] = sum_{f,j} J[e,f] * R[f,i,j] * v_k[f,e,j],  k = 0..b-1
  * 'ef,fij,fej->ei' x b (test/test_loopy_utils.py:34-48) or, with layout flags,
  * 'ifj,fe,fej->ei' (tuning/impls/ifj_fe_fej_to_ei.py:46-60).
- *   v, out: HOST arrays of b device pointers; v_k [nf][E][Nfp]; out_k [E][Np] */
+ *   v, out: HOST arrays of b device pointers; v_k [nf][E][Nfp]; out_k [E][Np]
+ * Matrix-core kernels for tetrahedra p = 1..5 and triangles p = 1..5, any b >= 1: two or more fields go in groups of 2..4
+ * (p = 4: up to 8) per launch, never a group of one; a call of ONE field runs the single-field kernel, whose result is
+ * bitwise what that field has as a member of a larger call.  fe_facemass_prepared_f64 with b == 1 ignores R_prepared (the
+ * single-field kernel builds its fragments from R, which is always given): same bits. */
 int fe_facemass_f64(const double* J, const double* R,
                     const double* const* v, double* const* out,
                     int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b,
