@@ -124,6 +124,9 @@ SIGNATURES = {
     "fe_grad3d_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _p]),
     "fe_div3d_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _p]),
     "fe_facemass_mixed_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_grad3d_mixed_state_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _p]),
+    "fe_div3d_mixed_state_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _p]),
+    "fe_facemass_mixed_state_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
     "fe_grad3d_strided_f64": (_int, [_p, _i64, _p, _pp, _pp, _i64, _i64, _i32, _i32, _i32, _p]),
     "fe_div3d_strided_f64": (_int, [_p, _i64, _p, _pp, _i64, _pp, _i64, _i32, _i32, _i32, _p]),
     "fe_facemass_strided_f64": (_int, [_p, _i64, _p, _pp, _i64, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
@@ -363,6 +366,31 @@ def facemass_strided(J: int, ldJ: int, R: int, v: Sequence[int], ldIn: int, out:
         raise InvalidParameterError("face-mass: need as many outputs as fields")
     check(load_library().fe_facemass_strided_f64(J, ldJ, R, _ptr_array(v), ldIn, _ptr_array(out), E, Np, nf, Nfp, len(v),
                                                  layout_flags, stream))
+
+
+def grad3d_mixed_state(J: int, D: int, u: Sequence[int], out: Sequence[int], E: int, Np: int, op_flags: int = 0,
+                       stream: int = 0) -> None:
+    """grad of float32 fields into float32 results, float64 J, operator and arithmetic (fe_grad3d_mixed_state_f64)."""
+    if len(u) != len(out):
+        raise InvalidParameterError("grad: need as many outputs as fields")
+    check(load_library().fe_grad3d_mixed_state_f64(J, D, _ptr_array(u), _ptr_array(out), E, Np, len(u), op_flags, stream))
+
+
+def div3d_mixed_state(J: int, D: int, u: Sequence[int], out: Sequence[int], E: int, Np: int, op_flags: int = 0,
+                      stream: int = 0) -> None:
+    """div of float32 fields into float32 results (fe_div3d_mixed_state_f64)."""
+    if len(u) != len(out):
+        raise InvalidParameterError("div: need as many outputs as fields")
+    check(load_library().fe_div3d_mixed_state_f64(J, D, _ptr_array(u), _ptr_array(out), E, Np, len(u), op_flags, stream))
+
+
+def facemass_mixed_state(J: int, R: int, v: Sequence[int], out: Sequence[int], E: int, Np: int, nf: int, Nfp: int,
+                         layout_flags: int = 0, stream: int = 0) -> None:
+    """face-mass of float32 fields into float32 results (fe_facemass_mixed_state_f64)."""
+    if len(v) != len(out):
+        raise InvalidParameterError("face-mass: need as many outputs as fields")
+    check(load_library().fe_facemass_mixed_state_f64(J, R, _ptr_array(v), _ptr_array(out), E, Np, nf, Nfp, len(v),
+                                                     layout_flags, stream))
 
 
 def div3d_acc(J: int, D: int, u: int, out: int, E: int, Np: int, alpha: float, beta: float, op_flags: int = 0,
@@ -674,6 +702,8 @@ def last_launch_info() -> dict:
     d["mixed_fields"] = bool(d["kind"] & 32)             # fe_grad3d_mixed_f64 / fe_div3d_mixed_f64 / fe_facemass_mixed_f64
     d["plain_field_loads"] = bool(d["kind"] & 64)        # ... with the fields through registers instead of LDS-DMA
     d["element_slice"] = bool(d["kind"] & 128)           # fe_grad3d_strided_f64 / fe_div3d_strided_f64 / fe_facemass_strided_f64
+    d["float32_results"] = bool(d["kind"] & 256)         # fe_grad3d_mixed_state_f64 / fe_div3d_... / fe_facemass_mixed_state_f64
+    d["dword_stores"] = bool(d["kind"] & 512)            # ... with one float per lane instead of 16-byte stores
     d["kind"] = "B build interleaved" if d["kind"] & 4 else "default"
     return d
 

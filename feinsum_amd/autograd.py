@@ -255,6 +255,9 @@ def evaluate_differentiable(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[st
 
     if operator_gradients not in ("auto", "kernel"):
         raise InvalidParameterError(f"operator_gradients must be 'auto' or 'kernel' (got {operator_gradients!r})")
+    if isinstance(transform, (str, Mapping)) and (transform if isinstance(transform, str) else transform.get("variant")) == "mixed_state":
+        raise NotImplementedError("evaluate_differentiable: transform 'mixed_state' rounds its float64 results to float32 and has no "
+                                  "backward pass; differentiate under 'mixed_family' or 'auto'")
     if _FN is None:
         _FN = _function()
     q = _as_queue(cq)

@@ -31,11 +31,51 @@
 // top of tile t.  Face-mass has room for its own output buffer and keeps fe_facemass_f32.h's order L(m) S(m-2) L(m+1) S(m-1).
 #pragma once
 #include "fe_common.h"
-#include "fe_grad.h"   // grad_row_tiles
+#include "fe_grad.h"       // grad_row_tiles
+#include "fe_grad_f32.h"   // v4f
+#include <type_traits>
 
 namespace fe {
 
 constexpr int kLaunchMixedFields = 32, kLaunchPlainFieldLoads = 64;   // `kind` bits of fe_last_launch_info
+constexpr int kLaunchFloat32Results = 256, kLaunchDwordStores = 512;  // ... of the float32-result kernels (OUT = float below)
+// Float32 results (the kernels' template parameter OUT = float): the same arithmetic up to the float64 value that goes into the
+// wave's transposition buffer; that value is narrowed there by a plain (float) cast -- one round-to-nearest-even -- so the buffer
+// holds floats and is half the size.  Two forms of the non-temporal stores, chosen per launch by the rule of the load forms and
+// passed as a wave-uniform bit of the kernel's flag word (one scalar branch per store group, as kOpLoadsTemporal):
+//   * 16 bytes per lane -- when every output plane of the launch starts on an 8-byte boundary (the only alignment of 16-byte
+//     global stores this project has verified, tools/align_test.hip; a tile's offset in a plane is a multiple of 64 bytes);
+//   * kOpDwordStores: one float per lane, consecutive lanes consecutive floats -- otherwise (grad's planes x E Np 4 at odd E Np).
+//     This form waits for its loads with vmcnt(0), like the register form of the field loads.
+constexpr int kOpDwordStores = 2;    // in the opT word of grad and div, in the jfe word of face-mass
+
+template <typename OUT>
+constexpr bool kFloat32Results = std::is_same<OUT, float>::value;
+
+// the float out tile of COUNT values from the wave's transposition buffer to global memory, non-temporal; INSTR16: the store
+// instructions of the 16-byte form as the geometry counts them for its vmcnt
+template <int COUNT, int INSTR16>
+__device__ __forceinline__ void wave_store_f32(const float* ob, float* op, int lane, bool dwords) {
+    static_assert(COUNT % 4 == 0 && INSTR16 == (COUNT / 4 + 63) / 64, "the counted vmcnt: one 16-byte store per 64 chunks of four floats");
+    if (dwords) {
+        constexpr int INSTR = (COUNT + 63) / 64;
+#pragma unroll
+        for (int c = 0; c < INSTR; ++c) {
+            const int i = c * 64 + lane;
+            if ((c + 1) * 64 <= COUNT || i < COUNT) __builtin_nontemporal_store(ob[i], op + i);
+        }
+    } else {
+        constexpr int CHUNKS = COUNT / 4, INSTR = (CHUNKS + 63) / 64;
+#pragma unroll
+        for (int c = 0; c < INSTR; ++c) {
+            const int q = c * 64 + lane;
+            if ((c + 1) * 64 <= CHUNKS || q < CHUNKS) {
+                const v4f val = *reinterpret_cast<const v4f*>(ob + 4 * q);
+                __builtin_nontemporal_store(val, reinterpret_cast<v4f*>(op + 4 * q));
+            }
+        }
+    }
+}
 
 template <int NP>
 struct MixedRows {
@@ -61,17 +101,17 @@ __device__ __forceinline__ void wave_copy_f32(const float* __restrict__ g, float
 
 // ---------------------------------------------------------------------------------------------------------------- div
 
-template <int NP_, int M_>
+template <int NP_, int M_, typename OUT = double>
 struct DivMixedGeomT : MixedRows<NP_> {
     using MixedRows<NP_>::NS;
     static constexpr int NP = NP_, M = M_, TEL = 16 * M;
     static constexpr int KSJ = (NP + 3) / 4, KS = 3 * KSJ;          // k-step 3 jq + r
     static constexpr int PLANE_F = TEL * NP, P_CHUNKS = PLANE_F / 4, P_INSTR = (P_CHUNKS + 63) / 64;   // one float32 u plane of a tile
     static constexpr int J_ROW_CHUNKS = TEL / 2, J_CHUNKS = 9 * J_ROW_CHUNKS, J_INSTR = (J_CHUNKS + 63) / 64;
-    static constexpr int O_CHUNKS = PLANE_F / 2, O_INSTR = (O_CHUNKS + 63) / 64;                       // the float64 out tile
+    static constexpr int O_CHUNKS = PLANE_F * (int)sizeof(OUT) / 16, O_INSTR = (O_CHUNKS + 63) / 64;   // the out tile, 16-byte chunks
     static constexpr int LOADS = 3 * P_INSTR + J_INSTR, STORES = O_INSTR;
     struct Slot {
-        float u[3][PLANE_F];     // u[x][e0 .. e0+TEL-1][0..Np-1]; once consumed: the out tile, double [TEL][Np]
+        float u[3][PLANE_F];     // u[x][e0 .. e0+TEL-1][0..Np-1]; once consumed: the out tile, OUT [TEL][Np]
         double j[9 * TEL];       // J[x*3+r][e0 .. e0+TEL-1]
     };
     struct WaveIn {
@@ -84,13 +124,15 @@ struct DivMixedGeomT : MixedRows<NP_> {
     static constexpr int LDS_BYTES = (IN_BYTES > OP_D * 8 ? IN_BYTES : OP_D * 8) + ASMALL_D * 8;
     static constexpr int BLOCKS_PER_CU = 2;
     static_assert(PLANE_F % 4 == 0 && sizeof(Slot) % 16 == 0 && (3 * PLANE_F * 4) % 16 == 0, "16-byte LDS-DMA chunks");
-    static_assert(PLANE_F * 8 <= 3 * PLANE_F * 4, "the out tile fits the consumed u planes");
+    static_assert(PLANE_F * sizeof(OUT) <= 3 * PLANE_F * sizeof(float) && (PLANE_F * sizeof(OUT)) % 16 == 0,
+                  "the out tile (OUT [TEL][Np], whole 16-byte chunks) fits the consumed u planes");
     static_assert(BLOCKS_PER_CU * LDS_BYTES <= 160 * 1024, "two blocks per CU");
     static_assert(STORES + LOADS <= 60, "counted vmcnt must fit the 6-bit field");
 };
 
+template <typename OUT>
 __device__ __forceinline__ void div3d_item_mixed(const double* __restrict__ J, const double* __restrict__ D,
-                                                 const float* __restrict__ u, double* __restrict__ out, int64_t E, int Np,
+                                                 const float* __restrict__ u, OUT* __restrict__ out, int64_t E, int Np,
                                                  int64_t e, int i, int opT) {
     const int si = opT ? 1 : Np, sj = opT ? Np : 1;
     double jac[9];
@@ -104,14 +146,17 @@ __device__ __forceinline__ void div3d_item_mixed(const double* __restrict__ J, c
             acc = __builtin_fma(D[(int64_t)r * Np * Np + (int64_t)i * si + (int64_t)j * sj], ju, acc);
         }
     }
-    out[e * Np + i] = acc;
+    out[e * Np + i] = (OUT)acc;
 }
 
-template <int NP_, int M_, bool PLAIN>
+// OUT = float: float32 results; op_flags then also carries kOpDwordStores
+template <int NP_, int M_, bool PLAIN, typename OUT = double>
 __global__ __launch_bounds__(256, 2) void div3d_mixed_kernel(const double* __restrict__ J, const double* __restrict__ D,
-                                                             const float* __restrict__ u, double* __restrict__ out, int64_t E,
-                                                             int64_t nTiles, int opT) {
-    using G = DivMixedGeomT<NP_, M_>;
+                                                             const float* __restrict__ u, OUT* __restrict__ out, int64_t E,
+                                                             int64_t nTiles, int op_flags) {
+    using G = DivMixedGeomT<NP_, M_, OUT>;
+    const int opT = kFloat32Results<OUT> ? (op_flags & 1) : op_flags;
+    const bool dwords = kFloat32Results<OUT> && (op_flags & kOpDwordStores) != 0;
     constexpr int NP = G::NP, M = G::M;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -187,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void div3d_mixed_kernel(const double* __res
     while (tile < tEnd) {
         balance_priority(younger_half, iteration);
         // vector-memory ops in issue order: L(t) S(t-1) L(t+1); the plain form waits for everything
-        if (!PLAIN && iteration >= 1 && tile + stride < tEnd) wait_vmcnt<G::STORES + G::LOADS>();
+        if (!PLAIN && !dwords && iteration >= 1 && tile + stride < tEnd) wait_vmcnt<G::STORES + G::LOADS>();
         else wait_vmcnt<0>();
         if constexpr (PLAIN) wave_lds_fence();
         ++iteration;
@@ -214,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void div3d_mixed_kernel(const double* __res
             }
         }
         wave_lds_fence();   // the u planes are in registers: they become the out tile
-        double* ob = reinterpret_cast<double*>(&S->u[0][0]);
+        OUT* ob = reinterpret_cast<OUT*>(&S->u[0][0]);
 
 #pragma unroll
         for (int m = 0; m < M; ++m) {
@@ -240,21 +285,25 @@ __global__ __launch_bounds__(256, 2) void div3d_mixed_kernel(const double* __res
 #pragma unroll
             for (int t = 0; t < G::BT; ++t)
 #pragma unroll
-                for (int qq = 0; qq < 4; ++qq) ob[(16 * m + n) * NP + 16 * t + g + 4 * qq] = acc[t][qq];
+                for (int qq = 0; qq < 4; ++qq) ob[(16 * m + n) * NP + 16 * t + g + 4 * qq] = (OUT)acc[t][qq];
 #pragma unroll
             for (int q = 0; q < G::NS; ++q) {
                 const int i = 16 * G::BT + 4 * q + g;
-                if (16 * G::BT + 4 * q + 3 < NP || i < NP) ob[(16 * m + n) * NP + i] = accs[q];
+                if (16 * G::BT + 4 * q + 3 < NP || i < NP) ob[(16 * m + n) * NP + i] = (OUT)accs[q];
             }
         }
         wave_lds_fence();
-        double* op = out + tile * (G::TEL * NP);
+        OUT* op = out + tile * (G::TEL * NP);
+        if constexpr (kFloat32Results<OUT>) {
+            wave_store_f32<G::PLANE_F, G::STORES>(ob, op, lane, dwords);
+        } else {
 #pragma unroll
-        for (int c = 0; c < G::O_INSTR; ++c) {
-            const int q = c * 64 + lane;
-            if ((c + 1) * 64 <= G::O_CHUNKS || q < G::O_CHUNKS) {
-                const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * q);
-                __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * q));
+            for (int c = 0; c < G::O_INSTR; ++c) {
+                const int q = c * 64 + lane;
+                if ((c + 1) * 64 <= G::O_CHUNKS || q < G::O_CHUNKS) {
+                    const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * q);
+                    __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * q));
+                }
             }
         }
         wave_lds_fence();
@@ -267,7 +316,7 @@ __global__ __launch_bounds__(256, 2) void div3d_mixed_kernel(const double* __res
 
 // ---------------------------------------------------------------------------------------------------------- face-mass
 
-template <int NP_, int NFP_, int M_>
+template <int NP_, int NFP_, int M_, typename OUT = double>
 struct FmMixedGeomT : MixedRows<NP_> {
     using MixedRows<NP_>::NS;
     static constexpr int NP = NP_, NFP = NFP_, NF = 4, M = M_, TEL = 16 * M;
@@ -275,12 +324,12 @@ struct FmMixedGeomT : MixedRows<NP_> {
     static constexpr int SLAB_F = TEL * NFP, UNIT_F = NF * SLAB_F;  // floats per face slab of a unit, per unit
     static constexpr int SLAB_CHUNKS = SLAB_F / 4, SLAB_INSTR = (SLAB_CHUNKS + 63) / 64;
     static constexpr int J_CHUNKS = NF * TEL / 2, J_INSTR = (J_CHUNKS + 63) / 64;
-    static constexpr int SUB_D = TEL * NP, SUB_CHUNKS = SUB_D / 2, SUB_INSTR = (SUB_CHUNKS + 63) / 64;   // the out tile of a unit
+    static constexpr int SUB_D = TEL * NP, SUB_CHUNKS = SUB_D * (int)sizeof(OUT) / 16, SUB_INSTR = (SUB_CHUNKS + 63) / 64;   // the out tile of a unit
     static constexpr int UNIT_LOADS = NF * SLAB_INSTR, UNIT_STORES = SUB_INSTR;
     struct WaveIn {
         float v[2][UNIT_F];      // ring of field slabs: v[slot][f][e][j]
         double j[2][NF * TEL];   // J tile of the unit in that slot, [e][f] or [f][e] as in global memory
-        double o[SUB_D];         // output transposition buffer
+        OUT o[SUB_D];            // output transposition buffer
     };
     static constexpr int WAVES = 4;
     static constexpr int OP_D = NF * NP * NFP;
@@ -288,25 +337,30 @@ struct FmMixedGeomT : MixedRows<NP_> {
     static constexpr int IN_BYTES = (int)sizeof(WaveIn) * WAVES;
     static constexpr int LDS_BYTES = (IN_BYTES > OP_D * 8 ? IN_BYTES : OP_D * 8) + ASMALL_D * 8;
     static constexpr int BLOCKS_PER_CU = 2;
-    static_assert(K % 4 == 0 && SLAB_F % 4 == 0 && SUB_D % 2 == 0 && (UNIT_F * 4) % 16 == 0 && sizeof(WaveIn) % 16 == 0, "geometry");
+    static_assert(K % 4 == 0 && SLAB_F % 4 == 0 && (SUB_D * sizeof(OUT)) % 16 == 0 && (UNIT_F * 4) % 16 == 0 && sizeof(WaveIn) % 16 == 0, "geometry");
     static_assert(BLOCKS_PER_CU * LDS_BYTES <= 160 * 1024, "two blocks per CU");
     static_assert(2 * UNIT_STORES + UNIT_LOADS + J_INSTR <= 60, "counted vmcnt must fit the 6-bit field");
 };
 
-// field k of a mixed launch: float32 in, float64 out (FieldPtrs carries the inputs as double*: the argument pack is untyped)
+// field k of a mixed launch: float32 in, float64 or float32 out (FieldPtrs carries both as double*: the argument pack is untyped)
 __device__ __forceinline__ const float* field_in_mixed(const FieldPtrs& P, int k) { return reinterpret_cast<const float*>(field_in(P, k)); }
+template <typename OUT>
+__device__ __forceinline__ OUT* field_out_mixed(const FieldPtrs& P, int k) { return reinterpret_cast<OUT*>(field_out(P, k)); }
 
-template <int NP_, int NFP_, int M_, bool PLAIN>
+// OUT = float: float32 results (P.out holds float*); jfe_flags then also carries kOpDwordStores
+template <int NP_, int NFP_, int M_, bool PLAIN, typename OUT = double>
 __global__ __launch_bounds__(256, 2) void facemass_mixed_kernel(const double* __restrict__ J, const double* __restrict__ R, FieldPtrs P,
-                                                                int nb, int64_t E, int64_t nTiles, int jfe, int rlayout) {
-    using G = FmMixedGeomT<NP_, NFP_, M_>;
+                                                                int nb, int64_t E, int64_t nTiles, int jfe_flags, int rlayout) {
+    using G = FmMixedGeomT<NP_, NFP_, M_, OUT>;
+    const int jfe = kFloat32Results<OUT> ? (jfe_flags & 1) : jfe_flags;
+    const bool dwords = kFloat32Results<OUT> && (jfe_flags & kOpDwordStores) != 0;
     constexpr int NP = G::NP, NFP = G::NFP, NF = G::NF, M = G::M;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     typename G::WaveIn* L = reinterpret_cast<typename G::WaveIn*>(smem) + wave;
     double* asmall = reinterpret_cast<double*>(smem + (G::LDS_BYTES - G::ASMALL_D * 8));
-    double* ob = L->o;
+    OUT* ob = L->o;
     const int n = lane & 15, g = lane >> 4;
     const unsigned bid = blockIdx.x, nblk = gridDim.x;
     const int64_t stride = (int64_t)nblk * G::WAVES, tEnd = nTiles;
@@ -380,7 +434,7 @@ __global__ __launch_bounds__(256, 2) void facemass_mixed_kernel(const double* __
                     for (int j = 0; j < NFP; ++j)
                         acc = __builtin_fma(rl[f * sF + i * sI + j * sJ], jf * (double)vk[((int64_t)f * E + e) * NFP + j], acc);
                 }
-                field_out(P, k)[e * NP + i] = acc;
+                field_out_mixed<OUT>(P, k)[e * NP + i] = (OUT)acc;
             }
         });
     }
@@ -404,7 +458,7 @@ __global__ __launch_bounds__(256, 2) void facemass_mixed_kernel(const double* __
     while (tile < tEnd) {
         if (fk == 0) balance_priority(younger_half, iteration++);
         // ---- wait for this unit's loads; younger ops: S(m-2), L(m+1), S(m-1); the plain form waits for everything
-        if (!PLAIN && done >= 2 && t1 < tEnd) {
+        if (!PLAIN && !dwords && done >= 2 && t1 < tEnd) {
             if (k1 == 0) wait_vmcnt<2 * G::UNIT_STORES + G::UNIT_LOADS + G::J_INSTR>();
             else wait_vmcnt<2 * G::UNIT_STORES + G::UNIT_LOADS>();
         } else {
@@ -448,21 +502,25 @@ __global__ __launch_bounds__(256, 2) void facemass_mixed_kernel(const double* __
 #pragma unroll
             for (int t = 0; t < G::BT; ++t)
 #pragma unroll
-                for (int qq = 0; qq < 4; ++qq) ob[(16 * m + n) * NP + 16 * t + g + 4 * qq] = acc[t][qq];
+                for (int qq = 0; qq < 4; ++qq) ob[(16 * m + n) * NP + 16 * t + g + 4 * qq] = (OUT)acc[t][qq];
 #pragma unroll
             for (int q = 0; q < G::NS; ++q) {
                 const int i = 16 * G::BT + 4 * q + g;
-                if (16 * G::BT + 4 * q + 3 < NP || i < NP) ob[(16 * m + n) * NP + i] = accs[q];
+                if (16 * G::BT + 4 * q + 3 < NP || i < NP) ob[(16 * m + n) * NP + i] = (OUT)accs[q];
             }
         }
         wave_lds_fence();
-        double* op = field_out(P, fk) + tile * (G::TEL * NP);
+        OUT* op = field_out_mixed<OUT>(P, fk) + tile * (G::TEL * NP);
+        if constexpr (kFloat32Results<OUT>) {
+            wave_store_f32<G::SUB_D, G::UNIT_STORES>(ob, op, lane, dwords);
+        } else {
 #pragma unroll
-        for (int c = 0; c < G::SUB_INSTR; ++c) {
-            const int q = c * 64 + lane;
-            if ((c + 1) * 64 <= G::SUB_CHUNKS || q < G::SUB_CHUNKS) {
-                const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * q);
-                __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * q));
+            for (int c = 0; c < G::SUB_INSTR; ++c) {
+                const int q = c * 64 + lane;
+                if ((c + 1) * 64 <= G::SUB_CHUNKS || q < G::SUB_CHUNKS) {
+                    const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * q);
+                    __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * q));
+                }
             }
         }
         wave_lds_fence();
@@ -481,20 +539,20 @@ __global__ __launch_bounds__(256, 2) void facemass_mixed_kernel(const double* __
 // three r of TG consecutive i of one element), stage 2  out[x,e,i] = sum_r J[x,r,e] * tmp  lane-local on the VALU (one multiply,
 // two explicit fused multiply-adds).  The float32 u tile is widened where the B fragments are read.  Data movement is
 // fe_grad_f32.h's static walk: loads one tile ahead into a double buffer, L(t) S(t-1) L(t+1) | wait L(t).
-template <int M_, int NP_>
+template <int M_, int NP_, typename OUT = double>
 struct GradMixedGeomT {
     static constexpr int M = M_, NP = NP_, TEL = 16 * M, RT = grad_row_tiles(NP_), TG = (4 * RT) / 3, KS = (NP_ + 3) / 4;
-    static constexpr int TILE_F = TEL * NP;             // floats of the u tile = doubles of one out plane of a tile
+    static constexpr int TILE_F = TEL * NP;             // floats of the u tile = values of one out plane of a tile
     static constexpr int U_CHUNKS = TILE_F / 4, U_INSTR = (U_CHUNKS + 63) / 64;
     static constexpr int J_ROW_CHUNKS = TEL / 2, J_CHUNKS = 9 * J_ROW_CHUNKS, J_INSTR = (J_CHUNKS + 63) / 64;
-    static constexpr int O_CHUNKS = TILE_F / 2, PLANE_STORES = (O_CHUNKS + 63) / 64;
+    static constexpr int O_CHUNKS = TILE_F * (int)sizeof(OUT) / 16, PLANE_STORES = (O_CHUNKS + 63) / 64;
     static constexpr int LOADS = U_INSTR + J_INSTR, STORES = 3 * PLANE_STORES;
     struct WaveLds {
         float u[2][TILE_F];      // prefetch double buffer
         double j[2][9 * TEL];    // J[x*3+r][e0 .. e0+TEL-1], double buffered
     };
     struct WaveOut {
-        double o[2][TILE_F];     // output transposition buffers (a whole plane of the tile), alternating
+        OUT o[2][TILE_F];        // output transposition buffers (a whole plane of the tile), alternating
     };
     static constexpr int WAVES = 4;
     static constexpr int OP_D = 3 * NP * NP;
@@ -502,13 +560,14 @@ struct GradMixedGeomT {
     static constexpr int OUT_BYTES = (int)sizeof(WaveOut) * WAVES;
     static constexpr int LDS_BYTES = IN_BYTES + (OUT_BYTES > OP_D * 8 ? OUT_BYTES : OP_D * 8);   // (the operator is staged over the output buffers)
     static constexpr int BLOCKS_PER_CU = 2;
-    static_assert(TILE_F % 4 == 0 && (TILE_F * 4) % 16 == 0 && sizeof(WaveLds) % 16 == 0, "16-byte LDS-DMA chunks");
+    static_assert(TILE_F % 4 == 0 && (TILE_F * 4) % 16 == 0 && sizeof(WaveLds) % 16 == 0 && sizeof(WaveOut) % 16 == 0, "16-byte chunks");
     static_assert(BLOCKS_PER_CU * LDS_BYTES <= 160 * 1024, "two blocks per CU");
     static_assert(LOADS + STORES <= 60, "counted vmcnt must fit the 6-bit field");
 };
 
+template <typename OUT>
 __device__ __forceinline__ void grad3d_item_mixed(const double* __restrict__ J, const double* __restrict__ D,
-                                                  const float* __restrict__ u, double* __restrict__ out, int64_t E, int Np,
+                                                  const float* __restrict__ u, OUT* __restrict__ out, int64_t E, int Np,
                                                   int64_t e, int i, int opT) {
     double t0 = 0.0, t1 = 0.0, t2 = 0.0;
     const float* ue = u + e * Np;
@@ -524,15 +583,18 @@ __device__ __forceinline__ void grad3d_item_mixed(const double* __restrict__ J, 
     }
     for (int x = 0; x < 3; ++x)
         out[((int64_t)x * E + e) * Np + i] =
-            __builtin_fma(J[(int64_t)(x * 3 + 2) * E + e], t2,
-                          __builtin_fma(J[(int64_t)(x * 3 + 1) * E + e], t1, J[(int64_t)(x * 3 + 0) * E + e] * t0));
+            (OUT)__builtin_fma(J[(int64_t)(x * 3 + 2) * E + e], t2,
+                               __builtin_fma(J[(int64_t)(x * 3 + 1) * E + e], t1, J[(int64_t)(x * 3 + 0) * E + e] * t0));
 }
 
-template <int M, int NP_, bool PLAIN>
+// OUT = float: float32 results; op_flags then also carries kOpDwordStores
+template <int M, int NP_, bool PLAIN, typename OUT = double>
 __global__ __launch_bounds__(256, 2) void grad3d_mixed_kernel(const double* __restrict__ J, const double* __restrict__ D,
-                                                              const float* __restrict__ u, double* __restrict__ out, int64_t E,
-                                                              int64_t nTiles, int opT) {
-    using G = GradMixedGeomT<M, NP_>;
+                                                              const float* __restrict__ u, OUT* __restrict__ out, int64_t E,
+                                                              int64_t nTiles, int op_flags) {
+    using G = GradMixedGeomT<M, NP_, OUT>;
+    const int opT = kFloat32Results<OUT> ? (op_flags & 1) : op_flags;
+    const bool dwords = kFloat32Results<OUT> && (op_flags & kOpDwordStores) != 0;
     constexpr int NP = G::NP;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -612,6 +674,8 @@ __global__ __launch_bounds__(256, 2) void grad3d_mixed_kernel(const double* __re
         if constexpr (PLAIN) {
             wait_vmcnt<0>();
             wave_lds_fence();
+        } else if (dwords) {
+            wait_vmcnt<0>();
         } else if (nt < tEnd) {
             if (first) wait_vmcnt<G::LOADS>();
             else wait_vmcnt<G::LOADS + G::STORES>();
@@ -647,7 +711,7 @@ __global__ __launch_bounds__(256, 2) void grad3d_mixed_kernel(const double* __re
         const int64_t e0 = tile * G::TEL;
 #pragma unroll
         for (int x = 0; x < 3; ++x) {
-            double* ob = LO->o[x & 1];
+            OUT* ob = LO->o[x & 1];
 #pragma unroll
             for (int m = 0; m < M; ++m) {
                 const double j0 = jt[(x * 3 + 0) * G::TEL + 16 * m + n];
@@ -661,17 +725,21 @@ __global__ __launch_bounds__(256, 2) void grad3d_mixed_kernel(const double* __re
                     const double t2 = acc[m][(s + 2) >> 2][(s + 2) & 3];
                     const double val = __builtin_fma(j2, t2, __builtin_fma(j1, t1, j0 * t0));
                     const int i = G::TG * g + k;
-                    if (G::TG * 3 + k < NP || i < NP) ob[(16 * m + n) * NP + i] = val;
+                    if (G::TG * 3 + k < NP || i < NP) ob[(16 * m + n) * NP + i] = (OUT)val;
                 }
             }
             wave_lds_fence();
-            double* op = out + ((int64_t)x * E + e0) * NP;
+            OUT* op = out + ((int64_t)x * E + e0) * NP;
+            if constexpr (kFloat32Results<OUT>) {
+                wave_store_f32<G::TILE_F, G::PLANE_STORES>(ob, op, lane, dwords);
+            } else {
 #pragma unroll
-            for (int c = 0; c < G::PLANE_STORES; ++c) {
-                const int q = c * 64 + lane;
-                if ((c + 1) * 64 <= G::O_CHUNKS || q < G::O_CHUNKS) {
-                    const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * q);
-                    __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * q));
+                for (int c = 0; c < G::PLANE_STORES; ++c) {
+                    const int q = c * 64 + lane;
+                    if ((c + 1) * 64 <= G::O_CHUNKS || q < G::O_CHUNKS) {
+                        const v2d val = *reinterpret_cast<const v2d*>(ob + 2 * q);
+                        __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(op + 2 * q));
+                    }
                 }
             }
             wave_lds_fence();

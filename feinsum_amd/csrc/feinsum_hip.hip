@@ -178,6 +178,7 @@ struct CallCheck {
     int32_t Np, b, flags, flag_mask;
     const char* flag_name = "operator";
     int in_align = 8;                       // 4: float32 fields
+    int out_align = 8;                      // 4: float32 results
     const double* alpha = nullptr;          // with beta: an accumulating call
     const double* beta = nullptr;
     int64_t ld[3] = {0, 0, 0};              // ldJ, ldIn, ldOut of a call on an element slice, where ld_used
@@ -229,8 +230,9 @@ int check_call(const CallCheck& c) {
         if (reinterpret_cast<uintptr_t>(c.in[k]) & (uintptr_t)(c.in_align - 1))
             return fail(FE_EINVAL, c.in_align == 4 ? "%s: field %d must be 4-byte aligned (a float32 array)"
                                                    : "%s: field %d: device pointers must be 8-byte aligned (float64 arrays)", who, k);
-        if (reinterpret_cast<uintptr_t>(c.out[k]) & 7u)
-            return fail(FE_EINVAL, "%s: output %d: device pointers must be 8-byte aligned (float64 arrays)", who, k);
+        if (reinterpret_cast<uintptr_t>(c.out[k]) & (uintptr_t)(c.out_align - 1))
+            return fail(FE_EINVAL, c.out_align == 4 ? "%s: output %d must be 4-byte aligned (a float32 array)"
+                                                    : "%s: output %d: device pointers must be 8-byte aligned (float64 arrays)", who, k);
     }
     if (!c.scope_first)
         if (int rc = check_scope(c)) return rc;
@@ -1381,17 +1383,18 @@ int launch_f32_facemass(const fe_argpack* a, const double* const* vin, double* c
 // ---- float32 fields in float64 grad, div and face-mass (fe_mixed.h).  A launch below one wave tile still runs one block: its
 // remainder code covers every element.  `plain`: the launch's field loads go through registers (a field plane that does not
 // start on an 8-byte boundary: fe_mixed.h).  grad and div take the same arguments: one launcher, one launch per field.
-template <typename G, auto KD, auto KP>
-int launch_mixed_fields(const double* J, const double* D, const float* const* v, double* const* outs, int b, int64_t E, int opT,
-                     bool plain, const char* what, const char* what_plain, hipStream_t s) {
+// Float32 results (OUT = float): `opT` also carries fe::kOpDwordStores, `kind` the bits that say so.
+template <typename G, auto KD, auto KP, typename OUT = double>
+int launch_mixed_fields(const double* J, const double* D, const float* const* v, OUT* const* outs, int b, int64_t E, int opT,
+                     bool plain, const char* what, const char* what_plain, hipStream_t s, int kind = 0) {
     const int64_t nTiles = E / G::TEL;
     const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
     const Walk walk = walk_static(nTiles > 0 ? nTiles : 1);
     for (int k = 0; k < b; ++k) {
         const float* u = v[k];
-        double* out = outs[k];
+        OUT* out = outs[k];
         auto args = [&](const Launch&) {
-            return call(opT, fe::kLaunchMixedFields | (plain ? fe::kLaunchPlainFieldLoads : 0), J, D, u, out, E, nTiles, opT);
+            return call(opT, fe::kLaunchMixedFields | (plain ? fe::kLaunchPlainFieldLoads : 0) | kind, J, D, u, out, E, nTiles, opT);
         };
         if (int rc = plain ? mfma_launch<KP>(s, walk, geo, what_plain, args) : mfma_launch<KD>(s, walk, geo, what, args)) return rc;
     }
@@ -1401,7 +1404,7 @@ int launch_mixed_fields(const double* J, const double* D, const float* const* v,
 
 template <typename G, auto KD, auto KP>
 int launch_mixed_facemass(const double* J, const double* R, const float* const* v, double* const* outs, int b, int64_t E, int jl,
-                          int rl, bool plain, const char* what, const char* what_plain, hipStream_t s) {
+                          int rl, bool plain, const char* what, const char* what_plain, hipStream_t s, int kind = 0) {
     const int64_t nTiles = E / G::TEL;
     const Geometry geo = {G::WAVES, 256, G::LDS_BYTES, G::BLOCKS_PER_CU, G::BLOCKS_PER_CU};
     const Walk walk = walk_static(nTiles > 0 ? nTiles : 1);
@@ -1409,7 +1412,7 @@ int launch_mixed_facemass(const double* J, const double* R, const float* const* 
     if (int rc = fe::for_each_field_group(b, fe::kMaxFields, false, [&](int k0, int nb) {
             const fe::FieldPtrs P = field_group(reinterpret_cast<const double* const*>(v) + k0, outs + k0, nb);
             auto args = [&](const Launch&) {
-                return call(0, fe::kLaunchMixedFields | (plain ? fe::kLaunchPlainFieldLoads : 0), J, R, P, nb, E, nTiles, jl, rl);
+                return call(0, fe::kLaunchMixedFields | (plain ? fe::kLaunchPlainFieldLoads : 0) | kind, J, R, P, nb, E, nTiles, jl, rl);
             };
             return plain ? mfma_launch<KP>(s, walk, geo, what_plain, args) : mfma_launch<KD>(s, walk, geo, what, args);
         }))
@@ -3369,6 +3372,89 @@ int fe_facemass_mixed_f64(const double* J, const double* R, const void* const* f
         return launch_mixed_facemass<fe::FmMixedGeomT<O::NP, O::NFP, O::MF>, fe::facemass_mixed_kernel<O::NP, O::NFP, O::MF, false>,
                                      fe::facemass_mixed_kernel<O::NP, O::NFP, O::MF, true>>(J, R, v, outs, b, E, L.jfe, L.rifj, plain, what,
                                                                                             what_plain, s);
+    });
+}
+
+// float32 fields and float32 results, float64 J / operator / arithmetic (fe_mixed.h, OUT = float).  The store form of a launch:
+// 16 bytes per lane when every output plane starts on an 8-byte boundary, else one float per lane.
+int fe_div3d_mixed_state_f64(const double* J, const double* D, const void* const* fields, void** outs, int64_t E, int32_t Np,
+                             int32_t b, int32_t layout_flags, void* stream) {
+    forget_last_launch();
+    const float* const* v = reinterpret_cast<const float* const*>(fields);
+    float* const* o = reinterpret_cast<float* const*>(outs);
+    CallCheck c = {"div, float32 fields and results", J, D, fields, ptr_table(outs), E, Np, b, layout_flags, FE_OP_TRANSPOSED};
+    c.in_align = c.out_align = 4;
+    c.scope = kScopeTet; c.scope_first = true;
+    FE_CHECK_CALL(c);
+    bool plain = false, dwords = false;   // (the rules of fe_div3d_mixed_f64; the outputs have one plane each)
+    for (int k = 0; k < b; ++k) {
+        for (int x = 0; x < 3; ++x) plain = plain || ((reinterpret_cast<uintptr_t>(v[k]) + (uintptr_t)x * (uintptr_t)E * Np * 4u) & 7u) != 0;
+        dwords = dwords || (reinterpret_cast<uintptr_t>(o[k]) & 7u) != 0;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int op_flags = ((layout_flags & FE_OP_TRANSPOSED) ? 1 : 0) | (dwords ? fe::kOpDwordStores : 0);
+    return fe::with_tet_order(Np, [&](auto o_) {
+        using O = decltype(o_);
+        static const What what("div float32 fields+results Np=%d M=%d", O::NP, O::MD),
+            what_plain("div float32 fields+results Np=%d M=%d, plain loads", O::NP, O::MD);
+        return launch_mixed_fields<fe::DivMixedGeomT<O::NP, O::MD, float>, fe::div3d_mixed_kernel<O::NP, O::MD, false, float>,
+                                   fe::div3d_mixed_kernel<O::NP, O::MD, true, float>, float>(J, D, v, o, b, E, op_flags, plain, what,
+                                                                                            what_plain, s, fe::kLaunchFloat32Results | (dwords ? fe::kLaunchDwordStores : 0));
+    });
+}
+
+int fe_grad3d_mixed_state_f64(const double* J, const double* D, const void* const* fields, void** outs, int64_t E, int32_t Np,
+                              int32_t b, int32_t layout_flags, void* stream) {
+    forget_last_launch();
+    const float* const* v = reinterpret_cast<const float* const*>(fields);
+    float* const* o = reinterpret_cast<float* const*>(outs);
+    CallCheck c = {"grad, float32 fields and results", J, D, fields, ptr_table(outs), E, Np, b, layout_flags, FE_OP_TRANSPOSED};
+    c.in_align = c.out_align = 4;
+    c.scope = kScopeTet; c.scope_first = true;
+    FE_CHECK_CALL(c);
+    bool plain = false, dwords = ((uint64_t)E * (uint64_t)Np) % 2 != 0;   // planes x E Np floats behind an output's start
+    for (int k = 0; k < b; ++k) {
+        plain = plain || (reinterpret_cast<uintptr_t>(v[k]) & 7u) != 0;
+        dwords = dwords || (reinterpret_cast<uintptr_t>(o[k]) & 7u) != 0;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int op_flags = ((layout_flags & FE_OP_TRANSPOSED) ? 1 : 0) | (dwords ? fe::kOpDwordStores : 0);
+    return fe::with_tet_order(Np, [&](auto o_) {
+        using O = decltype(o_);
+        static const What what("grad float32 fields+results Np=%d M=%d", O::NP, O::MG),
+            what_plain("grad float32 fields+results Np=%d M=%d, plain loads", O::NP, O::MG);
+        return launch_mixed_fields<fe::GradMixedGeomT<O::MG, O::NP, float>, fe::grad3d_mixed_kernel<O::MG, O::NP, false, float>,
+                                   fe::grad3d_mixed_kernel<O::MG, O::NP, true, float>, float>(J, D, v, o, b, E, op_flags, plain, what,
+                                                                                             what_plain, s, fe::kLaunchFloat32Results | (dwords ? fe::kLaunchDwordStores : 0));
+    });
+}
+
+int fe_facemass_mixed_state_f64(const double* J, const double* R, const void* const* fields, void** outs, int64_t E, int32_t Np,
+                                int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream) {
+    forget_last_launch();
+    const float* const* v = reinterpret_cast<const float* const*>(fields);
+    CallCheck c = {"face-mass, float32 fields and results", J, R, fields, ptr_table(outs), E, Np, b, layout_flags, 7};
+    c.flag_name = "layout";
+    c.in_align = c.out_align = 4;
+    c.faces = true; c.nf = nf; c.Nfp = Nfp;
+    c.scope = kScopeTetFaces; c.scope_first = true;
+    FE_CHECK_CALL(c);
+    bool plain = false, dwords = false;   // (the rule of fe_facemass_mixed_f64; the outputs have one plane each)
+    for (int k = 0; k < b; ++k) {
+        for (int f = 0; f < 4; ++f) plain = plain || ((reinterpret_cast<uintptr_t>(v[k]) + (uintptr_t)f * (uintptr_t)E * Nfp * 4u) & 7u) != 0;
+        dwords = dwords || (reinterpret_cast<uintptr_t>(outs[k]) & 7u) != 0;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const fe::FmLayout L(layout_flags, Np, nf, Nfp, E);
+    return fe::with_tet_order(Np, [&](auto o_) {
+        using O = decltype(o_);
+        static const What what("face-mass float32 fields+results Np=%d M=%d", O::NP, O::MF),
+            what_plain("face-mass float32 fields+results Np=%d M=%d, plain loads", O::NP, O::MF);
+        // (the field tables are untyped in FieldPtrs: the kernel reads P.out as float*)
+        return launch_mixed_facemass<fe::FmMixedGeomT<O::NP, O::NFP, O::MF, float>, fe::facemass_mixed_kernel<O::NP, O::NFP, O::MF, false, float>,
+                                     fe::facemass_mixed_kernel<O::NP, O::NFP, O::MF, true, float>>(
+            J, R, v, reinterpret_cast<double* const*>(outs), b, E, L.jfe | (dwords ? fe::kOpDwordStores : 0), L.rifj, plain, what,
+            what_plain, s, fe::kLaunchFloat32Results | (dwords ? fe::kLaunchDwordStores : 0));
     });
 }
 

@@ -29,7 +29,9 @@ Argument conventions kept from the reference:
                ``family.match_adjoint_family`` recognises only; ``"operator_adjoint"``: the
                operator-gradient kernels, for the einsums ``family.match_operator_adjoint`` recognises only;
                ``"mixed_family"``: grad, div and face-mass with float32 fields in float64 geometry factors and
-               operators, for the einsums ``family.match_mixed_family`` recognises only); in a dict, ``"prepared": True`` lets a
+               operators, for the einsums ``family.match_mixed_family`` recognises only, DESIGN.md §3j;
+               ``"mixed_state"``: the same einsums with float32 RESULTS -- float64 arithmetic, one rounding to nearest
+               where a result is stored, outputs allocated and expected as float32); in a dict, ``"prepared": True`` lets a
                bound launch (``timeit``) use a prepared copy of its operator
                matrices; ``"placement"`` (or ``$FEINSUM_PLACEMENT``): ``timeit``
                allocates one array per operand as the reference does; with the
@@ -210,16 +212,21 @@ def generate_input_arrays(cq: Any, einsum: BatchedEinsum, long_dim_length: int,
                              for name, arr in host.items()})
 
 
-def result_dtype(einsum: BatchedEinsum, row: int = 0) -> np.dtype:
-    """dtype of an output = ``np.result_type`` of its operands (codegen/loopy.py:258-260)."""
+def result_dtype(einsum: BatchedEinsum, row: int = 0, transform: Any = None) -> np.dtype:
+    """dtype of an output = ``np.result_type`` of its operands (codegen/loopy.py:258-260) -- except under the transform
+    ``"mixed_state"``, whose results are float32 (float64 arithmetic, rounded once at the store)."""
+    if _variant_from_transform(transform) == "mixed_state":
+        return np.dtype("float32")
     return np.result_type(*[arg.dtype for arg in einsum.args[row]])
 
 
-def generate_out_arrays(cq: Any, einsum: BatchedEinsum, long_dim_length: int, *, split: bool = False) -> Mapping[str, Any]:
+def generate_out_arrays(cq: Any, einsum: BatchedEinsum, long_dim_length: int, *, split: bool = False,
+                        transform: Any = None) -> Mapping[str, Any]:
     """Zero-filled device outputs ``_fe_out, _fe_out_0, ...`` (reference: measure.py:44-60).  *split*: one array each
     from the split allocator (``feinsum_amd.placement.zeros``: 4 MiB pieces alternating between two classes of physical
     memory) instead of the torch allocator; arrays below 8 MiB come from torch either way.  Allocated and zero-filled
-    on the queue's stream (see :class:`DeviceQueue`): a launch on that queue is ordered behind the fill."""
+    on the queue's stream (see :class:`DeviceQueue`): a launch on that queue is ordered behind the fill.  *transform*: the
+    one the arrays are for (:func:`result_dtype`)."""
     import torch
 
     q = _as_queue(cq)
@@ -229,11 +236,11 @@ def generate_out_arrays(cq: Any, einsum: BatchedEinsum, long_dim_length: int, *,
         if split and len(einsum.output_names) > 1:   # several arrays, allocated one after the other: say what is coming
             from feinsum_amd import placement
 
-            nbytes = sum(int(np.prod(shape)) * result_dtype(einsum, k).itemsize for k in range(len(einsum.output_names)))
+            nbytes = sum(int(np.prod(shape)) * result_dtype(einsum, k, transform).itemsize for k in range(len(einsum.output_names)))
             if nbytes >= placement.SPLIT_MIN_BYTES:
                 placement.split_reserve(nbytes, q.torch_device)
         for k, name in enumerate(einsum.output_names):
-            tdtype = getattr(torch, result_dtype(einsum, k).name)
+            tdtype = getattr(torch, result_dtype(einsum, k, transform).name)
             if split:
                 from feinsum_amd import placement
 
@@ -591,15 +598,16 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     einsum that ``family.match_adjoint_family`` recognises, else ``NotImplementedError``) runs the adjoint kernels, and
     ``"operator_adjoint"`` (that transform only: ``family.match_operator_adjoint``, else ``NotImplementedError``) the
     operator-gradient kernels.  ``"mixed_family"`` (that transform only: ``family.match_mixed_family``, else
-    ``NotImplementedError`` naming the rule) runs the DG kernels for float32 fields.
+    ``NotImplementedError`` naming the rule) runs the DG kernels for float32 fields, and ``"mixed_state"`` (that transform
+    only, the same einsums, the same error) their forms with float32 results.
     """
     variant = _variant_from_transform(transform)
-    if variant == "mixed_family":
+    if variant in ("mixed_family", "mixed_state"):
         if match_mixed_family(einsum) is None:
             raise NotImplementedError(
-                f"transform 'mixed_family': einsum '{einsum.get_subscripts()}' x {einsum.b} is not {MIXED_FAMILY_RULE}"
+                f"transform '{variant}': einsum '{einsum.get_subscripts()}' x {einsum.b} is not {MIXED_FAMILY_RULE}"
                 " (feinsum_amd.family.match_mixed_family)")
-        return "mixed_family"
+        return variant
     if variant == "adjoint":
         if match_adjoint_family(einsum) is None:
             raise NotImplementedError(
@@ -693,6 +701,45 @@ def _strided_runs(plan: KernelPlan, einsum: BatchedEinsum, arg_dict: Mapping[str
                     f"group out of bases of equal length, at least two of each length, or hand in C-contiguous arrays ({ELEMENT_SLICE_RULE})")
             runs.append((group[0], lds, members))
     return runs
+
+
+class _MixedStateLaunch:
+    """grad, div or face-mass of tetrahedra p = 1..4 with float32 fields AND float32 results in float64 geometry, operator and
+    arithmetic (transform ``"mixed_state"``): the named entry points ``fe_grad3d_mixed_state_f64`` /
+    ``fe_div3d_mixed_state_f64`` / ``fe_facemass_mixed_state_f64``, one call per group of ``_family_groups``.  No prepared
+    operators."""
+
+    fields_f32 = True     # (operator.py: float32 fields, a launch of its own)
+
+    def __init__(self, plan: KernelPlan, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any]) -> None:
+        self.plan = plan
+        self._keep = (arg_dict, outs)
+        role, rows, p = plan.roles, einsum.args, plan.params
+        op_role, in_role = ("D", "u") if "D" in role else ("R", "v")
+        self.entry_point = {FAMILY_GRAD: "fe_grad3d_mixed_state_f64", FAMILY_DIV: "fe_div3d_mixed_state_f64",
+                            FAMILY_FACEMASS: "fe_facemass_mixed_state_f64"}[plan.family]
+        j_axis = einsum.in_idx_sets[role["J"]].index(plan.long_index)
+        self.E = int(arg_dict[rows[0][role["J"]].name].shape[j_axis])
+        self.calls = []      # (function, arguments in front of the stream)
+        for group in _family_groups(plan, einsum):
+            first = rows[group[0]]
+            J, A = arg_dict[first[role["J"]].name].data_ptr(), arg_dict[first[role[op_role]].name].data_ptr()
+            vptrs = [arg_dict[rows[m][role[in_role]].name].data_ptr() for m in group]
+            optrs = [outs[m].data_ptr() for m in group]
+            if plan.family == FAMILY_GRAD:
+                self.calls.append((_hip.grad3d_mixed_state, (J, A, vptrs, optrs, self.E, p["Np"], plan.layout_flags)))
+            elif plan.family == FAMILY_DIV:
+                self.calls.append((_hip.div3d_mixed_state, (J, A, vptrs, optrs, self.E, p["Np"], plan.layout_flags)))
+            else:
+                self.calls.append((_hip.facemass_mixed_state, (J, A, vptrs, optrs, self.E, p["Np"], p["nf"], p["Nfp"],
+                                                               plan.layout_flags)))
+
+    def launch(self, stream_ptr: int) -> None:
+        for fn, args in self.calls:
+            fn(*args, stream=stream_ptr)
+
+    def time_batch(self, n: int, stream_ptr: int) -> float:
+        return _hip.time_with_events(self.launch, n, stream_ptr)
 
 
 class _StridedFamilyLaunch:
@@ -832,7 +879,7 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     given = {name: out_dict[name] for name in einsum.output_names if out_dict is not None and name in out_dict}
     for k, name in enumerate(einsum.output_names):
         if name in given:
-            if _check_tensor(name, given[name], out_shape, result_dtype(einsum, k), q, out_axis):
+            if _check_tensor(name, given[name], out_shape, result_dtype(einsum, k, transform), q, out_axis):
                 sliced.append(name)
     _refuse_aliased_outputs(einsum, arg_dict, given)     # before anything is allocated, prepared or launched
     alpha, beta = _check_scale(alpha, beta)
@@ -850,7 +897,7 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
     owned = []                # ... and the arrays: they belong to the queue's stream (DeviceQueue)
     with _on_stream_of(q):
         for k, name in enumerate(einsum.output_names):
-            dt = result_dtype(einsum, k)
+            dt = result_dtype(einsum, k, transform)
             if name in given:
                 outs.append(given[name])
             else:
@@ -874,6 +921,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
             bound = AdjointLaunch(match_operator_adjoint(einsum), einsum, arg_dict, outs, stream=q.stream)
     elif kind == "mixed_family":     # (accumulation: the "axpby" route -- accumulate_route knows no other for it)
         bound = _FamilyLaunch(match_mixed_family(einsum), einsum, arg_dict, outs, None)
+    elif kind == "mixed_state":      # (float32 outputs: result_dtype; accumulation by "axpby" with float32 temporaries)
+        bound = _MixedStateLaunch(match_mixed_family(einsum), einsum, arg_dict, outs)
     elif kind == "family" and sliced:
         bound = _StridedFamilyLaunch(match_family(einsum), einsum, arg_dict, outs)
     elif kind == "family":
@@ -1018,6 +1067,9 @@ def validate_batched_einsum_transform(einsum: BatchedEinsum, cq: Any, transform:
                                 optimize="optimal")
                 for name, row in zip(einsum.output_names, einsum.args)}
     outs = evaluate(einsum, q, arg_dict, transform=transform, wait=True, schedule=schedule)
+    state = _variant_from_transform(transform) == "mixed_state"     # float32 results: the reference rounded likewise
+    if state:
+        ref_outs = {name: ref.astype(np.float32) for name, ref in ref_outs.items()}
     if set(ref_outs) != set(outs):
         raise RuntimeError("Output names mismatch")
     rows = dict(zip(einsum.output_names, range(len(einsum.args))))
@@ -1026,7 +1078,7 @@ def validate_batched_einsum_transform(einsum: BatchedEinsum, cq: Any, transform:
         ref = ref_outs[name]
         if got.dtype != ref.dtype:
             raise RuntimeError(f"dtype mismatch for output '{name}'")
-        atol, rtol = _tolerances(validation_dtype(einsum, rows[name]))
+        atol, rtol = _tolerances(np.dtype("float32") if state else validation_dtype(einsum, rows[name]))
         try:
             np.testing.assert_allclose(got, ref, atol=atol, rtol=rtol)
         except AssertionError as exc:
@@ -1094,17 +1146,17 @@ def timeit_details(einsum: BatchedEinsum, *, transform: Any = None, cq: Any = No
 
         try:
             with torch.cuda.device(q.torch_device):
-                out_dict = generate_out_arrays(q, einsum, long_dim_length, split=True)
+                out_dict = generate_out_arrays(q, einsum, long_dim_length, split=True, transform=transform)
             infos = {n: placement.split_info(t) for n, t in out_dict.items()}
             report = {"mode": "split", "outputs": {n: ({"pieces_by_class": i["pieces_by_class"], "first_pieces": i["first_pieces"]} if i
                                                       else "torch allocation (below 8 MiB, or no second class of physical memory found)") for n, i in infos.items()},
                       "alloc_ms": round(sum(i.get("alloc_ms", 0.0) for i in infos.values()), 3)}
         except (RuntimeError, HipLibraryError) as exc:     # the allocator could not serve: the reference's protocol, and say so
             logger.warning("split allocator not available (%s); timing torch allocations", str(exc)[:160])
-            out_dict = generate_out_arrays(q, einsum, long_dim_length)
+            out_dict = generate_out_arrays(q, einsum, long_dim_length, transform=transform)
             report = {"mode": "separate", "fallback": f"split allocator failed: {str(exc)[:160]}"}
     else:
-        out_dict = generate_out_arrays(q, einsum, long_dim_length)
+        out_dict = generate_out_arrays(q, einsum, long_dim_length, transform=transform)
     # `transform={"prepared": True}`: the operator matrices are written once in fragment layout (see
     # _FamilyLaunch.prepare_operators) instead of being rebuilt by every launch
     prepare = _prepared_from_transform(transform, False)

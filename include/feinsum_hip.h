@@ -448,6 +448,22 @@ int fe_div3d_mixed_f64(const double* J, const double* D, const void* const* v, d
 int fe_facemass_mixed_f64(const double* J, const double* R, const void* const* v, double* const* outs,
                           int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream);
 
+/* The same with FLOAT32 RESULTS: the arguments of fe_*_mixed_f64, `outs` a table of `float*` (spelled `void**`; the table is not written).  Geometry,
+ * operator, products and sums stay float64; every output entry is float32(x), x the float64 value fe_*_mixed_f64 stores for that
+ * entry in the same launch, narrowed once by IEEE round-to-nearest-even where it enters the wave's transposition buffer (results
+ * beyond the float32 range become +-Inf, NaN stays NaN).  Results do not depend on where the arrays lie.
+ * Scope first: another shape than tetrahedra p = 1..4 is FE_EUNSUPPORTED; then a field or output that is not 4-byte aligned, a J
+ * or operator that is not 8-byte aligned: FE_EINVAL; both before any device work.  The outputs of a launch leave by 16-byte
+ * stores when every output plane starts on an 8-byte boundary (div, face-mass: every output; grad: every output, and E Np even),
+ * and by 4-byte stores otherwise.  fe_last_launch_info as for fe_*_mixed_f64, with the further `kind` bits 256: float32
+ * results, 512: the 4-byte store form.  Asynchronous on `stream`; E = 0 launches nothing. */
+int fe_grad3d_mixed_state_f64(const double* J, const double* D, const void* const* v, void** outs,
+                              int64_t E, int32_t Np, int32_t b, int32_t layout_flags, void* stream);
+int fe_div3d_mixed_state_f64(const double* J, const double* D, const void* const* v, void** outs,
+                             int64_t E, int32_t Np, int32_t b, int32_t layout_flags, void* stream);
+int fe_facemass_mixed_state_f64(const double* J, const double* R, const void* const* v, void** outs,
+                                int64_t E, int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* stream);
+
 /* float64 grad 'xre,rij,ej->xei', div 'xre,rij,xej->ei' and face-mass 'ef,fij,fej->ei' x b on an ELEMENT SLICE of larger
  * arrays: E is the number of elements of the launch, and every array whose element axis is not its leading one has a
  * leading dimension of its own, in elements, as BLAS has lda (every pointer addresses element 0 of the slice):
