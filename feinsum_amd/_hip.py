@@ -151,9 +151,11 @@ SIGNATURES = {
     "fe_time_launches": (_int, [_i32, C.POINTER(ArgPack), _i32, _p, C.POINTER(C.c_float)]),
     "fe_einsum_generic": (_int, [C.POINTER(EinsumDesc), _pp, _p, _p]),
     "fe_einsum_contract": (_int, [C.POINTER(EinsumDesc), _pp, _p, _p]),
+    "fe_einsum_contract_acc": (_int, [C.POINTER(EinsumDesc), _pp, _p, _f64, _f64, _p]),
     "fe_einsum_contract_groups": (_int, [C.POINTER(EinsumDesc), C.POINTER(_i32), C.POINTER(_i32)]),
     "fe_einsum_reduce_plan": (_int, [C.POINTER(EinsumDesc), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_size)]),
     "fe_einsum_reduce": (_int, [C.POINTER(EinsumDesc), _pp, _p, _p, _size, _p]),
+    "fe_einsum_reduce_acc": (_int, [C.POINTER(EinsumDesc), _pp, _p, _p, _size, _f64, _f64, _p]),
     "fe_geomadj_f64": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _p]),
     "fe_facemass_adj_f64": (_int, [_p, _p, _pp, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
     "fe_opgrad_plan": (_int, [_i64, _i32, C.POINTER(_i64), C.POINTER(_size)]),
@@ -593,6 +595,14 @@ def einsum_contract(desc: EinsumDesc, operands: Sequence[int], out: int, stream:
     check(load_library().fe_einsum_contract(C.byref(desc), _ptr_array(operands), out, stream))
 
 
+def einsum_contract_acc(desc: EinsumDesc, operands: Sequence[int], out: int, alpha: float, beta: float,
+                        stream: int = 0) -> None:
+    """``out <- alpha * E + beta * out`` inside the contraction kernel (``fe_einsum_contract_acc``), *E* what
+    :func:`einsum_contract` stores; ``beta == 0`` does not read *out*."""
+    check(load_library().fe_einsum_contract_acc(C.byref(desc), _ptr_array(operands), out, float(alpha), float(beta),
+                                                stream))
+
+
 REDUCE_PATH_NAMES = {FE_REDUCE_VALU: "valu", FE_REDUCE_MFMA: "mfma"}
 
 
@@ -610,6 +620,14 @@ def einsum_reduce(desc: EinsumDesc, operands: Sequence[int], out: int, workspace
     workspace of at least the bytes :func:`einsum_reduce_plan` reports."""
     check(load_library().fe_einsum_reduce(C.byref(desc), _ptr_array(operands), out, workspace,
                                           C.c_size_t(int(workspace_bytes)), stream))
+
+
+def einsum_reduce_acc(desc: EinsumDesc, operands: Sequence[int], out: int, workspace: int, workspace_bytes: int,
+                      alpha: float, beta: float, stream: int = 0) -> None:
+    """``out <- alpha * E + beta * out`` in the combine launch of the split reduction (``fe_einsum_reduce_acc``), *E* what
+    :func:`einsum_reduce` stores; same workspace; ``beta == 0`` does not read *out*."""
+    check(load_library().fe_einsum_reduce_acc(C.byref(desc), _ptr_array(operands), out, workspace,
+                                              C.c_size_t(int(workspace_bytes)), float(alpha), float(beta), stream))
 
 
 def set_tail_rounds(rounds: int) -> int:

@@ -163,6 +163,19 @@ def intermediate_shapes(steps: Sequence[Step], extent: Mapping[str, int]) -> Dic
             for st in steps if st.result is not None}
 
 
+def check_accumulating_steps(steps: Sequence[Step]) -> None:
+    """``NotImplementedError`` unless the step of *steps* (``plan_steps``) that writes the einsum's output can accumulate
+    inside its kernel (``{"accumulate": "kernel"}``): a two-operand step, which runs on the contraction kernel
+    (``fe_einsum_contract_acc``).  A one-input last step -- a caller's schedule that ends in a pure reduction -- runs on
+    the generic kernel, which has no accumulating form."""
+    for st in steps:
+        if st.result is None and len(st.inputs) != 2:
+            raise NotImplementedError(
+                f"the step '{st.subscripts}' that writes the output has {len(st.inputs)} input(s) and runs on the generic"
+                ' kernel, which has no accumulating form: {"accumulate": "kernel"} needs a two-operand last step'
+                ' (use {"accumulate": "axpby"} or another schedule)')
+
+
 _REAL = (np.dtype("float64"), np.dtype("float32"))
 
 
@@ -207,18 +220,28 @@ class ContractionLaunch:
 
     The intermediates are allocated on *stream* (the queue's stream: the launches run there), so that the caching
     allocator hands their blocks to later allocations only in that stream's order; a launch on another stream marks
-    them as used by it (``record_stream``) so that they outlive its work too."""
+    them as used by it (``record_stream``) so that they outlive its work too.
+
+    *scale* = ``(alpha, beta)``: the launch accumulates, ``out <- alpha E + beta out``, inside the kernel of the step that
+    writes each row's output (``fe_einsum_contract_acc``); the earlier steps and the intermediates are those of the
+    overwriting launch.  ``NotImplementedError`` (:func:`check_accumulating_steps`) before anything is allocated when
+    that step is not a two-operand one."""
 
     entry_point = "fe_einsum_contract"
 
     def __init__(self, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any],
-                 sizes: Mapping[str, int], schedule: Optional[ContractionSchedule] = None, stream: Any = None) -> None:
+                 sizes: Mapping[str, int], schedule: Optional[ContractionSchedule] = None, stream: Any = None,
+                 scale: Optional[Tuple[float, float]] = None) -> None:
         import contextlib
 
         import torch
 
         extent = _extents(einsum, sizes)
         self.steps = plan_steps(einsum, schedule)
+        self.scale = scale
+        if scale is not None:
+            check_accumulating_steps(self.steps)
+            self.entry_point = "fe_einsum_contract_acc"
         self.step_dtypes = plan_step_dtypes(einsum, self.steps)
         tmp_dtype = {st.result: dt for st, dt in zip(self.steps, self.step_dtypes) if st.result is not None}
         device = outs[0].device
@@ -237,6 +260,8 @@ class ContractionLaunch:
                 target = out if st.result is None else self.intermediates[st.result]
                 d = _desc(st.subscripts, tensors, extent, dtypes)
                 fn = _hip.einsum_contract if len(tensors) == 2 else _hip.einsum_generic
+                if scale is not None and st.result is None:
+                    fn = _contract_acc_call(*scale)
                 self.launches.append((fn, d, [t.data_ptr() for t in tensors], target.data_ptr()))
 
     def launch(self, stream_ptr: int) -> None:
@@ -252,3 +277,10 @@ class ContractionLaunch:
 
     def time_batch(self, n: int, stream_ptr: int) -> float:
         return _hip.time_with_events(self.launch, n, stream_ptr)
+
+
+def _contract_acc_call(alpha: float, beta: float):
+    def call(desc: "_hip.EinsumDesc", operands: Sequence[int], out: int, stream: int) -> None:
+        _hip.einsum_contract_acc(desc, operands, out, alpha, beta, stream)
+    call.entry_point = "fe_einsum_contract_acc"
+    return call

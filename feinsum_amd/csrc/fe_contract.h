@@ -116,9 +116,21 @@ __device__ __forceinline__ int64_t ct_koff(const int64_t (&idx)[kCtMaxIdx], int 
 // only, [kb, ke), and writes its masked partial tile into slice ks of the workspace C[ks * c_size + ...] (the layout of
 // the output), which reduce_combine_kernel then sums in slice order.  The MFMA loop, the staging and the loads are
 // those of the plain kernel; SPLIT = false is the plain kernel.
-template <typename T, int V, typename TA = T, typename TB = T, int VB = V, bool SPLIT = false>
+//
+// ACC (fe_einsum_contract_acc): C <- alpha E + beta C, E the sum above.  The kernel then takes two more arguments behind
+// C, alpha and beta of type T (SCALE...: empty without ACC, so the plain and the split-K instantiations keep their
+// argument list).  Only the store epilogue differs.  beta != 0 (block-uniform: one scalar branch per tile): a thread
+// first loads all of its up to 16 old values -- under the guards, at the addresses and through the row map of its stores,
+// so every entry is read and written by one thread and nothing is ordered across threads -- and then stores
+// axpby_combine(alpha, E, beta, old); the loads are issued before the first store, so their latency is paid once per
+// tile.  beta == 0: alpha E is stored and nothing is read.  The loads stand behind the k loop's last barrier.
+template <typename T, int V, typename TA = T, typename TB = T, int VB = V, bool SPLIT = false, bool ACC = false,
+          typename... SCALE>
 __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan P, const TA* __restrict__ A,
-                                                                   const TB* __restrict__ B, T* __restrict__ C) {
+                                                                   const TB* __restrict__ B, T* __restrict__ C,
+                                                                   SCALE... scale) {
+    static_assert(!(SPLIT && ACC), "the split-K partials are combined by reduce_combine_kernel, which accumulates");
+    static_assert(sizeof...(SCALE) == (ACC ? 2 : 0), "ACC: (alpha, beta) behind C; nothing otherwise");
     typedef CtMfma<T> Mfma;
     typedef typename Mfma::acc_t acc_t;
     constexpr int VA = V;
@@ -271,18 +283,88 @@ __global__ __launch_bounds__(kCtThreads) void contract_mfma_kernel(ContractPlan 
             colC[g] = 0;
             if (cv[g]) ct_decode(col, P.nn, P.n_ext, P.n_sc, P.n_sc, P.n_sc, colC[g], unused0, unused1);
         }
+        if constexpr (ACC) {
+            const T ab[2] = {T(scale)...};
+            const T alpha = ab[0], beta = ab[1];
+            int64_t offC[2][4];
+            bool rv[2][4];
 #pragma unroll
-        for (int f = 0; f < 2; ++f)
+            for (int f = 0; f < 2; ++f)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = m0 + 32 * wm + 16 * f + Mfma::row(lane, r);
-                if (row >= P.M) continue;
-                int64_t rowC;
-                ct_decode(row, P.nm, P.m_ext, P.m_sc, P.m_sc, P.m_sc, rowC, unused0, unused1);
+                for (int r = 0; r < 4; ++r) {
+                    const int64_t row = m0 + 32 * wm + 16 * f + Mfma::row(lane, r);
+                    rv[f][r] = row < P.M;
+                    int64_t rowC = 0;
+                    if (rv[f][r]) ct_decode(row, P.nm, P.m_ext, P.m_sc, P.m_sc, P.m_sc, rowC, unused0, unused1);
+                    offC[f][r] = boffC + rowC;
+                }
+            if (beta != T(0)) {
+                // Loads, then the 16 combines in straight-line code, then the stores: the one wait for the old values stands
+                // in front of the combines.  (A combine inside a store's own guard put a wait -- which counts the earlier
+                // stores too -- in front of every store: 16 round trips per tile, 8 % on a 1024^3 GEMM.)  A tile inside C,
+                // which is block-uniform, needs no guard at all: its loads and stores are straight-line code as well.
+                const bool full = m0 + kCtBM <= P.M && n0 + kCtBM <= P.N;
+                T val[2][4][2];
+                if (full) {
 #pragma unroll
-                for (int g = 0; g < 2; ++g)
-                    if (cv[g]) Cs[boffC + rowC + colC[g]] = acc[f][g][r];
+                    for (int f = 0; f < 2; ++f)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int g = 0; g < 2; ++g) val[f][r][g] = Cs[offC[f][r] + colC[g]];
+                } else {
+#pragma unroll
+                    for (int f = 0; f < 2; ++f)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int g = 0; g < 2; ++g) val[f][r][g] = rv[f][r] && cv[g] ? Cs[offC[f][r] + colC[g]] : T(0);
+                }
+#pragma unroll
+                for (int f = 0; f < 2; ++f)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int g = 0; g < 2; ++g) val[f][r][g] = axpby_combine(alpha, acc[f][g][r], beta, val[f][r][g]);
+                if (full) {
+#pragma unroll
+                    for (int f = 0; f < 2; ++f)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int g = 0; g < 2; ++g) Cs[offC[f][r] + colC[g]] = val[f][r][g];
+                } else {
+#pragma unroll
+                    for (int f = 0; f < 2; ++f)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int g = 0; g < 2; ++g)
+                                if (rv[f][r] && cv[g]) Cs[offC[f][r] + colC[g]] = val[f][r][g];
+                }
+            } else {
+#pragma unroll
+                for (int f = 0; f < 2; ++f)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int g = 0; g < 2; ++g)
+                            if (rv[f][r] && cv[g]) Cs[offC[f][r] + colC[g]] = alpha * acc[f][g][r];
             }
+        } else {
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int64_t row = m0 + 32 * wm + 16 * f + Mfma::row(lane, r);
+                    if (row >= P.M) continue;
+                    int64_t rowC;
+                    ct_decode(row, P.nm, P.m_ext, P.m_sc, P.m_sc, P.m_sc, rowC, unused0, unused1);
+#pragma unroll
+                    for (int g = 0; g < 2; ++g)
+                        if (cv[g]) Cs[boffC + rowC + colC[g]] = acc[f][g][r];
+                }
+        }
     }
 }
 

@@ -168,9 +168,12 @@ __global__ __launch_bounds__(kRdThreads) void reduce_partial_kernel(ReducePlan P
 
 // out[o] = sum_s ws[s * n_out + o]: one wave per output entry, lane l adds slices l, l + 64, ... in order, then
 // a fixed butterfly.  Grid: ceil(n_out / 4) blocks of 256.
-template <typename T>
+// ACC (fe_einsum_reduce_acc): out[o] <- alpha (that sum) + beta out[o], two more arguments of type T behind `slices`
+// (SCALE...: empty without ACC); beta == 0 does not read out (axpby_combine, fe_common.h).  The sum is the same.
+template <typename T, bool ACC = false, typename... SCALE>
 __global__ __launch_bounds__(kRdThreads) void reduce_combine_kernel(const T* __restrict__ ws, T* __restrict__ out,
-                                                                    int64_t n_out, int64_t slices) {
+                                                                    int64_t n_out, int64_t slices, SCALE... scale) {
+    static_assert(sizeof...(SCALE) == (ACC ? 2 : 0), "ACC: (alpha, beta) behind slices; nothing otherwise");
     const int64_t o = (int64_t)blockIdx.x * (kRdThreads / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     T acc = T(0);
@@ -178,7 +181,13 @@ __global__ __launch_bounds__(kRdThreads) void reduce_combine_kernel(const T* __r
         for (int64_t s = lane; s < slices; s += 64) acc += ws[s * n_out + o];
 #pragma unroll
     for (int w = 32; w >= 1; w /= 2) acc += __shfl_xor(acc, w, 64);
-    if (o < n_out && lane == 0) out[o] = acc;
+    if constexpr (ACC) {
+        const T ab[2] = {T(scale)...};
+        const T alpha = ab[0], beta = ab[1];
+        if (o < n_out && lane == 0) out[o] = beta != T(0) ? axpby_combine(alpha, acc, beta, out[o]) : alpha * acc;
+    } else {
+        if (o < n_out && lane == 0) out[o] = acc;
+    }
 }
 
 }  // namespace fe

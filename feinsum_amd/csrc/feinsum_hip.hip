@@ -1587,6 +1587,10 @@ struct SplitK {   // split-K launch of contract_launch: slices of slice_len k ea
     void* ws;
 };
 
+struct AccScale {   // out <- alpha E + beta out (fe_einsum_contract_acc, fe_einsum_reduce_acc)
+    double alpha, beta;
+};
+
 struct ReduceSetup {
     int path;               // FE_REDUCE_VALU / FE_REDUCE_MFMA
     int64_t n_out, slices;
@@ -2725,9 +2729,10 @@ int fe_einsum_generic(const fe_einsum_desc* d, const void* const* operands, void
 }
 
 // fe_einsum_contract, and (split: not null) the split-K launch of fe_einsum_reduce, which writes split->slices partial
-// outputs into split->ws instead of `out`.
+// outputs into split->ws instead of `out`.  acc (not null, never with split): out <- alpha E + beta out in the store
+// epilogue of the ACC instantiations (fe_einsum_contract_acc).
 static int contract_launch(const fe_einsum_desc* d, const void* const* operands, void* out, void* stream,
-                           const SplitK* split) {
+                           const SplitK* split, const AccScale* acc = nullptr) {
     if (!d || !operands) return fail(FE_EINVAL, "contract: null descriptor");
     if (d->n_operands != 2)
         return fail(FE_EUNSUPPORTED, "contract: %d operands (the contraction kernel takes exactly 2)", d->n_operands);
@@ -2894,6 +2899,41 @@ static int contract_launch(const fe_einsum_desc* d, const void* const* operands,
         return FE_OK;
     }
     const dim3 grid((unsigned)(P.n_tiles < cap ? P.n_tiles : cap)), block(fe::kCtThreads);
+    if (acc) {   // the ladder below, on the accumulating instantiations
+#define FE_CONTRACT_ACC_CASE(T, TA, TB, VVA, VVB, NAME)                                                                 \
+    do {                                                                                                                \
+        static PerDeviceOnce once;                                                                                      \
+        if (int rc = configured(once, fe::contract_mfma_kernel<T, VVA, TA, TB, VVB, false, true, T, T>, NAME " acc", 0, \
+                                fe::kCtThreads, fe::kCtBlocksPerCu))                                                    \
+            return rc;                                                                                                  \
+        hipLaunchKernelGGL((fe::contract_mfma_kernel<T, VVA, TA, TB, VVB, false, true, T, T>), grid, block, 0, s, P,    \
+                           static_cast<const TA*>(opA), static_cast<const TB*>(opB), static_cast<T*>(out),              \
+                           (T)acc->alpha, (T)acc->beta);                                                                \
+    } while (0)
+        if (a_f32 && b_f32) {
+            if (VA > 1) FE_CONTRACT_ACC_CASE(double, float, float, 4, 4, "contract f32 x f32 -> f64 (16-byte groups)");
+            else FE_CONTRACT_ACC_CASE(double, float, float, 1, 1, "contract f32 x f32 -> f64");
+        } else if (a_f32) {
+            if (VA > 1 && VB > 1) FE_CONTRACT_ACC_CASE(double, float, double, 4, 2, "contract f32 x f64 (16-byte groups)");
+            else if (VA > 1) FE_CONTRACT_ACC_CASE(double, float, double, 4, 1, "contract f32 x f64 (A 16-byte groups)");
+            else if (VB > 1) FE_CONTRACT_ACC_CASE(double, float, double, 1, 2, "contract f32 x f64 (B 16-byte groups)");
+            else FE_CONTRACT_ACC_CASE(double, float, double, 1, 1, "contract f32 x f64");
+        } else if (b_f32) {
+            if (VA > 1 && VB > 1) FE_CONTRACT_ACC_CASE(double, double, float, 2, 4, "contract f64 x f32 (16-byte groups)");
+            else if (VA > 1) FE_CONTRACT_ACC_CASE(double, double, float, 2, 1, "contract f64 x f32 (A 16-byte groups)");
+            else if (VB > 1) FE_CONTRACT_ACC_CASE(double, double, float, 1, 4, "contract f64 x f32 (B 16-byte groups)");
+            else FE_CONTRACT_ACC_CASE(double, double, float, 1, 1, "contract f64 x f32");
+        } else if (f64) {
+            if (V > 1) FE_CONTRACT_ACC_CASE(double, double, double, 2, 2, "contract f64 (16-byte groups)");
+            else FE_CONTRACT_ACC_CASE(double, double, double, 1, 1, "contract f64");
+        } else {
+            if (V > 1) FE_CONTRACT_ACC_CASE(float, float, float, 4, 4, "contract f32 (16-byte groups)");
+            else FE_CONTRACT_ACC_CASE(float, float, float, 1, 1, "contract f32");
+        }
+#undef FE_CONTRACT_ACC_CASE
+        FE_HIP_CHECK(hipGetLastError());
+        return FE_OK;
+    }
 #define FE_CONTRACT_CASE(T, VV, NAME)                                                                                   \
     do {                                                                                                                \
         static PerDeviceOnce once;                                                                                      \
@@ -2941,6 +2981,14 @@ int fe_einsum_contract(const fe_einsum_desc* d, const void* const* operands, voi
     return contract_launch(d, operands, out, stream, nullptr);
 }
 
+int fe_einsum_contract_acc(const fe_einsum_desc* d, const void* const* operands, void* out, double alpha, double beta,
+                           void* stream) {
+    if (!std::isfinite(alpha) || !std::isfinite(beta))
+        return fail(FE_EINVAL, "contract: alpha and beta must be finite (got %g, %g)", alpha, beta);
+    const AccScale acc = {alpha, beta};
+    return contract_launch(d, operands, out, stream, nullptr, &acc);
+}
+
 int fe_einsum_reduce_plan(const fe_einsum_desc* d, int32_t* path, int64_t* slices, size_t* workspace_bytes) {
     if (!path || !slices || !workspace_bytes) return fail(FE_EINVAL, "reduce plan: null pointer");
     ReduceSetup r;
@@ -2965,11 +3013,21 @@ int launch_reduce_combine(const char* name, const void* workspace, void* out, in
     return FE_OK;
 }
 
-}  // namespace
-extern "C" {
+// out[o] <- alpha (that sum) + beta out[o]: the second launch of fe_einsum_reduce_acc.
+template <typename T>
+int launch_reduce_combine_acc(const char* name, const void* workspace, void* out, int64_t n_out, int64_t slices,
+                              const AccScale& acc, hipStream_t s) {
+    static PerDeviceOnce once;
+    if (int rc = configured(once, fe::reduce_combine_kernel<T, true, T, T>, name, 0, fe::kRdThreads, 1)) return rc;
+    const dim3 cgrid((unsigned)((n_out + fe::kRdThreads / 64 - 1) / (fe::kRdThreads / 64))), cblock(fe::kRdThreads);
+    hipLaunchKernelGGL((fe::reduce_combine_kernel<T, true, T, T>), cgrid, cblock, 0, s, static_cast<const T*>(workspace),
+                       static_cast<T*>(out), n_out, slices, (T)acc.alpha, (T)acc.beta);
+    return FE_OK;
+}
 
-int fe_einsum_reduce(const fe_einsum_desc* d, const void* const* operands, void* out, void* workspace,
-                     size_t workspace_bytes, void* stream) {
+// fe_einsum_reduce, and (acc: not null) fe_einsum_reduce_acc: the partials alike, the accumulating combine launch.
+int reduce_launch(const fe_einsum_desc* d, const void* const* operands, void* out, void* workspace,
+                  size_t workspace_bytes, void* stream, const AccScale* acc) {
     if (!operands) return fail(FE_EINVAL, "reduce: null operand array");
     ReduceSetup r;
     if (int rc = reduce_setup("reduce", d, &r)) return rc;
@@ -3024,11 +3082,32 @@ int fe_einsum_reduce(const fe_einsum_desc* d, const void* const* operands, void*
 #undef FE_REDUCE_CASE
         FE_HIP_CHECK(hipGetLastError());
     }
-    if (int rc = f64 ? launch_reduce_combine<double>("reduce combine f64", workspace, out, r.n_out, r.slices, s)
-                     : launch_reduce_combine<float>("reduce combine f32", workspace, out, r.n_out, r.slices, s))
+    if (acc) {
+        if (int rc = f64 ? launch_reduce_combine_acc<double>("reduce combine f64 acc", workspace, out, r.n_out, r.slices, *acc, s)
+                         : launch_reduce_combine_acc<float>("reduce combine f32 acc", workspace, out, r.n_out, r.slices, *acc, s))
+            return rc;
+    } else if (int rc = f64 ? launch_reduce_combine<double>("reduce combine f64", workspace, out, r.n_out, r.slices, s)
+                            : launch_reduce_combine<float>("reduce combine f32", workspace, out, r.n_out, r.slices, s)) {
         return rc;
+    }
     FE_HIP_CHECK(hipGetLastError());
     return FE_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int fe_einsum_reduce(const fe_einsum_desc* d, const void* const* operands, void* out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    return reduce_launch(d, operands, out, workspace, workspace_bytes, stream, nullptr);
+}
+
+int fe_einsum_reduce_acc(const fe_einsum_desc* d, const void* const* operands, void* out, void* workspace,
+                         size_t workspace_bytes, double alpha, double beta, void* stream) {
+    if (!std::isfinite(alpha) || !std::isfinite(beta))
+        return fail(FE_EINVAL, "reduce: alpha and beta must be finite (got %g, %g)", alpha, beta);
+    const AccScale acc = {alpha, beta};
+    return reduce_launch(d, operands, out, workspace, workspace_bytes, stream, &acc);
 }
 
 int fe_einsum_contract_groups(const fe_einsum_desc* d, int32_t* out_group, int32_t* sum_group) {

@@ -813,6 +813,17 @@ def accumulate_route(einsum: BatchedEinsum, transform: Any = None) -> str:
     output where they store the new one -- for float64 grad and div of tetrahedra p = 1..4, either operator layout, the
     variant ``"auto"`` or ``"mfma"``; ``NotImplementedError`` for everything else (face-mass accumulates through
     ``"kernel"``).
+
+    The contraction and the split reduction accumulate inside their kernels on request, never by default:
+    ``{"variant": "contraction", "accumulate": "kernel"}`` returns ``"kernel"`` for an einsum of two or more float32 /
+    float64 operands (``fe_einsum_contract_acc``: the store epilogue of the step that writes the output), and
+    ``{"variant": "reduction", "accumulate": "kernel"}`` for float32 / float64 operands (``fe_einsum_reduce_acc``: the
+    launch that sums the partials).  Without a forced route both variants stay ``"axpby"``, and ``"epilogue"`` stays
+    ``NotImplementedError`` for them.  One check is left to bind time, because it needs the schedule and the sizes, which
+    this function does not see: the step that writes the output must run on the contraction or the split-reduction
+    kernel; a last step on the generic kernel (a caller's schedule whose last step has one input, a ``"generic"`` last
+    step of ``reduction.plan_reduction``) is ``NotImplementedError`` naming the step, before anything is allocated or
+    launched.
     """
     forced = transform.get("accumulate") if isinstance(transform, Mapping) else None
     if forced is not None and forced not in ACCUMULATE_ROUTES:
@@ -831,6 +842,13 @@ def accumulate_route(einsum: BatchedEinsum, transform: Any = None) -> str:
         raise NotImplementedError(
             f"einsum '{einsum.get_subscripts()}' x {einsum.b} has no accumulating epilogue under this transform (float64"
             f" grad or div of tetrahedra p = 1..4, variant auto or mfma){hint}")
+    if forced == "kernel" and variant in ("contraction", "reduction"):
+        real = all(np.dtype(d) in (np.dtype("float64"), np.dtype("float32")) for d in einsum.arg_to_dtype.values())
+        if real and (variant == "reduction" or einsum.n >= 2):
+            return "kernel"
+        raise NotImplementedError(
+            f"einsum '{einsum.get_subscripts()}' x {einsum.b} has no accumulating kernel under the transform '{variant}'"
+            " (float32 / float64 operands" + ("" if variant == "reduction" else ", two or more of them") + ")")
     if forced == "kernel" and not fused:
         raise NotImplementedError(
             f"einsum '{einsum.get_subscripts()}' x {einsum.b} has no accumulating kernel under this transform (float64"
@@ -911,9 +929,11 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
             owned.extend(outs)
     kind = launch_kind(einsum, transform, sizes)
     if kind == "contraction":
-        bound = ContractionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
+        bound = ContractionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream,
+                                  scale=(alpha, beta) if route == "kernel" else None)
     elif kind == "reduction":
-        bound = ReductionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream)
+        bound = ReductionLaunch(einsum, arg_dict, outs, sizes, schedule, stream=q.stream,
+                                scale=(alpha, beta) if route == "kernel" else None)
     elif kind == "adjoint":
         bound = AdjointLaunch(match_adjoint_family(einsum), einsum, arg_dict, outs)
     elif kind == "operator_adjoint":
@@ -998,8 +1018,10 @@ def evaluate(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any], *,
     two ways (:func:`accumulate_route`; the bound launch says which in ``bound.accumulate``): the accumulating face-mass
     kernel, which reads the old output where it stores the new one, or the ordinary launch into a temporary (allocated at
     bind time on the queue's stream) followed by ``fe_axpby`` on the same stream.  ``transform={"accumulate": "epilogue"}``
-    opts grad and div of tetrahedra p = 1..4 into kernels that accumulate the same way as the face-mass one.  (1, 0), the default, is the code path
-    without any of this.  DESIGN.md section 3m.
+    opts grad and div of tetrahedra p = 1..4 into kernels that accumulate the same way as the face-mass one, and
+    ``{"variant": "contraction" | "reduction", "accumulate": "kernel"}`` the contraction and the split reduction (no temporary;
+    the step that writes the output must run on one of these two kernels, else ``NotImplementedError`` at bind).  (1, 0), the
+    default, is the code path without any of this.  DESIGN.md section 3m.
 
     Aliasing: an output handed in through *out_dict* may not share a byte with any input, nor with another output
     (``InvalidParameterError``, raised before anything is allocated, prepared or launched, under every transform): the

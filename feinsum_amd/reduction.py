@@ -23,8 +23,9 @@ from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 
 from feinsum_amd import _hip
-from feinsum_amd.contraction import (AUTO_MIN_K, AUTO_MIN_M, AUTO_MIN_MN, AUTO_MIN_N, Step, _desc, _extents, _split,
-                                     contraction_sizes, intermediate_shapes, plan_step_dtypes, plan_steps)
+from feinsum_amd.contraction import (AUTO_MIN_K, AUTO_MIN_M, AUTO_MIN_MN, AUTO_MIN_N, Step, _contract_acc_call, _desc,
+                                     _extents, _split, contraction_sizes, intermediate_shapes, plan_step_dtypes,
+                                     plan_steps)
 from feinsum_amd.contraction_schedule import ContractionSchedule
 from feinsum_amd.einsum import BatchedEinsum
 
@@ -168,6 +169,18 @@ def plan_reduction(einsum: BatchedEinsum, sizes: Mapping[str, int],
     return tuple(plan)
 
 
+def check_accumulating_plan(plan: Sequence[Tuple[Step, str]]) -> None:
+    """``NotImplementedError`` unless the step of *plan* (:func:`plan_reduction`) that writes the einsum's output can
+    accumulate inside its kernel (``{"accumulate": "kernel"}``): a ``"reduce"`` step (``fe_einsum_reduce_acc``) or a
+    ``"contract"`` step (``fe_einsum_contract_acc``).  A ``"generic"`` last step has no accumulating form."""
+    for st, how in plan:
+        if st.result is None and how == "generic":
+            raise NotImplementedError(
+                f"the step '{st.subscripts}' that writes the output runs on the generic kernel, which has no accumulating"
+                ' form: {"accumulate": "kernel"} needs a split-reduction or contraction last step (use'
+                ' {"accumulate": "axpby"} or another schedule)')
+
+
 def _auto_contract(subscripts: str, extent: Mapping[str, int]) -> bool:
     _, M, N, K = contraction_sizes(subscripts, extent)
     return M >= AUTO_MIN_M and N >= AUTO_MIN_N and K >= AUTO_MIN_K and M * N >= AUTO_MIN_MN
@@ -178,12 +191,19 @@ class ReductionLaunch:
 
     The intermediates and the one workspace every split launch shares (the launches run one after the other on one
     stream) are allocated on *stream*, as ``ContractionLaunch`` allocates its intermediates; a launch on another stream
-    marks them with ``record_stream``."""
+    marks them with ``record_stream``.
+
+    *scale* = ``(alpha, beta)``: the launch accumulates, ``out <- alpha E + beta out``, inside the step that writes each
+    row's output -- ``fe_einsum_reduce_acc`` for a ``"reduce"`` step (its combine launch), ``fe_einsum_contract_acc`` for a
+    ``"contract"`` step; the earlier steps, the intermediates and the workspace are those of the overwriting launch.
+    ``NotImplementedError`` (:func:`check_accumulating_plan`) before anything is allocated for a ``"generic"`` last
+    step."""
 
     entry_point = "fe_einsum_reduce"
 
     def __init__(self, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any],
-                 sizes: Mapping[str, int], schedule: Optional[ContractionSchedule] = None, stream: Any = None) -> None:
+                 sizes: Mapping[str, int], schedule: Optional[ContractionSchedule] = None, stream: Any = None,
+                 scale: Optional[Tuple[float, float]] = None) -> None:
         import contextlib
 
         import torch
@@ -191,6 +211,10 @@ class ReductionLaunch:
         check_reduction(einsum, sizes)
         extent = _extents(einsum, sizes)
         self.plan = plan_reduction(einsum, sizes, schedule)
+        self.scale = scale
+        if scale is not None:
+            check_accumulating_plan(self.plan)
+            self.entry_point = "fe_einsum_reduce_acc"
         steps = [st for st, _ in self.plan]
         # (one launch of the whole einsum: no intermediates, and each row computes in its own np.result_type)
         step_dtypes: Tuple[np.dtype, ...] = plan_step_dtypes(einsum, steps) if len(steps) > 1 else ()
@@ -211,15 +235,18 @@ class ReductionLaunch:
                 d = _desc(st.subscripts, tensors, extent, dtypes)
                 if how == "reduce":
                     ws_bytes = max(ws_bytes, _hip.einsum_reduce_plan(d)[2])
-                pending.append((how, d, [t.data_ptr() for t in tensors], target.data_ptr()))
+                acc = scale is not None and st.result is None
+                pending.append((how, acc, d, [t.data_ptr() for t in tensors], target.data_ptr()))
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             self.workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
         ws = self.workspace.data_ptr() if self.workspace is not None else 0
         self._keep = (arg_dict, outs)
         self.launches = []
-        for how, d, ops, out_ptr in pending:
+        for how, acc, d, ops, out_ptr in pending:
             if how == "reduce":
-                self.launches.append((_reduce_call(ws, ws_bytes), d, ops, out_ptr))
+                self.launches.append((_reduce_call(ws, ws_bytes, scale if acc else None), d, ops, out_ptr))
+            elif acc:   # (check_accumulating_plan: a "contract" step)
+                self.launches.append((_contract_acc_call(*scale), d, ops, out_ptr))
             else:
                 self.launches.append((_hip.einsum_contract if how == "contract" else _hip.einsum_generic,
                                       d, ops, out_ptr))
@@ -243,12 +270,16 @@ class ReductionLaunch:
         return _hip.time_with_events(self.launch, n, stream_ptr)
 
 
-def _reduce_call(ws: int, ws_bytes: int):
+def _reduce_call(ws: int, ws_bytes: int, scale: Optional[Tuple[float, float]] = None):
     def call(desc: "_hip.EinsumDesc", operands: Sequence[int], out: int, stream: int) -> None:
-        _hip.einsum_reduce(desc, operands, out, ws, ws_bytes, stream)
+        if scale is None:
+            _hip.einsum_reduce(desc, operands, out, ws, ws_bytes, stream)
+        else:
+            _hip.einsum_reduce_acc(desc, operands, out, ws, ws_bytes, scale[0], scale[1], stream)
+    call.entry_point = "fe_einsum_reduce" if scale is None else "fe_einsum_reduce_acc"
     return call
 
 
 __all__ = ["REDUCE_MAX_OUT", "REDUCE_MIN_SUM", "REDUCE_MAX_TILES", "REDUCE_STREAM_FACTOR", "reduction_sizes",
            "reduce_path", "split_path", "auto_picks_reduction", "check_reduction", "streams_in_one_launch",
-           "plan_reduction", "ReductionLaunch"]
+           "plan_reduction", "check_accumulating_plan", "ReductionLaunch"]

@@ -652,6 +652,18 @@ int fe_einsum_generic(const fe_einsum_desc* desc, const void* const* operands,
  * `stream`, no allocation.  Mixed float32 / float64 operands (FE_DTYPE_OPERAND_F32) run the float64 kernel.  A summed extent of 0 writes zeros; an empty output launches nothing. */
 int fe_einsum_contract(const fe_einsum_desc* desc, const void* const* operands, void* out, void* stream);
 
+/* The contraction that adds onto what its output already holds, inside the kernel's store epilogue:
+ *   out <- alpha * E + beta * out,      E what fe_einsum_contract stores for the same arguments, bit for bit.
+ * Descriptor, operands, output, alignment and every error as fe_einsum_contract (n_operands != 2: FE_EUNSUPPORTED); in
+ * addition alpha and beta must be finite (FE_EINVAL before any device work); they are cast to float for a float32
+ * output.  The combine is fma(alpha, E, beta * out) as in fe_facemass_acc_f64 and fe_axpby: two roundings at most, none
+ * when alpha and beta are signed powers of two and E is exact.  beta == 0 does not read out (what it holds, NaN and
+ * infinity included, does not reach the result) and stores alpha * E, also for alpha == 0.  A summed extent of 0 gives
+ * E = 0: out <- beta * out, or alpha * 0 with beta == 0.  An empty output launches nothing.  Every entry is read and
+ * written by the same thread, so out may hold any earlier result, but it may not overlap an operand. */
+int fe_einsum_contract_acc(const fe_einsum_desc* desc, const void* const* operands, void* out, double alpha, double beta,
+                           void* stream);
+
 /* The index groups fe_einsum_contract forms for `desc` (host only, no device work): out_group[k] for output index k,
  * sum_group[k] for summed index k, each FE_CONTRACT_*; m / n are named before the launcher's orientation swap.
  * The dtype field is ignored: the groups depend on the strides alone. */
@@ -689,6 +701,16 @@ int fe_einsum_reduce_plan(const fe_einsum_desc* desc, int32_t* path, int64_t* sl
  * writes zeros; an empty output launches nothing. */
 int fe_einsum_reduce(const fe_einsum_desc* desc, const void* const* operands, void* out, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* The split reduction that adds onto what its output already holds: out <- alpha * E + beta * out, E what
+ * fe_einsum_reduce stores for the same arguments, bit for bit (the partials, the slices and the order of the sum are its
+ * own; the launch that sums the partials combines -- on either path).  fe_einsum_reduce_plan serves both.  Descriptor,
+ * operands, output, workspace, alignment and every error as fe_einsum_reduce; in addition alpha and beta must be finite
+ * (FE_EINVAL before any device work); they are cast to float for a float32 output.  The combine, the beta == 0 rule
+ * (out is not read), alpha == 0 and a summed extent of 0 are those of fe_einsum_contract_acc.  An empty output launches
+ * nothing.  out may not overlap an operand or the workspace. */
+int fe_einsum_reduce_acc(const fe_einsum_desc* desc, const void* const* operands, void* out, void* workspace,
+                         size_t workspace_bytes, double alpha, double beta, void* stream);
 
 /* ---- adjoint kernels of the DG families (feinsum_amd/csrc/fe_adjoint.h) ----
  *
