@@ -162,6 +162,8 @@ SIGNATURES = {
     "fe_opgrad_f64": (_int, [_p, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _p, _size,
                           _p]),
     "fe_facemass_opgrad_f64": (_int, [_p, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _size, _p]),
+    "fe_elemop_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
+    "fe_elemop_supported": (_int, [_i32, _i32]),
 }
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
@@ -399,6 +401,21 @@ def div3d_acc(J: int, D: int, u: int, out: int, E: int, Np: int, alpha: float, b
               stream: int = 0) -> None:
     """``out <- alpha * div(u) + beta * out`` inside the matrix-core kernel (fe_div3d_acc_f64); as :func:`grad3d_acc`."""
     check(load_library().fe_div3d_acc_f64(J, D, u, out, E, Np, op_flags, float(alpha), float(beta), stream))
+
+
+def elemop(J: Optional[int], A: int, u: Sequence[int], out: Sequence[int], E: int, Ni: int, Nj: int, op_flags: int = 0,
+           stream: int = 0) -> None:
+    """The element-local operator of any shape on the matrix cores (fe_elemop_f64): ``out_k[e, i] = [J[e]] sum_j A[i, j]
+    u_k[e, j]``, A ``(Ni, Nj)`` or stored ``(Nj, Ni)`` with ``OP_TRANSPOSED``.  NotImplementedError: (Ni, Nj) outside
+    :func:`elemop_supported`."""
+    if len(u) != len(out):
+        raise InvalidParameterError("elemop: need as many outputs as fields")
+    check(load_library().fe_elemop_f64(J, A, _ptr_array(u), _ptr_array(out), E, Ni, Nj, len(u), op_flags, stream))
+
+
+def elemop_supported(Ni: int, Nj: int) -> bool:
+    """The size rule of fe_elemop_f64, asked of the library (host only: no device needed)."""
+    return bool(load_library().fe_elemop_supported(int(Ni), int(Nj)))
 
 
 def axpby(out: int, x: int, n: int, alpha: float, beta: float, float64: bool = True, stream: int = 0) -> None:
@@ -722,6 +739,7 @@ def last_launch_info() -> dict:
     d["element_slice"] = bool(d["kind"] & 128)           # fe_grad3d_strided_f64 / fe_div3d_strided_f64 / fe_facemass_strided_f64
     d["float32_results"] = bool(d["kind"] & 256)         # fe_grad3d_mixed_state_f64 / fe_div3d_... / fe_facemass_mixed_state_f64
     d["dword_stores"] = bool(d["kind"] & 512)            # ... with one float per lane instead of 16-byte stores
+    d["element_operator"] = bool(d["kind"] & 1024)       # fe_elemop_f64
     d["kind"] = "B build interleaved" if d["kind"] & 4 else "default"
     return d
 

@@ -258,6 +258,9 @@ def evaluate_differentiable(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[st
     if isinstance(transform, (str, Mapping)) and (transform if isinstance(transform, str) else transform.get("variant")) == "mixed_state":
         raise NotImplementedError("evaluate_differentiable: transform 'mixed_state' rounds its float64 results to float32 and has no "
                                   "backward pass; differentiate under 'mixed_family' or 'auto'")
+    if isinstance(transform, (str, Mapping)) and (transform if isinstance(transform, str) else transform.get("variant")) == "element_operator":
+        raise NotImplementedError("evaluate_differentiable: transform 'element_operator' has no backward pass yet (its u-adjoint is the "
+                                  "same kernel with the transposed operator); differentiate under 'auto'")
     if _FN is None:
         _FN = _function()
     q = _as_queue(cq)

@@ -22,6 +22,7 @@
 #include "../../include/feinsum_hip.h"
 #include "fe_common.h"
 #include "fe_adjoint.h"
+#include "fe_elemop.h"
 #include "fe_opgrad.h"
 #include "fe_contract.h"
 #include "fe_div.h"
@@ -3949,6 +3950,74 @@ int fe_facemass_opgrad_f64(const double* J, const double* const* g, const double
             default: return launch_opgrad_partial<6, 21, true>(ga, slices, s);
         }
     });
+}
+
+}  // extern "C"
+
+// ---- element-local operator of any shape (fe_elemop.h) ----
+namespace {
+
+constexpr int kKindElementOperator = 1024;   // fe_last_launch_info `kind`
+
+// the largest dynamic LDS of the shapes that run on elemop_kernel<RT>: what the residency of the instantiation is checked at
+int elemop_lds_max(int rt) {
+    int most = 0;
+    for (int ni = 16 * rt - 15; ni <= 16 * rt; ++ni)
+        for (int nj = 1; nj <= fe::kElemOpMaxN; ++nj)
+            if (fe::elemop_supported(ni, nj)) most = std::max(most, fe::elemop_lds_bytes(ni, nj));
+    return most;
+}
+
+template <int RT>
+int launch_elemop(const fe::ElemOpArgs& g, hipStream_t s) {
+    static const std::string what = "element operator RT=" + std::to_string(RT);
+    if (int rc = configured<fe::elemop_kernel<RT>>(what.c_str(), elemop_lds_max(RT), fe::kElemOpThreads, 2)) return rc;
+    const unsigned grid = persistent_grid(g.n_tiles * g.nb, fe::kElemOpWaves);
+    hipLaunchKernelGGL(fe::elemop_kernel<RT>, dim3(grid), dim3(fe::kElemOpThreads), fe::elemop_lds_bytes(g.Ni, g.Nj), s, g);
+    FE_HIP_CHECK(hipGetLastError());
+    note_launch(false, 0, grid, fe::kElemOpWaves, g.n_tiles, g.n_tiles, kKindElementOperator);
+    return FE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fe_elemop_supported(int32_t Ni, int32_t Nj) { return fe::elemop_supported(Ni, Nj) ? 1 : 0; }
+
+int fe_elemop_f64(const double* J, const double* A, const double* const* u, double* const* out, int64_t E, int32_t Ni,
+                  int32_t Nj, int32_t b, int32_t op_flags, void* stream) {
+    forget_last_launch();
+    const bool sized = Ni > 0 && Nj > 0;
+    // (J is optional: where it is null the operator stands in for it in the check of pointers)
+    CallCheck c = {"elemop", J ? static_cast<const void*>(J) : A, A, ptr_table(u), ptr_table(out), E,
+                   sized ? std::max(Ni, Nj) : std::min(Ni, Nj), b, op_flags, FE_OP_TRANSPOSED};
+    FE_CHECK_CALL(c);
+    if (!fe::elemop_supported(Ni, Nj))
+        return fail(FE_EUNSUPPORTED, "elemop: (Ni, Nj) = (%d, %d) is outside the size rule (1 <= Ni, Nj <= %d and "
+                    "ceil(Ni / 16) * ceil(Nj / 4) <= %d)", Ni, Nj, fe::kElemOpMaxN, fe::kElemOpMaxFragments);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t n_tiles = (E + 15) / 16;
+    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {     // at most kMaxFields fields per launch
+        fe::ElemOpArgs g = {};
+        g.J = J, g.A = A, g.E = E, g.n_tiles = n_tiles;
+        g.Ni = Ni, g.Nj = Nj, g.KS = fe::elemop_k_steps(Nj), g.nb = std::min(b - k0, fe::kMaxFields);
+        g.opT = (op_flags & FE_OP_TRANSPOSED) ? 1 : 0;
+        g.buf_doubles = fe::elemop_buffer_doubles(Ni, Nj);
+        g.magic_ni = (unsigned)(((1u << 20) + Ni - 1) / Ni);
+        for (int k = 0; k < g.nb; ++k) g.f.v[k] = u[k0 + k], g.f.out[k] = out[k0 + k];
+        int rc;
+        switch (fe::elemop_row_tiles(Ni)) {
+            case 1: rc = launch_elemop<1>(g, s); break;
+            case 2: rc = launch_elemop<2>(g, s); break;
+            case 3: rc = launch_elemop<3>(g, s); break;
+            case 4: rc = launch_elemop<4>(g, s); break;
+            case 5: rc = launch_elemop<5>(g, s); break;
+            default: rc = launch_elemop<6>(g, s); break;
+        }
+        if (rc != FE_OK) return rc;
+    }
+    return FE_OK;
 }
 
 }  // extern "C"

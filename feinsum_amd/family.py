@@ -335,3 +335,71 @@ def match_operator_adjoint(einsum: BatchedEinsum) -> Optional[AdjointPlan]:
             params = {"nf": shape[0], "Np": shape[1], "Nfp": shape[2]}
         return AdjointPlan(kind, flags, role, dict(mapping), params)
     return None
+
+
+# --------------------------------------------------------------------------
+# the element-local operator of any shape: 'ij,ej->ei' / 'e,ij,ej->ei' with Ni != Nj, and square
+# sizes the MATAPPLY family has no matrix-core kernel for.  A matcher of its own -- match_family and "auto" are untouched;
+# only transform="element_operator" reaches the kernel of csrc/fe_elemop.h.
+# --------------------------------------------------------------------------
+
+ELEMENT_OPERATOR_MAX_N = 96           # fe::kElemOpMaxN
+ELEMENT_OPERATOR_MAX_FRAGMENTS = 64   # fe::kElemOpMaxFragments: the operator image, 512 bytes per fragment, stays within 32 KiB
+ELEMENT_OPERATOR_RULE = ("the element-local operator 'ij,ej->ei' or 'e,ij,ej->ei' (operator 'ij' or 'ji'; up to index renaming and "
+                         "operand order), every operand float64, fixed extents 1 <= Ni, Nj <= 96 with ceil(Ni / 16) * ceil(Nj / 4) "
+                         "<= 64 (the operator's matrix-core image and four wave tiles fit half a CU's LDS)")
+
+_ELEMENT_OPERATOR_TEMPLATES = (
+    (0, "e,ij,ej->ei", ("J", "A", "u")),
+    (OP_TRANSPOSED, "e,ji,ej->ei", ("J", "A", "u")),
+    (0, "ij,ej->ei", ("A", "u")),
+    (OP_TRANSPOSED, "ji,ej->ei", ("A", "u")),
+)
+
+
+def element_operator_supported(Ni: int, Nj: int) -> bool:
+    """The size rule of ``fe_elemop_f64`` (``fe_elemop_supported`` in C says the same): a pure function of (Ni, Nj)."""
+    Ni, Nj = int(Ni), int(Nj)
+    return (1 <= Ni <= ELEMENT_OPERATOR_MAX_N and 1 <= Nj <= ELEMENT_OPERATOR_MAX_N
+            and ((Ni + 15) // 16) * ((Nj + 3) // 4) <= ELEMENT_OPERATOR_MAX_FRAGMENTS)
+
+
+@dataclass(frozen=True)
+class ElementOperatorPlan:
+    """How ``fe_elemop_f64`` evaluates an einsum: ``layout_flags`` (``OP_TRANSPOSED``), ``roles`` (``"J"`` -- three-operand
+    forms only --, ``"A"``, ``"u"`` -> operand position), the einsum's letter of the element axis and ``params`` (Ni, Nj)."""
+
+    layout_flags: int
+    roles: Dict[str, int]
+    long_index: str
+    params: Dict[str, int]
+
+    name = "element_operator"
+
+
+def match_element_operator(einsum: BatchedEinsum) -> Optional[ElementOperatorPlan]:
+    """The :class:`ElementOperatorPlan` of an element-local operator -- :data:`ELEMENT_OPERATOR_RULE` -- else ``None``."""
+    if {np.dtype(dt) for dt in einsum.arg_to_dtype.values()} != {np.dtype("float64")}:
+        return None
+    for flags, subscripts, roles in _ELEMENT_OPERATOR_TEMPLATES:
+        m = _match_template(einsum, subscripts)
+        if m is None:
+            continue
+        perm, mapping = m
+        dim = lambda t: einsum.index_to_dim_length[mapping[t]]  # noqa: E731
+        if isinstance(dim("i"), SizeParam) or isinstance(dim("j"), SizeParam):
+            continue
+        if not element_operator_supported(int(dim("i")), int(dim("j"))):
+            continue
+        return ElementOperatorPlan(flags, {role: perm[k] for k, role in enumerate(roles)}, mapping["e"],
+                                   {"Ni": int(dim("i")), "Nj": int(dim("j"))})
+    return None
+
+
+def element_operator_groups(plan: ElementOperatorPlan, einsum: BatchedEinsum) -> list:
+    """The rows of each launch, as ``range`` objects: consecutive rows that share A (and J) -- the rule of
+    ``measure._family_groups``; rows that share them without being neighbours launch separately."""
+    role = plan.roles
+    key = lambda row: (row[role["J"]].name if "J" in role else None, row[role["A"]].name)   # noqa: E731
+    starts = [k for k, row in enumerate(einsum.args) if k == 0 or key(row) != key(einsum.args[k - 1])]
+    return [range(k, k2) for k, k2 in zip(starts, starts[1:] + [len(einsum.args)])]

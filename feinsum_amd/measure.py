@@ -31,7 +31,10 @@ Argument conventions kept from the reference:
                ``"mixed_family"``: grad, div and face-mass with float32 fields in float64 geometry factors and
                operators, for the einsums ``family.match_mixed_family`` recognises only, DESIGN.md §3j;
                ``"mixed_state"``: the same einsums with float32 RESULTS -- float64 arithmetic, one rounding to nearest
-               where a result is stored, outputs allocated and expected as float32); in a dict, ``"prepared": True`` lets a
+               where a result is stored, outputs allocated and expected as float32; ``"element_operator"``: the
+               element-local operator ``ij,ej->ei`` / ``e,ij,ej->ei`` of any shape within ``family.ELEMENT_OPERATOR_RULE`` --
+               rectangular, or square at any size -- on the matrix cores, for the einsums ``family.match_element_operator``
+               recognises only); in a dict, ``"prepared": True`` lets a
                bound launch (``timeit``) use a prepared copy of its operator
                matrices; ``"placement"`` (or ``$FEINSUM_PLACEMENT``): ``timeit``
                allocates one array per operand as the reference does; with the
@@ -70,8 +73,8 @@ from feinsum_amd.einsum import INT_CLASSES, BatchedEinsum, SizeParam
 from feinsum_amd.adjoint import AdjointLaunch
 from feinsum_amd.family import (FAMILY_DIV, FAMILY_DIVCOMP, FAMILY_FACEMASS, FAMILY_GRAD,
                                 FAMILY_GRADPLANES, OP_J_ES, KernelPlan,
-                                MIXED_FAMILY_RULE, match_adjoint_family, match_family, match_mixed_family,
-                                match_operator_adjoint)
+                                ELEMENT_OPERATOR_RULE, MIXED_FAMILY_RULE, element_operator_groups, match_adjoint_family,
+                                match_element_operator, match_family, match_mixed_family, match_operator_adjoint)
 
 logger = logging.getLogger(__name__)
 
@@ -599,9 +602,17 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     ``"operator_adjoint"`` (that transform only: ``family.match_operator_adjoint``, else ``NotImplementedError``) the
     operator-gradient kernels.  ``"mixed_family"`` (that transform only: ``family.match_mixed_family``, else
     ``NotImplementedError`` naming the rule) runs the DG kernels for float32 fields, and ``"mixed_state"`` (that transform
-    only, the same einsums, the same error) their forms with float32 results.
+    only, the same einsums, the same error) their forms with float32 results.  ``"element_operator"`` (that transform only:
+    ``family.match_element_operator``, else ``NotImplementedError`` naming ``family.ELEMENT_OPERATOR_RULE``) runs the
+    element-local operator of any shape on the matrix cores.
     """
     variant = _variant_from_transform(transform)
+    if variant == "element_operator":
+        if match_element_operator(einsum) is None:
+            raise NotImplementedError(
+                f"transform 'element_operator': einsum '{einsum.get_subscripts()}' x {einsum.b} is not {ELEMENT_OPERATOR_RULE}"
+                " (feinsum_amd.family.match_element_operator, ELEMENT_OPERATOR_RULE)")
+        return "element_operator"
     if variant in ("mixed_family", "mixed_state"):
         if match_mixed_family(einsum) is None:
             raise NotImplementedError(
@@ -737,6 +748,38 @@ class _MixedStateLaunch:
     def launch(self, stream_ptr: int) -> None:
         for fn, args in self.calls:
             fn(*args, stream=stream_ptr)
+
+    def time_batch(self, n: int, stream_ptr: int) -> float:
+        return _hip.time_with_events(self.launch, n, stream_ptr)
+
+
+class _ElementOperatorLaunch:
+    """The element-local operator of any shape (transform ``"element_operator"``): the named entry point ``fe_elemop_f64``,
+    one call per group of ``family.element_operator_groups``.  No prepared operators; a launch of its own in a bound
+    operator (``operator._merge`` fuses ``_FamilyLaunch`` stages only)."""
+
+    entry_point = "fe_elemop_f64"
+
+    def __init__(self, plan: Any, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any]) -> None:
+        self.plan = plan
+        self._keep = (arg_dict, outs)
+        role, rows, p = plan.roles, einsum.args, plan.params
+        u_axis = einsum.in_idx_sets[role["u"]].index(plan.long_index)
+        self.E = int(arg_dict[rows[0][role["u"]].name].shape[u_axis])
+        self.calls = []      # (arguments of _hip.elemop in front of the stream)
+        self.rows = []       # the rows of every call
+        for group in element_operator_groups(plan, einsum):
+            first = rows[group[0]]
+            J = arg_dict[first[role["J"]].name].data_ptr() if "J" in role else None
+            A = arg_dict[first[role["A"]].name].data_ptr()
+            uptrs = [arg_dict[rows[m][role["u"]].name].data_ptr() for m in group]
+            optrs = [outs[m].data_ptr() for m in group]
+            self.rows.append(tuple(group))
+            self.calls.append((J, A, uptrs, optrs, self.E, p["Ni"], p["Nj"], plan.layout_flags))
+
+    def launch(self, stream_ptr: int) -> None:
+        for args in self.calls:
+            _hip.elemop(*args, stream=stream_ptr)
 
     def time_batch(self, n: int, stream_ptr: int) -> float:
         return _hip.time_with_events(self.launch, n, stream_ptr)
@@ -901,6 +944,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
                 sliced.append(name)
     _refuse_aliased_outputs(einsum, arg_dict, given)     # before anything is allocated, prepared or launched
     alpha, beta = _check_scale(alpha, beta)
+    if _variant_from_transform(transform) == "element_operator":
+        launch_kind(einsum, transform, sizes)            # (likewise: the size rule refuses before anything is allocated)
     if sliced:                                           # (likewise: which launches take slices, and how their fields group)
         if not accepts_element_slices(einsum, transform, alpha, beta):
             raise InvalidParameterError(f"argument '{sliced[0]}' must be C-contiguous for this launch: {ELEMENT_SLICE_RULE}")
@@ -943,6 +988,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
         bound = _FamilyLaunch(match_mixed_family(einsum), einsum, arg_dict, outs, None)
     elif kind == "mixed_state":      # (float32 outputs: result_dtype; accumulation by "axpby" with float32 temporaries)
         bound = _MixedStateLaunch(match_mixed_family(einsum), einsum, arg_dict, outs)
+    elif kind == "element_operator":  # (accumulation: the "axpby" route only)
+        bound = _ElementOperatorLaunch(match_element_operator(einsum), einsum, arg_dict, outs)
     elif kind == "family" and sliced:
         bound = _StridedFamilyLaunch(match_family(einsum), einsum, arg_dict, outs)
     elif kind == "family":

@@ -762,6 +762,23 @@ int fe_facemass_opgrad_f64(const double* J, const double* const* g, const double
                            int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- the element-local operator of any shape (feinsum_amd/csrc/fe_elemop.h) ----
+ *
+ *   out_k[e][i] = sum_j A[i][j] * u_k[e][j]                    'ij,ej->ei' x b          J == NULL
+ *   out_k[e][i] = J[e] * (sum_j A[i][j] * u_k[e][j])           'e,ij,ej->ei' x b
+ * A [Ni][Nj], or stored [Nj][Ni] with FE_OP_TRANSPOSED in op_flags; u_k [E][Nj], out_k [E][Ni], b >= 1 fields that share A
+ * (and J); float64, every array C-contiguous and 8-byte aligned (no more is asked).  On the matrix cores, rectangular and square:
+ * fe_elemop_supported(Ni, Nj) != 0 -- 1 <= Ni, Nj <= 96 and ceil(Ni / 16) * ceil(Nj / 4) <= 64 -- else FE_EUNSUPPORTED.
+ * Every sum runs over j ascending, four j per matrix instruction; the factor J[e] is applied to the finished sum (one more
+ * rounding).  Results are bitwise reproducible and do not depend on E, on where the arrays lie or on b.
+ * Checks, all before any device work: E < 0, Ni or Nj <= 0, b < 1, stray flag bits, a null pointer table, a pointer that is not
+ * 8-byte aligned: FE_EINVAL; E == 0 launches nothing (FE_OK); then null device pointers and E * max(Ni, Nj) >= 2^39: FE_EINVAL; then
+ * the size rule.  Asynchronous on `stream`, re-entrant: no allocation, no workspace, no state.  fe_last_launch_info: `kind` bit
+ * 1024, tiles = ceil(E / 16) (per field), static walk.  Not a family of fe_launch. */
+int fe_elemop_f64(const double* J, const double* A, const double* const* u, double* const* out, int64_t E, int32_t Ni,
+                  int32_t Nj, int32_t b, int32_t op_flags, void* stream);
+int fe_elemop_supported(int32_t Ni, int32_t Nj);   /* host only: needs no device */
+
 #ifdef __cplusplus
 }
 #endif
