@@ -162,6 +162,8 @@ SIGNATURES = {
     "fe_opgrad_f64": (_int, [_p, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _p, _size,
                           _p]),
     "fe_facemass_opgrad_f64": (_int, [_p, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _size, _p]),
+    "fe_weightedop_f64": (_int, [_p, _p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_weightedop_supported": (_int, [_i32, _i32, _i32]),
     "fe_elemop_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
     "fe_elemop_supported": (_int, [_i32, _i32]),
 }
@@ -416,6 +418,25 @@ def elemop(J: Optional[int], A: int, u: Sequence[int], out: Sequence[int], E: in
 def elemop_supported(Ni: int, Nj: int) -> bool:
     """The size rule of fe_elemop_f64, asked of the library (host only: no device needed)."""
     return bool(load_library().fe_elemop_supported(int(Ni), int(Nj)))
+
+
+WO_P_T = 1   # FE_WO_P_T: P stored [Nq][Ni]
+WO_A_T = 2   # FE_WO_A_T: A stored [Nj][Nq]
+
+
+def weightedop(P: int, W: int, A: int, u: Sequence[int], out: Sequence[int], E: int, Ni: int, Nq: int, Nj: int,
+               op_flags: int = 0, stream: int = 0) -> None:
+    """The weighted element operator in one matrix-core kernel (fe_weightedop_f64): ``out_k[e, i] = sum_q P[i, q] W[e, q]
+    sum_j A[q, j] u_k[e, j]``, P ``(Ni, Nq)`` or stored ``(Nq, Ni)`` with ``WO_P_T``, A ``(Nq, Nj)`` or stored ``(Nj, Nq)``
+    with ``WO_A_T``.  NotImplementedError: (Ni, Nq, Nj) outside :func:`weightedop_supported`."""
+    if len(u) != len(out):
+        raise InvalidParameterError("weightedop: need as many outputs as fields")
+    check(load_library().fe_weightedop_f64(P, W, A, _ptr_array(u), _ptr_array(out), E, Ni, Nq, Nj, len(u), op_flags, stream))
+
+
+def weightedop_supported(Ni: int, Nq: int, Nj: int) -> bool:
+    """The size rule of fe_weightedop_f64, asked of the library (host only: no device needed)."""
+    return bool(load_library().fe_weightedop_supported(int(Ni), int(Nq), int(Nj)))
 
 
 def axpby(out: int, x: int, n: int, alpha: float, beta: float, float64: bool = True, stream: int = 0) -> None:
@@ -740,6 +761,7 @@ def last_launch_info() -> dict:
     d["float32_results"] = bool(d["kind"] & 256)         # fe_grad3d_mixed_state_f64 / fe_div3d_... / fe_facemass_mixed_state_f64
     d["dword_stores"] = bool(d["kind"] & 512)            # ... with one float per lane instead of 16-byte stores
     d["element_operator"] = bool(d["kind"] & 1024)       # fe_elemop_f64
+    d["weighted_element_operator"] = bool(d["kind"] & 2048)   # fe_weightedop_f64
     d["kind"] = "B build interleaved" if d["kind"] & 4 else "default"
     return d
 

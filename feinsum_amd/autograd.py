@@ -261,6 +261,9 @@ def evaluate_differentiable(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[st
     if isinstance(transform, (str, Mapping)) and (transform if isinstance(transform, str) else transform.get("variant")) == "element_operator":
         raise NotImplementedError("evaluate_differentiable: transform 'element_operator' has no backward pass yet (its u-adjoint is the "
                                   "same kernel with the transposed operator); differentiate under 'auto'")
+    if isinstance(transform, (str, Mapping)) and (transform if isinstance(transform, str) else transform.get("variant")) == "weighted_element_operator":
+        raise NotImplementedError("evaluate_differentiable: transform 'weighted_element_operator' has no backward pass yet (its "
+                                  "u-adjoint is the same kernel with P and A exchanged and transposed); differentiate under 'auto'")
     if _FN is None:
         _FN = _function()
     q = _as_queue(cq)

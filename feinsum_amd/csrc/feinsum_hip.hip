@@ -23,6 +23,7 @@
 #include "fe_common.h"
 #include "fe_adjoint.h"
 #include "fe_elemop.h"
+#include "fe_weightedop.h"
 #include "fe_opgrad.h"
 #include "fe_contract.h"
 #include "fe_div.h"
@@ -191,6 +192,8 @@ struct CallCheck {
     int min_b = 1;
     bool scope_first = false;               // the slice entry points: the scope comes before the structure (tests pin it)
     int variant = FE_VARIANT_AUTO, variant_hi = FE_VARIANT_AUTO;
+    const void* op2 = nullptr;              // a second operator (the weighted element operator), where has_op2
+    bool has_op2 = false;
 };
 
 int check_scope(const CallCheck& c) {
@@ -225,7 +228,7 @@ int check_call(const CallCheck& c) {
     for (int i = 0; i < 3; ++i)
         if (c.ld_used[i] && c.ld[i] >= (int64_t)1 << 40)
             return fail(FE_EINVAL, "%s: leading dimension too large (%lld)", who, (long long)c.ld[i]);
-    if ((reinterpret_cast<uintptr_t>(c.J) | reinterpret_cast<uintptr_t>(c.op)) & 7u)
+    if ((reinterpret_cast<uintptr_t>(c.J) | reinterpret_cast<uintptr_t>(c.op) | reinterpret_cast<uintptr_t>(c.op2)) & 7u)
         return fail(FE_EINVAL, "%s: device pointers must be 8-byte aligned (float64 arrays: J and the operator)", who);
     for (int k = 0; k < c.b; ++k) {
         if (reinterpret_cast<uintptr_t>(c.in[k]) & (uintptr_t)(c.in_align - 1))
@@ -238,7 +241,7 @@ int check_call(const CallCheck& c) {
     if (!c.scope_first)
         if (int rc = check_scope(c)) return rc;
     if (c.E == 0) return kCheckDone;
-    if (!c.J || !c.op) return fail(FE_EINVAL, "%s: null device pointer", who);
+    if (!c.J || !c.op || (c.has_op2 && !c.op2)) return fail(FE_EINVAL, "%s: null device pointer", who);
     for (int k = 0; k < c.b; ++k)
         if (!c.in[k] || !c.out[k]) return fail(FE_EINVAL, "%s: null field pointer %d (a null device pointer)", who, k);
     if (c.E * (int64_t)c.Np >= (int64_t)1 << 39) return fail(FE_EINVAL, "%s: E*Np too large (%lld)", who, (long long)(c.E * c.Np));
@@ -4014,6 +4017,85 @@ int fe_elemop_f64(const double* J, const double* A, const double* const* u, doub
             case 4: rc = launch_elemop<4>(g, s); break;
             case 5: rc = launch_elemop<5>(g, s); break;
             default: rc = launch_elemop<6>(g, s); break;
+        }
+        if (rc != FE_OK) return rc;
+    }
+    return FE_OK;
+}
+
+}  // extern "C"
+
+// ---- weighted element operator iq,eq,qj,ej->ei (fe_weightedop.h) ----
+namespace {
+
+constexpr int kKindWeightedElementOperator = 2048;   // fe_last_launch_info `kind`
+
+// the largest dynamic LDS of the shapes that run on weightedop_kernel<RQ, RI>: what the residency of the instantiation is checked at
+int weightedop_lds_max(int rq, int ri) {
+    int most = 0;
+    for (int ni = 16 * ri - 15; ni <= 16 * ri; ++ni)
+        for (int nq = 16 * rq - 15; nq <= 16 * rq; ++nq)
+            for (int nj = 1; nj <= fe::kWtOpMaxN; ++nj)
+                if (fe::weightedop_supported(ni, nq, nj)) most = std::max(most, fe::weightedop_lds_bytes(ni, nq, nj));
+    return most;
+}
+
+template <int RQ, int RI>
+int launch_weightedop(const fe::WtOpArgs& g, hipStream_t s) {
+    static const std::string what = "weighted element operator RQ=" + std::to_string(RQ) + " RI=" + std::to_string(RI);
+    static const int lds_max = weightedop_lds_max(RQ, RI);
+    if (int rc = configured<fe::weightedop_kernel<RQ, RI>>(what.c_str(), lds_max, fe::kWtOpThreads, 2)) return rc;
+    const unsigned grid = persistent_grid(g.n_tiles, fe::kWtOpWaves);
+    hipLaunchKernelGGL((fe::weightedop_kernel<RQ, RI>), dim3(grid), dim3(fe::kWtOpThreads),
+                       fe::weightedop_lds_bytes(g.Ni, g.Nq, g.Nj), s, g);
+    FE_HIP_CHECK(hipGetLastError());
+    note_launch(false, 0, grid, fe::kWtOpWaves, g.n_tiles, g.n_tiles, kKindWeightedElementOperator);
+    return FE_OK;
+}
+
+template <int RQ>
+int launch_weightedop_rq(int ri, const fe::WtOpArgs& g, hipStream_t s) {
+    switch (ri) {
+        case 1: return launch_weightedop<RQ, 1>(g, s);
+        case 2: return launch_weightedop<RQ, 2>(g, s);
+        default: return launch_weightedop<RQ, 3>(g, s);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int fe_weightedop_supported(int32_t Ni, int32_t Nq, int32_t Nj) { return fe::weightedop_supported(Ni, Nq, Nj) ? 1 : 0; }
+
+int fe_weightedop_f64(const double* P, const double* W, const double* A, const double* const* u, double* const* out, int64_t E,
+                      int32_t Ni, int32_t Nq, int32_t Nj, int32_t b, int32_t op_flags, void* stream) {
+    forget_last_launch();
+    const bool sized = Ni > 0 && Nq > 0 && Nj > 0;
+    CallCheck c = {"weightedop", W, A, ptr_table(u), ptr_table(out), E,
+                   sized ? std::max(Ni, std::max(Nq, Nj)) : std::min(Ni, std::min(Nq, Nj)), b, op_flags, FE_WO_P_T | FE_WO_A_T};
+    c.op2 = P, c.has_op2 = true;
+    FE_CHECK_CALL(c);
+    if (!fe::weightedop_supported(Ni, Nq, Nj))
+        return fail(FE_EUNSUPPORTED, "weightedop: (Ni, Nq, Nj) = (%d, %d, %d) is outside the size rule (1 <= Ni, Nj <= %d, 1 <= Nq <= %d "
+                    "and both operator images with four wave buffers within %d bytes of LDS)", Ni, Nq, Nj, fe::kWtOpMaxN,
+                    fe::kWtOpMaxQ, fe::kWtOpMaxLds);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int k0 = 0; k0 < b; k0 += fe::kMaxFields) {     // at most kMaxFields fields per launch
+        fe::WtOpArgs g = {};
+        g.P = P, g.W = W, g.A = A, g.E = E, g.n_tiles = (E + 15) / 16;
+        g.Ni = Ni, g.Nq = Nq, g.Nj = Nj, g.KJ = fe::elemop_k_steps(Nj), g.KQ = fe::elemop_k_steps(Nq);
+        g.nb = std::min(b - k0, fe::kMaxFields);
+        g.pT = (op_flags & FE_WO_P_T) ? 1 : 0, g.aT = (op_flags & FE_WO_A_T) ? 1 : 0;
+        g.buf_doubles = fe::weightedop_buffer_doubles(Ni, Nq, Nj);
+        g.magic_ni = (unsigned)(((1u << 20) + Ni - 1) / Ni);
+        for (int k = 0; k < g.nb; ++k) g.f.v[k] = u[k0 + k], g.f.out[k] = out[k0 + k];
+        int rc;
+        switch (fe::elemop_row_tiles(Nq)) {
+            case 1: rc = launch_weightedop_rq<1>(fe::elemop_row_tiles(Ni), g, s); break;
+            case 2: rc = launch_weightedop_rq<2>(fe::elemop_row_tiles(Ni), g, s); break;
+            case 3: rc = launch_weightedop_rq<3>(fe::elemop_row_tiles(Ni), g, s); break;
+            default: rc = launch_weightedop_rq<4>(fe::elemop_row_tiles(Ni), g, s); break;
         }
         if (rc != FE_OK) return rc;
     }

@@ -403,3 +403,86 @@ def element_operator_groups(plan: ElementOperatorPlan, einsum: BatchedEinsum) ->
     key = lambda row: (row[role["J"]].name if "J" in role else None, row[role["A"]].name)   # noqa: E731
     starts = [k for k, row in enumerate(einsum.args) if k == 0 or key(row) != key(einsum.args[k - 1])]
     return [range(k, k2) for k, k2 in zip(starts, starts[1:] + [len(einsum.args)])]
+
+
+# --------------------------------------------------------------------------
+# the weighted element operator: 'iq,eq,qj,ej->ei' -- interpolate to a quadrature grid, weigh every
+# point of every element, project back -- in one launch.  A matcher of its own, like the one above: match_family and "auto"
+# are untouched; only transform="weighted_element_operator" reaches the kernel of csrc/fe_weightedop.h.
+# --------------------------------------------------------------------------
+
+WO_P_T = 1   # FE_WO_P_T: P stored (Nq, Ni)
+WO_A_T = 2   # FE_WO_A_T: A stored (Nj, Nq)
+WEIGHTED_ELEMENT_OPERATOR_MAX_N = 48              # fe::kWtOpMaxN: Ni, Nj
+WEIGHTED_ELEMENT_OPERATOR_MAX_Q = 64              # fe::kWtOpMaxQ: Nq
+WEIGHTED_ELEMENT_OPERATOR_MAX_LDS = 80 * 1024     # fe::kWtOpMaxLds: two blocks per CU
+WEIGHTED_ELEMENT_OPERATOR_RULE = (
+    "the weighted element operator 'iq,eq,qj,ej->ei' (P 'iq' or 'qi', A 'qj' or 'jq'; up to index renaming and operand order), "
+    "every operand float64, fixed extents 1 <= Ni, Nj <= 48 and 1 <= Nq <= 64 with 512 * (ceil(Nq / 16) * ceil(Nj / 4) + "
+    "ceil(Ni / 16) * ceil(Nq / 4)) + 32 * even(max(16 * Nj + 2, 16 * Nq + 2, 16 * (Ni | 1))) <= 81920 (both operators' "
+    "matrix-core images and four wave buffers fit half a CU's LDS)")
+
+_WEIGHTED_ELEMENT_OPERATOR_TEMPLATES = (
+    (0, "iq,eq,qj,ej->ei"),
+    (WO_P_T, "qi,eq,qj,ej->ei"),
+    (WO_A_T, "iq,eq,jq,ej->ei"),
+    (WO_P_T | WO_A_T, "qi,eq,jq,ej->ei"),
+)
+
+
+def weighted_element_operator_lds_bytes(Ni: int, Nq: int, Nj: int) -> int:
+    """Dynamic LDS of a block of ``fe_weightedop_f64`` (``fe::weightedop_lds_bytes``)."""
+    buf = (max(16 * Nj + 2, 16 * Nq + 2, 16 * (Ni | 1)) + 1) & ~1
+    return 8 * ((((Nq + 15) // 16) * ((Nj + 3) // 4) + ((Ni + 15) // 16) * ((Nq + 3) // 4)) * 64 + 4 * buf)
+
+
+def weighted_element_operator_supported(Ni: int, Nq: int, Nj: int) -> bool:
+    """The size rule of ``fe_weightedop_f64`` (``fe_weightedop_supported`` in C says the same): a pure function of
+    (Ni, Nq, Nj)."""
+    Ni, Nq, Nj = int(Ni), int(Nq), int(Nj)
+    return (1 <= Ni <= WEIGHTED_ELEMENT_OPERATOR_MAX_N and 1 <= Nj <= WEIGHTED_ELEMENT_OPERATOR_MAX_N
+            and 1 <= Nq <= WEIGHTED_ELEMENT_OPERATOR_MAX_Q
+            and weighted_element_operator_lds_bytes(Ni, Nq, Nj) <= WEIGHTED_ELEMENT_OPERATOR_MAX_LDS)
+
+
+@dataclass(frozen=True)
+class WeightedElementOperatorPlan:
+    """How ``fe_weightedop_f64`` evaluates an einsum: ``layout_flags`` (``WO_P_T | WO_A_T``), ``roles`` (``"P"``, ``"W"``,
+    ``"A"``, ``"u"`` -> operand position), the einsum's letter of the element axis and ``params`` (Ni, Nq, Nj)."""
+
+    layout_flags: int
+    roles: Dict[str, int]
+    long_index: str
+    params: Dict[str, int]
+
+    name = "weighted_element_operator"
+
+
+def match_weighted_element_operator(einsum: BatchedEinsum) -> Optional[WeightedElementOperatorPlan]:
+    """The :class:`WeightedElementOperatorPlan` of a weighted element operator -- :data:`WEIGHTED_ELEMENT_OPERATOR_RULE` --
+    else ``None``.  P and A may be the same array (the Galerkin form ``qi,eq,qj,ej->ei``)."""
+    if {np.dtype(dt) for dt in einsum.arg_to_dtype.values()} != {np.dtype("float64")}:
+        return None
+    for flags, subscripts in _WEIGHTED_ELEMENT_OPERATOR_TEMPLATES:
+        m = _match_template(einsum, subscripts)
+        if m is None:
+            continue
+        perm, mapping = m
+        dim = lambda t: einsum.index_to_dim_length[mapping[t]]  # noqa: E731
+        if any(isinstance(dim(t), SizeParam) for t in "iqj"):
+            continue
+        if not weighted_element_operator_supported(int(dim("i")), int(dim("q")), int(dim("j"))):
+            continue
+        return WeightedElementOperatorPlan(flags, {role: perm[k] for k, role in enumerate(("P", "W", "A", "u"))}, mapping["e"],
+                                           {"Ni": int(dim("i")), "Nq": int(dim("q")), "Nj": int(dim("j"))})
+    return None
+
+
+def weighted_element_operator_groups(plan: WeightedElementOperatorPlan, einsum: BatchedEinsum) -> list:
+    """The rows of each C call, as ``range`` objects: consecutive rows that share P, W and A -- the rule of
+    :func:`element_operator_groups`; rows that share them without being neighbours are calls of their own.  (A call of more
+    than 8 fields is split into kernel launches of at most 8 by the library.)"""
+    role = plan.roles
+    key = lambda row: (row[role["P"]].name, row[role["W"]].name, row[role["A"]].name)   # noqa: E731
+    starts = [k for k, row in enumerate(einsum.args) if k == 0 or key(row) != key(einsum.args[k - 1])]
+    return [range(k, k2) for k, k2 in zip(starts, starts[1:] + [len(einsum.args)])]

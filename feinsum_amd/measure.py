@@ -73,8 +73,10 @@ from feinsum_amd.einsum import INT_CLASSES, BatchedEinsum, SizeParam
 from feinsum_amd.adjoint import AdjointLaunch
 from feinsum_amd.family import (FAMILY_DIV, FAMILY_DIVCOMP, FAMILY_FACEMASS, FAMILY_GRAD,
                                 FAMILY_GRADPLANES, OP_J_ES, KernelPlan,
-                                ELEMENT_OPERATOR_RULE, MIXED_FAMILY_RULE, element_operator_groups, match_adjoint_family,
-                                match_element_operator, match_family, match_mixed_family, match_operator_adjoint)
+                                ELEMENT_OPERATOR_RULE, MIXED_FAMILY_RULE, WEIGHTED_ELEMENT_OPERATOR_RULE,
+                                element_operator_groups, match_adjoint_family, match_element_operator, match_family,
+                                match_mixed_family, match_operator_adjoint, match_weighted_element_operator,
+                                weighted_element_operator_groups)
 
 logger = logging.getLogger(__name__)
 
@@ -604,9 +606,18 @@ def launch_kind(einsum: BatchedEinsum, transform: Any, sizes: Mapping[str, int])
     ``NotImplementedError`` naming the rule) runs the DG kernels for float32 fields, and ``"mixed_state"`` (that transform
     only, the same einsums, the same error) their forms with float32 results.  ``"element_operator"`` (that transform only:
     ``family.match_element_operator``, else ``NotImplementedError`` naming ``family.ELEMENT_OPERATOR_RULE``) runs the
-    element-local operator of any shape on the matrix cores.
+    element-local operator of any shape on the matrix cores, and ``"weighted_element_operator"`` (that transform only:
+    ``family.match_weighted_element_operator``, else ``NotImplementedError`` naming
+    ``family.WEIGHTED_ELEMENT_OPERATOR_RULE``) the sandwich ``iq,eq,qj,ej->ei`` in one matrix-core kernel.
     """
     variant = _variant_from_transform(transform)
+    if variant == "weighted_element_operator":
+        if match_weighted_element_operator(einsum) is None:
+            raise NotImplementedError(
+                f"transform 'weighted_element_operator': einsum '{einsum.get_subscripts()}' x {einsum.b} is not "
+                f"{WEIGHTED_ELEMENT_OPERATOR_RULE} (feinsum_amd.family.match_weighted_element_operator, "
+                "WEIGHTED_ELEMENT_OPERATOR_RULE)")
+        return "weighted_element_operator"
     if variant == "element_operator":
         if match_element_operator(einsum) is None:
             raise NotImplementedError(
@@ -785,6 +796,37 @@ class _ElementOperatorLaunch:
         return _hip.time_with_events(self.launch, n, stream_ptr)
 
 
+class _WeightedElementOperatorLaunch:
+    """The weighted element operator ``iq,eq,qj,ej->ei`` (transform ``"weighted_element_operator"``): the named entry point
+    ``fe_weightedop_f64``, one call per group of ``family.weighted_element_operator_groups``.  No prepared operators; a
+    launch of its own in a bound operator (``operator._merge`` fuses ``_FamilyLaunch`` stages only)."""
+
+    entry_point = "fe_weightedop_f64"
+
+    def __init__(self, plan: Any, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any]) -> None:
+        self.plan = plan
+        self._keep = (arg_dict, outs)
+        role, rows, p = plan.roles, einsum.args, plan.params
+        u_axis = einsum.in_idx_sets[role["u"]].index(plan.long_index)
+        self.E = int(arg_dict[rows[0][role["u"]].name].shape[u_axis])
+        self.calls = []      # (arguments of _hip.weightedop in front of the stream)
+        self.rows = []       # the rows of every call
+        for group in weighted_element_operator_groups(plan, einsum):
+            first = rows[group[0]]
+            P, W, A = (arg_dict[first[role[r]].name].data_ptr() for r in ("P", "W", "A"))
+            uptrs = [arg_dict[rows[m][role["u"]].name].data_ptr() for m in group]
+            optrs = [outs[m].data_ptr() for m in group]
+            self.rows.append(tuple(group))
+            self.calls.append((P, W, A, uptrs, optrs, self.E, p["Ni"], p["Nq"], p["Nj"], plan.layout_flags))
+
+    def launch(self, stream_ptr: int) -> None:
+        for args in self.calls:
+            _hip.weightedop(*args, stream=stream_ptr)
+
+    def time_batch(self, n: int, stream_ptr: int) -> float:
+        return _hip.time_with_events(self.launch, n, stream_ptr)
+
+
 class _StridedFamilyLaunch:
     """float64 grad, div or face-mass of tetrahedra p = 1..4 with element slices among its arrays: the named entry points
     ``fe_grad3d_strided_f64`` / ``fe_div3d_strided_f64`` / ``fe_facemass_strided_f64``, one launch per group of
@@ -944,7 +986,7 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
                 sliced.append(name)
     _refuse_aliased_outputs(einsum, arg_dict, given)     # before anything is allocated, prepared or launched
     alpha, beta = _check_scale(alpha, beta)
-    if _variant_from_transform(transform) == "element_operator":
+    if _variant_from_transform(transform) in ("element_operator", "weighted_element_operator"):
         launch_kind(einsum, transform, sizes)            # (likewise: the size rule refuses before anything is allocated)
     if sliced:                                           # (likewise: which launches take slices, and how their fields group)
         if not accepts_element_slices(einsum, transform, alpha, beta):
@@ -990,6 +1032,8 @@ def _bind(einsum: BatchedEinsum, cq: Any, arg_dict: Mapping[str, Any],
         bound = _MixedStateLaunch(match_mixed_family(einsum), einsum, arg_dict, outs)
     elif kind == "element_operator":  # (accumulation: the "axpby" route only)
         bound = _ElementOperatorLaunch(match_element_operator(einsum), einsum, arg_dict, outs)
+    elif kind == "weighted_element_operator":  # (likewise)
+        bound = _WeightedElementOperatorLaunch(match_weighted_element_operator(einsum), einsum, arg_dict, outs)
     elif kind == "family" and sliced:
         bound = _StridedFamilyLaunch(match_family(einsum), einsum, arg_dict, outs)
     elif kind == "family":

@@ -32,7 +32,8 @@ from typing import Any, List, Mapping, Optional, Sequence, Tuple
 from feinsum_amd import _hip
 from feinsum_amd.einsum import BatchedEinsum
 from feinsum_amd.family import FAMILY_DIV, FAMILY_FACEMASS, FAMILY_GRAD
-from feinsum_amd.measure import _bind, _ElementOperatorLaunch, _FamilyLaunch, _MixedStateLaunch, _overlap, _StridedFamilyLaunch
+from feinsum_amd.measure import (_bind, _ElementOperatorLaunch, _FamilyLaunch, _MixedStateLaunch, _overlap, _StridedFamilyLaunch,
+                                 _WeightedElementOperatorLaunch)
 
 StageT = Tuple[BatchedEinsum, Mapping[str, Any]]
 
@@ -144,7 +145,7 @@ class BoundOperator:
         """C entry point behind every enqueue, in order (one per launch group)."""
         names: List[str] = []
         for b in self.launches:
-            if isinstance(b, (_StridedFamilyLaunch, _ElementOperatorLaunch)):   # element slices / "element_operator": never merged, one call per launch group
+            if isinstance(b, (_StridedFamilyLaunch, _ElementOperatorLaunch, _WeightedElementOperatorLaunch)):   # element slices / "element_operator" / "weighted_element_operator": never merged, one call per launch group
                 names += [b.entry_point] * len(b.calls)
             elif isinstance(b, _MixedStateLaunch):      # float32 fields and results: never merged, one call per launch group
                 names += [f"fe_{b.plan.name}_mixed_state"] * len(b.calls)

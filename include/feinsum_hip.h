@@ -762,6 +762,30 @@ int fe_facemass_opgrad_f64(const double* J, const double* const* g, const double
                            int32_t Np, int32_t nf, int32_t Nfp, int32_t b, int32_t layout_flags, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- the weighted element operator in one kernel (feinsum_amd/csrc/fe_weightedop.h; the two
+ * halves on their own: fe_elemop_f64 below) ----
+ *
+ *   out_k[e][i] = sum_q P[i][q] * W[e][q] * (sum_j A[q][j] * u_k[e][j])        'iq,eq,qj,ej->ei' x b
+ * Interpolation to a quadrature grid, a weight per element and point, projection back.  P [Ni][Nq], or stored [Nq][Ni] with
+ * FE_WO_P_T in op_flags; A [Nq][Nj], or stored [Nj][Nq] with FE_WO_A_T; P and A may be the same array.  W [E][Nq], u_k [E][Nj],
+ * out_k [E][Ni], b >= 1 fields that share P, W and A; float64, every array C-contiguous and 8-byte aligned (no more is asked).
+ * fe_weightedop_supported(Ni, Nq, Nj) != 0 -- 1 <= Ni, Nj <= 48, 1 <= Nq <= 64 and
+ *   512 * (ceil(Nq/16) * ceil(Nj/4) + ceil(Ni/16) * ceil(Nq/4)) + 32 * even(max(16 Nj + 2, 16 Nq + 2, 16 (Ni | 1))) <= 81920
+ * (the LDS of a block: two blocks per CU) -- else FE_EUNSUPPORTED.
+ * t[e][q] = sum_j A[q][j] u[e][j] is summed over j ascending, four j per matrix instruction; W[e][q] * t[e][q] costs one
+ * rounding; out is summed over q ascending, four q per matrix instruction.  An entry depends on row i of P, on A, on u_k[e][:]
+ * and on W[e][:] only.  Results are bitwise reproducible and do not depend on E, on where the arrays lie or on b.
+ * Checks, all before any device work: E < 0, Ni, Nq or Nj <= 0, b < 1, stray flag bits, a null pointer table, a pointer that is
+ * not 8-byte aligned: FE_EINVAL; E == 0 launches nothing (FE_OK); then null device pointers and E * max(Ni, Nq, Nj) >= 2^39:
+ * FE_EINVAL; then the size rule.  Asynchronous on `stream`, re-entrant: no allocation, no workspace, no state.
+ * fe_last_launch_info: `kind` bit 2048, tiles = ceil(E / 16) per launch (a tile carries all the fields of the launch; more than
+ * FE_MAX_FIELDS fields take further launches), static walk.  Not a family of fe_launch. */
+#define FE_WO_P_T 1   /* P stored [Nq][Ni] */
+#define FE_WO_A_T 2   /* A stored [Nj][Nq] */
+int fe_weightedop_f64(const double* P, const double* W, const double* A, const double* const* u, double* const* out, int64_t E,
+                      int32_t Ni, int32_t Nq, int32_t Nj, int32_t b, int32_t op_flags, void* stream);
+int fe_weightedop_supported(int32_t Ni, int32_t Nq, int32_t Nj);   /* host only: needs no device */
+
 /* ---- the element-local operator of any shape (feinsum_amd/csrc/fe_elemop.h) ----
  *
  *   out_k[e][i] = sum_j A[i][j] * u_k[e][j]                    'ij,ej->ei' x b          J == NULL
