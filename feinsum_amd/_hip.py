@@ -164,6 +164,8 @@ SIGNATURES = {
     "fe_facemass_opgrad_f64": (_int, [_p, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _size, _p]),
     "fe_weightedop_f64": (_int, [_p, _p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
     "fe_weightedop_supported": (_int, [_i32, _i32, _i32]),
+    "fe_weightgrad_f64": (_int, [_p, _p, _pp, _pp, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
+    "fe_weightgrad_supported": (_int, [_i32, _i32, _i32]),
     "fe_elemop_f64": (_int, [_p, _p, _pp, _pp, _i64, _i32, _i32, _i32, _i32, _p]),
     "fe_elemop_supported": (_int, [_i32, _i32]),
 }
@@ -437,6 +439,21 @@ def weightedop(P: int, W: int, A: int, u: Sequence[int], out: Sequence[int], E: 
 def weightedop_supported(Ni: int, Nq: int, Nj: int) -> bool:
     """The size rule of fe_weightedop_f64, asked of the library (host only: no device needed)."""
     return bool(load_library().fe_weightedop_supported(int(Ni), int(Nq), int(Nj)))
+
+
+def weightgrad(P: int, A: int, u: Sequence[int], g: Sequence[int], dW: int, E: int, Ni: int, Nq: int, Nj: int,
+               op_flags: int = 0, stream: int = 0) -> None:
+    """The gradient of the weighted element operator with respect to its weight (fe_weightgrad_f64): ``dW[e, q] = sum_k
+    (sum_i P[i, q] g_k[e, i]) (sum_j A[q, j] u_k[e, j])`` over at most 8 field pairs, P and A stored as for
+    :func:`weightedop`.  NotImplementedError: (Ni, Nq, Nj) outside :func:`weightgrad_supported`."""
+    if len(u) != len(g):
+        raise InvalidParameterError("weightgrad: need as many output gradients as fields")
+    check(load_library().fe_weightgrad_f64(P, A, _ptr_array(u), _ptr_array(g), dW, E, Ni, Nq, Nj, len(u), op_flags, stream))
+
+
+def weightgrad_supported(Ni: int, Nq: int, Nj: int) -> bool:
+    """The size rule of fe_weightgrad_f64, asked of the library (host only: no device needed)."""
+    return bool(load_library().fe_weightgrad_supported(int(Ni), int(Nq), int(Nj)))
 
 
 def axpby(out: int, x: int, n: int, alpha: float, beta: float, float64: bool = True, stream: int = 0) -> None:
@@ -762,6 +779,7 @@ def last_launch_info() -> dict:
     d["dword_stores"] = bool(d["kind"] & 512)            # ... with one float per lane instead of 16-byte stores
     d["element_operator"] = bool(d["kind"] & 1024)       # fe_elemop_f64
     d["weighted_element_operator"] = bool(d["kind"] & 2048)   # fe_weightedop_f64
+    d["weighted_weight_adjoint"] = bool(d["kind"] & 4096)     # fe_weightgrad_f64
     d["kind"] = "B build interleaved" if d["kind"] & 4 else "default"
     return d
 

@@ -24,6 +24,7 @@
 #include "fe_adjoint.h"
 #include "fe_elemop.h"
 #include "fe_weightedop.h"
+#include "fe_weightgrad.h"
 #include "fe_opgrad.h"
 #include "fe_contract.h"
 #include "fe_div.h"
@@ -4100,6 +4101,74 @@ int fe_weightedop_f64(const double* P, const double* W, const double* A, const d
         if (rc != FE_OK) return rc;
     }
     return FE_OK;
+}
+
+}  // extern "C"
+
+// ---- weight gradient of the weighted element operator, iq,qj,ej,ei->eq (fe_weightgrad.h) ----
+namespace {
+
+constexpr int kKindWeightedWeightAdjoint = 4096;   // fe_last_launch_info `kind`
+
+// the largest dynamic LDS of the shapes that run on wgrad_kernel<RQ>: what the residency of the instantiation is checked at
+int weightgrad_lds_max(int rq) {
+    int most = 0;
+    for (int ni = 1; ni <= fe::kWGradMaxN; ++ni)
+        for (int nq = 16 * rq - 15; nq <= 16 * rq; ++nq)
+            for (int nj = 1; nj <= fe::kWGradMaxN; ++nj)
+                if (fe::weightgrad_supported(ni, nq, nj)) most = std::max(most, fe::weightgrad_lds_bytes(ni, nq, nj));
+    return most;
+}
+
+template <int RQ>
+int launch_weightgrad(const fe::WGradArgs& g, hipStream_t s) {
+    static const std::string what = "weight gradient RQ=" + std::to_string(RQ);
+    static const int lds_max = weightgrad_lds_max(RQ);
+    if (int rc = configured<fe::wgrad_kernel<RQ>>(what.c_str(), lds_max, fe::kWGradThreads, 2)) return rc;
+    const unsigned grid = persistent_grid(g.n_tiles, fe::kWGradWaves);
+    hipLaunchKernelGGL(fe::wgrad_kernel<RQ>, dim3(grid), dim3(fe::kWGradThreads), fe::weightgrad_lds_bytes(g.Ni, g.Nq, g.Nj), s, g);
+    FE_HIP_CHECK(hipGetLastError());
+    note_launch(false, 0, grid, fe::kWGradWaves, g.n_tiles, g.n_tiles, kKindWeightedWeightAdjoint);
+    return FE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fe_weightgrad_supported(int32_t Ni, int32_t Nq, int32_t Nj) { return fe::weightgrad_supported(Ni, Nq, Nj) ? 1 : 0; }
+
+int fe_weightgrad_f64(const double* P, const double* A, const double* const* u, const double* const* g, double* dW, int64_t E,
+                      int32_t Ni, int32_t Nq, int32_t Nj, int32_t b, int32_t op_flags, void* stream) {
+    forget_last_launch();
+    const bool sized = Ni > 0 && Nq > 0 && Nj > 0;
+    // (the check of fe_weightedop_f64, its order and its texts: dW stands where W does, the g_k where the outputs do)
+    CallCheck c = {"weightgrad", dW, A, ptr_table(u), ptr_table(g), E,
+                   sized ? std::max(Ni, std::max(Nq, Nj)) : std::min(Ni, std::min(Nq, Nj)), b, op_flags, FE_WO_P_T | FE_WO_A_T};
+    c.op2 = P, c.has_op2 = true;
+    if (b > fe::kMaxFields && E >= 0 && sized)
+        return fail(FE_EINVAL, "weightgrad: b=%d, need at least one field and at most %d (the rows are summed in one launch)", b,
+                    fe::kMaxFields);
+    FE_CHECK_CALL(c);
+    if (!fe::weightgrad_supported(Ni, Nq, Nj))
+        return fail(FE_EUNSUPPORTED, "weightgrad: (Ni, Nq, Nj) = (%d, %d, %d) is outside the size rule (1 <= Ni, Nj <= %d, 1 <= Nq <= %d "
+                    "and both operator images with four wave buffers within %d bytes of LDS)", Ni, Nq, Nj, fe::kWGradMaxN,
+                    fe::kWGradMaxQ, fe::kWGradMaxLds);
+    fe::WGradArgs a = {};
+    a.P = P, a.A = A, a.dW = dW, a.E = E, a.n_tiles = (E + 15) / 16;
+    a.Ni = Ni, a.Nq = Nq, a.Nj = Nj, a.KI = fe::elemop_k_steps(Ni), a.KJ = fe::elemop_k_steps(Nj), a.nb = b;
+    a.pT = (op_flags & FE_WO_P_T) ? 1 : 0, a.aT = (op_flags & FE_WO_A_T) ? 1 : 0;
+    a.buf_doubles = fe::weightgrad_buffer_doubles(Ni, Nq, Nj);
+    a.magic_nq = (unsigned)(((1u << 20) + Nq - 1) / Nq);
+    for (int k = 0; k < b; ++k) a.item[2 * k] = u[k], a.item[2 * k + 1] = g[k];
+    for (int k = 2 * b; k < 2 * fe::kMaxFields; ++k) a.item[k] = u[0];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (fe::elemop_row_tiles(Nq)) {
+        case 1: return launch_weightgrad<1>(a, s);
+        case 2: return launch_weightgrad<2>(a, s);
+        case 3: return launch_weightgrad<3>(a, s);
+        default: return launch_weightgrad<4>(a, s);
+    }
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from itertools import permutations
-from typing import Dict, Optional, Tuple
+from typing import Dict, Iterator, Optional, Tuple
 
 import numpy as np
 
@@ -81,11 +81,16 @@ class KernelPlan:
 
 
 def _match_template(einsum: BatchedEinsum, subscripts: str) -> Optional[Tuple[Tuple[int, ...], Dict[str, str]]]:
+    return next(_template_matches(einsum, subscripts), None)
+
+
+def _template_matches(einsum: BatchedEinsum, subscripts: str) -> Iterator[Tuple[Tuple[int, ...], Dict[str, str]]]:
+    """Every (operand order, letters) under which *einsum* is the template, in the order of ``itertools.permutations``."""
     lhs, rhs = subscripts.split("->")
     t_in = [tuple(s) for s in lhs.split(",")]
     t_out = tuple(rhs)
     if len(t_in) != einsum.n or len(t_out) != len(einsum.out_idx_set):
-        return None
+        return
     for perm in permutations(range(einsum.n)):
         # template operand k <-> einsum operand perm[k]
         mapping: Dict[str, str] = {}
@@ -103,8 +108,7 @@ def _match_template(einsum: BatchedEinsum, subscripts: str) -> Optional[Tuple[Tu
             if not ok:
                 break
         if ok and len(set(mapping.values())) == len(mapping) == len(einsum.all_indices):
-            return perm, mapping
-    return None
+            yield perm, mapping
 
 
 def match_family(einsum: BatchedEinsum) -> Optional[KernelPlan]:
@@ -486,3 +490,72 @@ def weighted_element_operator_groups(plan: WeightedElementOperatorPlan, einsum: 
     key = lambda row: (row[role["P"]].name, row[role["W"]].name, row[role["A"]].name)   # noqa: E731
     starts = [k for k, row in enumerate(einsum.args) if k == 0 or key(row) != key(einsum.args[k - 1])]
     return [range(k, k2) for k, k2 in zip(starts, starts[1:] + [len(einsum.args)])]
+
+
+# --------------------------------------------------------------------------
+# the weight gradient of the weighted element operator: 'iq,qj,ej,ei->eq', what
+# adjoint_einsums(fwd, "W") builds.  A matcher of its own: match_family, match_adjoint_family, match_operator_adjoint, "auto"
+# and transform="adjoint" are untouched; only evaluate_differentiable(element_gradients="kernel") reaches the kernel of
+# csrc/fe_weightgrad.h.
+# --------------------------------------------------------------------------
+
+ADJ_WEIGHTED_W = "weighted_w"
+WEIGHTED_WEIGHT_ADJOINT_MAX_FIELDS = 8           # fe::kMaxFields: the rows one call sums
+WEIGHTED_WEIGHT_ADJOINT_RULE = (
+    "the weight gradient of the weighted element operator, 'iq,qj,ej,ei->eq' (P 'iq' or 'qi', A 'qj' or 'jq'; up to index "
+    "renaming and operand order), every operand float64, e a size parameter, all rows sharing P and A, fixed extents "
+    "1 <= Ni, Nj <= 48 and 1 <= Nq <= 64 with 512 * ceil(Nq / 16) * (ceil(Nj / 4) + ceil(Ni / 4)) + 32 * even(max(16 * Nj + 2, "
+    "16 * Ni + 2, 16 * (Nq | 1))) <= 81920 (both operators' matrix-core images and four wave buffers fit half a CU's LDS)")
+
+_WEIGHTED_WEIGHT_ADJOINT_TEMPLATES = (
+    (0, "iq,qj,ej,ei->eq"),
+    (WO_P_T, "qi,qj,ej,ei->eq"),
+    (WO_A_T, "iq,jq,ej,ei->eq"),
+    (WO_P_T | WO_A_T, "qi,jq,ej,ei->eq"),
+)
+
+
+def weighted_weight_adjoint_lds_bytes(Ni: int, Nq: int, Nj: int) -> int:
+    """Dynamic LDS of a block of ``fe_weightgrad_f64`` (``fe::weightgrad_lds_bytes``)."""
+    buf = (max(16 * Nj + 2, 16 * Ni + 2, 16 * (Nq | 1)) + 1) & ~1
+    return 8 * (((Nq + 15) // 16) * ((Nj + 3) // 4 + (Ni + 3) // 4) * 64 + 4 * buf)
+
+
+def weighted_weight_adjoint_supported(Ni: int, Nq: int, Nj: int) -> bool:
+    """The size rule of ``fe_weightgrad_f64`` (``fe_weightgrad_supported`` in C says the same): a pure function of
+    (Ni, Nq, Nj).  Every shape of :func:`weighted_element_operator_supported` is inside."""
+    Ni, Nq, Nj = int(Ni), int(Nq), int(Nj)
+    return (1 <= Ni <= WEIGHTED_ELEMENT_OPERATOR_MAX_N and 1 <= Nj <= WEIGHTED_ELEMENT_OPERATOR_MAX_N
+            and 1 <= Nq <= WEIGHTED_ELEMENT_OPERATOR_MAX_Q
+            and weighted_weight_adjoint_lds_bytes(Ni, Nq, Nj) <= WEIGHTED_ELEMENT_OPERATOR_MAX_LDS)
+
+
+def match_weighted_operator_weight_adjoint(einsum: BatchedEinsum) -> Optional[AdjointPlan]:
+    """The :class:`AdjointPlan` (kind ``"weighted_w"``; ``layout_flags``: ``WO_P_T | WO_A_T``; roles ``"P"``, ``"A"``, ``"u"``,
+    ``"g"``; params Ni, Nq, Nj) of :data:`WEIGHTED_WEIGHT_ADJOINT_RULE`, else ``None``.  P and A may be the same array; the u
+    and g operands of a row are different arrays.  The einsum is its own mirror image -- (P, g, i) for (A, u, j), both operators
+    transposed -- and both readings give the same bits (the product commutes); where both fit, the one whose g operands carry
+    the names of output gradients (``autograd.output_grad_name``) is taken, else the first."""
+    from feinsum_amd.autograd import GRAD_PREFIX
+
+    if {np.dtype(dt) for dt in einsum.arg_to_dtype.values()} != {np.dtype("float64")}:
+        return None
+    fits = []
+    for flags, subscripts in _WEIGHTED_WEIGHT_ADJOINT_TEMPLATES:
+        for perm, mapping in _template_matches(einsum, subscripts):
+            dim = lambda t: einsum.index_to_dim_length[mapping[t]]  # noqa: E731
+            if any(isinstance(dim(t), SizeParam) for t in "iqj") or not isinstance(dim("e"), SizeParam):
+                continue
+            if not weighted_weight_adjoint_supported(int(dim("i")), int(dim("q")), int(dim("j"))):
+                continue
+            role = {name: perm[k] for k, name in enumerate(("P", "A", "u", "g"))}
+            if len({(row[role["P"]].name, row[role["A"]].name) for row in einsum.args}) != 1:
+                continue      # every row shares P and A
+            if any(row[role["u"]].name == row[role["g"]].name for row in einsum.args):
+                continue
+            fits.append(AdjointPlan(ADJ_WEIGHTED_W, flags, role, dict(mapping),
+                                    {"Ni": int(dim("i")), "Nq": int(dim("q")), "Nj": int(dim("j"))}))
+    for plan in fits:
+        if all(row[plan.roles["g"]].name.startswith(GRAD_PREFIX) for row in einsum.args):
+            return plan
+    return fits[0] if fits else None

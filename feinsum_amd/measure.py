@@ -827,6 +827,42 @@ class _WeightedElementOperatorLaunch:
         return _hip.time_with_events(self.launch, n, stream_ptr)
 
 
+class _WeightGradLaunch:
+    """The weight gradient of the weighted element operator, ``iq,qj,ej,ei->eq`` with its rows summed
+    (``family.match_weighted_operator_weight_adjoint``): the named entry point ``fe_weightgrad_f64``, one call per at most 8
+    rows, call c into ``outs[c]`` -- whoever binds it adds them in that order.  Reached from the backward pass of
+    ``evaluate_differentiable(element_gradients="kernel")`` only."""
+
+    entry_point = "fe_weightgrad_f64"
+
+    def __init__(self, plan: Any, einsum: BatchedEinsum, arg_dict: Mapping[str, Any], outs: Sequence[Any]) -> None:
+        from feinsum_amd.family import WEIGHTED_WEIGHT_ADJOINT_MAX_FIELDS as per_call
+
+        self.plan = plan
+        self._keep = (arg_dict, outs)
+        role, rows, p = plan.roles, einsum.args, plan.params
+        self.E = int(arg_dict[rows[0][role["u"]].name].shape[0])
+        self.rows = [tuple(range(k, min(k + per_call, len(rows)))) for k in range(0, len(rows), per_call)]
+        if len(outs) != len(self.rows):
+            raise InvalidParameterError(f"the weight gradient of {len(rows)} rows takes {len(self.rows)} calls: one output each")
+        P, A = (arg_dict[rows[0][role[r]].name].data_ptr() for r in ("P", "A"))
+        self.calls = []      # (arguments of _hip.weightgrad in front of the stream)
+        for group, out in zip(self.rows, outs):
+            uptrs = [arg_dict[rows[m][role["u"]].name].data_ptr() for m in group]
+            gptrs = [arg_dict[rows[m][role["g"]].name].data_ptr() for m in group]
+            self.calls.append((P, A, uptrs, gptrs, out.data_ptr(), self.E, p["Ni"], p["Nq"], p["Nj"], plan.layout_flags))
+        self.accumulate = None
+        self.reads = tuple(sp for name in sorted(einsum.all_args) for sp in _spans(arg_dict[name]))
+        self.writes = tuple(_span(t) for t in outs)
+
+    def launch(self, stream_ptr: int) -> None:
+        for args in self.calls:
+            _hip.weightgrad(*args, stream=stream_ptr)
+
+    def time_batch(self, n: int, stream_ptr: int) -> float:
+        return _hip.time_with_events(self.launch, n, stream_ptr)
+
+
 class _StridedFamilyLaunch:
     """float64 grad, div or face-mass of tetrahedra p = 1..4 with element slices among its arrays: the named entry points
     ``fe_grad3d_strided_f64`` / ``fe_div3d_strided_f64`` / ``fe_facemass_strided_f64``, one launch per group of

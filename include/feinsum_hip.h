@@ -786,6 +786,26 @@ int fe_weightedop_f64(const double* P, const double* W, const double* A, const d
                       int32_t Ni, int32_t Nq, int32_t Nj, int32_t b, int32_t op_flags, void* stream);
 int fe_weightedop_supported(int32_t Ni, int32_t Nq, int32_t Nj);   /* host only: needs no device */
 
+/* ---- the gradient of the weighted element operator with respect to its weight (feinsum_amd/csrc/fe_weightgrad.h, DESIGN.md
+ * section 3s) ----
+ *
+ *   dW[e][q] = sum_k (sum_i P[i][q] * g_k[e][i]) * (sum_j A[q][j] * u_k[e][j])        'iq,qj,ej,ei->eq', b rows summed
+ * g_k [E][Ni] is the gradient of fe_weightedop_f64's output k, u_k [E][Nj] its field; P, A and op_flags (FE_WO_P_T, FE_WO_A_T) as
+ * there; dW [E][Nq] is overwritten.  1 <= b <= FE_MAX_FIELDS field pairs in one launch; float64, every array C-contiguous and
+ * 8-byte aligned.  fe_weightgrad_supported(Ni, Nq, Nj) != 0 -- 1 <= Ni, Nj <= 48, 1 <= Nq <= 64 and
+ *   512 * ceil(Nq/16) * (ceil(Nj/4) + ceil(Ni/4)) + 32 * even(max(16 Nj + 2, 16 Ni + 2, 16 (Nq | 1))) <= 81920
+ * (the LDS of a block: two blocks per CU; every shape of fe_weightedop_supported is inside) -- else FE_EUNSUPPORTED.
+ * Both inner sums run ascending, four terms per matrix instruction; the product and the sum over k are one fused multiply-add
+ * per field, fields ascending from +0.  An entry depends on column q of P, row q of A, u_k[e][:] and g_k[e][:] only.  Results are
+ * bitwise reproducible and do not depend on E or on where the arrays lie.
+ * Checks, all before any device work and in fe_weightedop_f64's order: E < 0, Ni, Nq or Nj <= 0, b < 1 or b > FE_MAX_FIELDS,
+ * stray flag bits, a null pointer table, a pointer that is not 8-byte aligned: FE_EINVAL; E == 0 launches nothing (FE_OK); then
+ * null device pointers and E * max(Ni, Nq, Nj) >= 2^39: FE_EINVAL; then the size rule.  Asynchronous on `stream`, re-entrant: no
+ * allocation, no workspace, no state.  fe_last_launch_info: `kind` bit 4096, tiles = ceil(E / 16), static walk. */
+int fe_weightgrad_f64(const double* P, const double* A, const double* const* u, const double* const* g, double* dW, int64_t E,
+                      int32_t Ni, int32_t Nq, int32_t Nj, int32_t b, int32_t op_flags, void* stream);
+int fe_weightgrad_supported(int32_t Ni, int32_t Nq, int32_t Nj);   /* host only: needs no device */
+
 /* ---- the element-local operator of any shape (feinsum_amd/csrc/fe_elemop.h) ----
  *
  *   out_k[e][i] = sum_j A[i][j] * u_k[e][j]                    'ij,ej->ei' x b          J == NULL
